@@ -8,21 +8,31 @@ x0 = 0), inputs resident in HBM.  W warm-up steps, then exactly K timed steps br
 barrier + device sync; rank 0 prints ONE JSON line.  (The convergence test is off during the timed
 region and the solve restarts from x = 0 on the device every 48 steps, so any K is valid.)
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--n GRID] [--no-cpu]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--grid GRID] [--dump-outputs DIR] [--full [--no-cpu] [--no-pmc] [--no-families]]
+
+A plain run sets up, warms up, times the K steps and prints the line; every other measurement and check
+(config.single_sweeps_same_process, roofline.back_to_back_*, config.spmv_finest_level, config.full_solve_to_1e-8,
+config.kernel_families, config.reference_level_policy, roofline.traffic, config.comm_us, config.multi_gpu_parity,
+cpu_baseline) runs with --full only and is null otherwise.
+
+--dump-outputs DIR writes what the timed path hands its caller after the last timed step, as float64 .npy files:
+x_sample.npy (the iterate x at rows x_sample_rows.npy: every row up to 2^21 rows, above that a fixed sample of 2^21
+rows drawn with seed 0; rank 0's block at N > 1) and residual_history.npy (the running solve's residual history).
+The inputs are generated, not random, so two runs with the same arguments compute the same thing.
 
 Extra objects in the line:
   "roofline"     dominant kernel = fused Jacobi sweep on the finest level.  achieved = the bytes the
                  launched layout has to move per launch (values / indices it really streams + b, x,
                  x_new; stated in DESIGN.md section 4) over the HIP-event time of those launches inside
                  the timed region; frac = achieved / 8 TB/s (<= 1 by construction).  traffic = HBM bytes
-                 per launch from rocprofv3 PMC counters collected IN THIS RUN (two child passes,
+                 per launch from rocprofv3 PMC counters collected IN THIS RUN (--full: two child passes,
                  FETCH_SIZE / WRITE_SIZE, tools/pmc_traffic.py) or null.  The SURVEY section 8d CSR
                  model (12 nnz + 36 n) is kept as csr_model_GBps / csr_model_frac: an effective rate,
                  not a roofline fraction, for layouts that do not stream CSR.
-  config.kernel_families   the same iterations with (i) constant-slot folding off, (ii) the CSR-stream
+  config.kernel_families   (--full) the same iterations with (i) constant-slot folding off, (ii) the CSR-stream
                  family forced (kind 0: reads rowptr/colindex/val exactly as the CSR model assumes),
                  (iii) sliced ELL (kind 2): it/s and dominant-kernel fraction of each.
-  "cpu_baseline" the CPU oracle timed on this host (rank 0, N=1 only): AMG-PCG it/s, bare CSR SpMV
+  "cpu_baseline" (--full) the CPU oracle timed on this host (rank 0, N=1 only): AMG-PCG it/s, bare CSR SpMV
                  GB/s and its fraction of this host's STREAM-triad rate.
 """
 from __future__ import annotations
@@ -56,6 +66,21 @@ def vcycle_bytes(levels, sweeps):
     return total
 
 
+DUMP_ROWS = 1 << 21  # rows of x that --dump-outputs writes: 2 x 16 MB in float64 (values + row numbers)
+
+
+def dump_outputs(out_dir, A, x_dev, nloc, hist):
+    """--dump-outputs: the iterate x after the last timed step (a seeded sample of DUMP_ROWS rows when it has more) and the
+    running solve's residual history -- what krylov_step_dev / krylov_history hand their caller -- as float64 .npy files."""
+    os.makedirs(out_dir, exist_ok=True)
+    x = np.empty(nloc)
+    A.d2h(x, x_dev)
+    rows = np.arange(nloc) if nloc <= DUMP_ROWS else np.sort(np.random.default_rng(0).choice(nloc, DUMP_ROWS, replace=False))
+    np.save(os.path.join(out_dir, "x_sample.npy"), x[rows])
+    np.save(os.path.join(out_dir, "x_sample_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "residual_history.npy"), np.asarray(hist, dtype=np.float64))
+
+
 T0 = time.time()
 
 
@@ -70,15 +95,21 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--grid", type=int, default=int(os.environ.get("SPARSH_BENCH_GRID", "216")),
                     help="grid points per side (216 -> 10.08M rows); env SPARSH_BENCH_GRID")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement and check beyond the timed steps (see the module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float64)")
     ap.add_argument("--no-cpu", action="store_true", default=os.environ.get("SPARSH_BENCH_NO_CPU", "0") == "1",
-                    help="skip the cpu_baseline leg; env SPARSH_BENCH_NO_CPU=1")
+                    help="with --full: skip the cpu_baseline leg; env SPARSH_BENCH_NO_CPU=1")
     ap.add_argument("--cpu-iters", type=int, default=30)  # ~10 s of 16-thread CPU work at 216^3
     ap.add_argument("--rccl", action="store_true", help="install the RCCL transport even with one rank (path check)")
     ap.add_argument("--no-pmc", action="store_true", default=os.environ.get("SPARSH_BENCH_NO_PMC", "0") == "1",
-                    help="skip the two rocprofv3 --pmc child passes that measure roofline.traffic; env SPARSH_BENCH_NO_PMC=1")
+                    help="with --full: skip the two rocprofv3 --pmc child passes that measure roofline.traffic; env SPARSH_BENCH_NO_PMC=1")
     ap.add_argument("--no-families", action="store_true", default=os.environ.get("SPARSH_BENCH_NO_FAMILIES", "0") == "1",
-                    help="skip the general-layout / CSR-stream / sliced-ELL comparison runs")
+                    help="with --full: skip the general-layout / CSR-stream / sliced-ELL comparison runs")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # Exactly one line may reach stdout (the JSON record): libraries such as RCCL print banners
     # there, so everything else is routed to stderr and the record is written to the saved fd.
@@ -268,6 +299,8 @@ def main():
     hist = first_segment[0] if first_segment else last_hist
     if not (np.all(np.isfinite(hist)) and np.all(np.isfinite(last_hist))):
         raise SystemExit("non-finite residual in the timed run")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, A, xd, nloc, last_hist)
 
     # dominant kernel: fused Jacobi sweep on the finest level, timed by HIP events on the
     # engine's stream inside the timed region (sparsh_profile)
@@ -353,7 +386,7 @@ def main():
         fmt_bytes = 24 * pr["nrow"]
         jac_bytes *= 2
     single_sweeps = None
-    if dbl:
+    if dbl and args.full:
         # the same handle, same hierarchy, with the double sweep switched off (outside the timed region): what the launch-per-sweep
         # path gives on this box in this process; histories are bitwise the same (tests/test_gpu_parity.py)
         try:
@@ -405,7 +438,7 @@ def main():
                             "model for TWO sweeps (2 x (12*nnz + 36*n)): an effective rate, not a bandwidth. With 16 waves per CU and two workgroup barriers per plane the kernel "
                             "is bound by fp64 VALU issue (7 mul + 7 add + an IEEE division per row and sweep, 2.3 sweep-equivalents per launch with the recomputed halo) about "
                             "as much as by HBM; avg_us is measured inside the solve over runs of consecutive double-sweep launches")
-        if world == 1 and mode == "single":
+        if args.full and world == 1 and mode == "single":
             # the same kernel launched back to back in this process (outside the timed region): the in-solve figure above varies
             # from process to process with the physical placement of a working set the size of the Infinity Cache
             try:
@@ -431,7 +464,7 @@ def main():
     # the metric's second half: plain SpMV y = A x on the finest level (HIP events, 20 launches, outside
     # the timed region), priced with the CSR model 12*nnz + 20*n of SURVEY §8d
     spmv = None
-    if mode != "replicas":
+    if args.full and mode != "replicas":
         try:
             t_spmv = A.bench_op("spmv", 0, 20)
             sp_bytes = 12 * pr["nnz"] + 20 * pr["nrow"]
@@ -446,15 +479,17 @@ def main():
             spmv = {"error": repr(e)}
 
     # outside the timed region: a complete solve to the reference tolerance on the same hierarchy
-    log("full solve to tol=1e-8")
-    A.set_stopping(1e-8, 100000, 1)
-    A.h2d(xd, np.zeros(nloc))
-    hfull, it_full, sec_full, rc_full = A.solve_dev("pcg", bd, xd)
-    full = {"iterations": it_full, "seconds": round(sec_full, 4), "final_residual": float(hfull[-1]) if len(hfull) else None, "rc": rc_full}
+    full = None
+    if args.full:
+        log("full solve to tol=1e-8")
+        A.set_stopping(1e-8, 100000, 1)
+        A.h2d(xd, np.zeros(nloc))
+        hfull, it_full, sec_full, rc_full = A.solve_dev("pcg", bd, xd)
+        full = {"iterations": it_full, "seconds": round(sec_full, 4), "final_residual": float(hfull[-1]) if len(hfull) else None, "rc": rc_full}
 
     # the boundary hands over host buffers (reference API): same full solve through sparsh_solve,
     # which adds H2D of b and x and D2H of x over PCIe -- reported, never used as `value`
-    if world == 1 and mode == "single":
+    if args.full and world == 1 and mode == "single":
         xh = np.zeros(n)
         t_h = time.perf_counter()
         hh, rc_h = A.solve("pcg", b, xh)
@@ -469,7 +504,7 @@ def main():
     # gets); (iii) sliced ELL.  Residual histories must equal the main run's (all families are bitwise equal).
     general = None
     families = None
-    if world == 1 and mode == "single" and not args.no_families:
+    if args.full and world == 1 and mode == "single" and not args.no_families:
         families = {}
         runs = [("general_values_layout", dict(fold=False, cfg=None), "constant-slot folding off: sliced diagonals with 8 B per stored entry, no column indices"),
                 ("csr_stream_kind0", dict(fold=True, cfg=(0, 3, -1, -1)), "workgroup CSR-stream kernels forced on every level: rowptr + colindex + val streamed (12 B per entry); "
@@ -517,7 +552,7 @@ def main():
     # transparency: the same problem with the REFERENCE's own level policy (level1 = 6 levels, whatever is left -- 314 928 rows at 216^3 --
     # goes to the direct solver, src/AMG_phases.cpp:51,77,89): iterations to 1e-8, time, and the steady iteration rate
     ref_policy = None
-    if world == 1 and mode == "single" and not args.no_families and coarse["extended"]:
+    if args.full and world == 1 and mode == "single" and not args.no_families and coarse["extended"]:
         log("reference level policy run (6 levels, direct solve of the rest)")
         try:
             prm_ref = sa.default_params(print_setup=0, print_solve=0, device=local_rank, host_threads=host_threads, coarse_limit=1 << 30)
@@ -542,7 +577,7 @@ def main():
     # two child processes (separate FETCH_SIZE / WRITE_SIZE passes, MI355X_MICROARCH.md), same grid, same
     # kernel configuration; corrected with calibration kernels of known size run in the same child.
     pmc_iteration = None
-    if roof is not None and rank == 0 and world == 1 and mode == "single" and not args.no_pmc:
+    if args.full and roof is not None and rank == 0 and world == 1 and mode == "single" and not args.no_pmc:
         import shutil
         import subprocess
         import tempfile
@@ -592,7 +627,7 @@ def main():
         finally:
             shutil.rmtree(tmpd, ignore_errors=True)
     elif roof is not None:
-        roof["traffic_how"] = "not measured in this run (counter passes run at N=1 on rank 0 only, or were disabled)"
+        roof["traffic_how"] = "not measured in this run (counter passes run with --full at N=1 on rank 0 only, unless disabled)"
 
     # SURVEY 8d metric (ii): HBM GB/s of the whole iteration -- on the bytes the launched layouts have to move, and on the bytes
     # the PMC counters saw (the same child passes as roofline.traffic, 10 iterations between marker launches)
@@ -616,7 +651,7 @@ def main():
     # multi-GPU diagnostics for tuning (collective calls, every rank): what one halo exchange, one
     # scalar all-reduce and the all-gather at the replication boundary cost on this node
     comm_us = None
-    if mode == "partitioned":
+    if args.full and mode == "partitioned":
         try:
             comm_us = {"halo_exchange_level": {}, "note": "average of 50 back-to-back steps alone on the engine's stream (HIP events, rank 0)"}
             for l in range(A.nlevels):
@@ -634,7 +669,7 @@ def main():
     # multi-GPU parity: rank 0 repeats the same iterations on ONE GPU (fresh handle, no transport)
     # and compares residual histories; the other ranks wait at the barrier below.
     parity = None
-    if mode == "partitioned" and world > 1:
+    if args.full and mode == "partitioned" and world > 1:
         if rank == 0:
             log("1-GPU reference run for the parity check")
             A1 = sa.sp_matrix_mg(rp, ci, v).setup(prm)
@@ -653,7 +688,7 @@ def main():
             dist.barrier()
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         import oracle
 
         ncores = sa.host_cpus()
@@ -771,6 +806,7 @@ def main():
                 "spmv_finest_level": spmv,
                 "residual_after_timed_steps": float(last_hist[-1]),
                 "solve_restarted_every": RESTART,
+                "full_run": args.full,  # --full: the measurements and checks beyond the timed steps ran (null fields otherwise)
                 "full_solve_to_1e-8": full,
                 "general_values_layout": general,
                 "kernel_families": families,

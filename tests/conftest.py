@@ -1,3 +1,4 @@
+import gzip
 import json
 import os
 import sys
@@ -17,9 +18,9 @@ if not (os.path.exists(os.path.join(ROOT, "sparsh_amg_amd", "libsparsh_amg.so"))
 
     __graft_entry__.build()
 
-REF_DIR = "/root/reference"  # exists only in the build container, never on the GPU box
-C0_MATRIX = os.path.join(REF_DIR, "matrix_poisson_P1_14401")
-C0_RHS = os.path.join(REF_DIR, "matrix_poisson_P1rhs_14401")
+# BASELINE.json configs[0]: the reference's bundled input files in their native text format, stored gzip-compressed
+C0_MATRIX_GZ = os.path.join(ROOT, "tests", "golden", "matrix_poisson_P1_14401.gz")
+C0_RHS_GZ = os.path.join(ROOT, "tests", "golden", "matrix_poisson_P1rhs_14401.gz")
 
 
 def pytest_configure(config):
@@ -37,9 +38,16 @@ C0_FIXTURE = os.path.join(ROOT, "tests", "golden", "c0_matrix.npz")  # data fixt
 
 
 @pytest.fixture(scope="session")
-def have_c0():
-    """The reference tree itself (build container only); the C0 *data* travels as C0_FIXTURE."""
-    return os.path.exists(C0_MATRIX) and os.path.exists(C0_RHS)
+def c0_files(tmp_path_factory):
+    """(matrix file, rhs file) of configs[0] as the readers take them: C0_MATRIX_GZ / C0_RHS_GZ unpacked."""
+    d = tmp_path_factory.mktemp("c0_files")
+    paths = []
+    for gz in (C0_MATRIX_GZ, C0_RHS_GZ):
+        p = d / os.path.basename(gz)[: -len(".gz")]
+        with gzip.open(gz, "rb") as f:
+            p.write_bytes(f.read())
+        paths.append(str(p))
+    return tuple(paths)
 
 
 def load_c0():

@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
-"""Regenerates tests/golden/c0_matrix.npz from the reference's bundled input files.
-
-Run in the build container only (the files live in /root/reference, which does not travel):
+"""Regenerates tests/golden/c0_matrix.npz from the reference's bundled input files, stored next to
+it gzip-compressed (matrix_poisson_P1_14401.gz, matrix_poisson_P1rhs_14401.gz):
     python tests/golden/make_c0_fixture.py
 
 The fixture is DATA: the 13761 x 13761 P1-FEM Poisson matrix (95065 entries) and its right-hand
@@ -10,21 +9,19 @@ side, i.e. BASELINE.json configs[0], parsed by the rules of the reference's nati
 row; rhs file: "n", then one value per line) and stored as CSR arrays.  Values are kept as the
 doubles strtod gives for the file's decimal text, so every consumer sees bit-identical inputs.
 """
+import gzip
 import os
-import sys
 
 import numpy as np
 
-REF = "/root/reference"
-OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "c0_matrix.npz")
+HERE = os.path.dirname(os.path.abspath(__file__))
+OUT = os.path.join(HERE, "c0_matrix.npz")
 
 
 def main():
-    mpath = os.path.join(REF, "matrix_poisson_P1_14401")
-    rpath = os.path.join(REF, "matrix_poisson_P1rhs_14401")
-    if not (os.path.exists(mpath) and os.path.exists(rpath)):
-        sys.exit("reference input files not found (build container only)")
-    with open(mpath) as f:
+    mpath = os.path.join(HERE, "matrix_poisson_P1_14401.gz")
+    rpath = os.path.join(HERE, "matrix_poisson_P1rhs_14401.gz")
+    with gzip.open(mpath, "rt") as f:
         n, m, nnz = (int(t) for t in f.readline().split())
         body = np.array(f.read().split())
     assert body.size == 3 * nnz, (body.size, nnz)
@@ -35,7 +32,7 @@ def main():
     rowptr = np.zeros(n + 1, dtype=np.int32)
     np.add.at(rowptr, rows + 1, 1)
     rowptr = np.cumsum(rowptr, dtype=np.int64).astype(np.int32)
-    with open(rpath) as f:
+    with gzip.open(rpath, "rt") as f:
         nb = int(f.readline().split()[0])
         b = np.array([float(t) for t in f.read().split()], dtype=np.float64)
     assert nb == n and b.size == n

@@ -9,7 +9,7 @@ import pytest
 import oracle
 import sparsh_amg_amd as sa
 from sparsh_amg_amd import problems
-from conftest import C0_MATRIX, C0_RHS, ROOT
+from conftest import ROOT
 
 
 def _same_hierarchy(A: sa.sp_matrix_mg, H: oracle.Hierarchy):
@@ -49,10 +49,8 @@ def test_hierarchy_matches_oracle_beck(gen, kw):
         assert abs(S - O).max() <= 1e-13 * abs(O).max()
 
 
-def test_c0_readcoo_equals_fixture(have_c0, c0_arrays):
-    if not have_c0:
-        pytest.skip("/root/reference exists in the build container only")
-    A, b = sa.readcoo(C0_MATRIX, C0_RHS)
+def test_c0_readcoo_equals_fixture(c0_files, c0_arrays):
+    A, b = sa.readcoo(*c0_files)
     rp, ci, v = A.rowptr, A.colindex, A.val
     assert np.array_equal(rp, c0_arrays[0]) and np.array_equal(ci, c0_arrays[1])
     assert np.array_equal(v, c0_arrays[2]) and np.array_equal(b, c0_arrays[3])

@@ -5,7 +5,7 @@ import pytest
 
 import oracle
 from sparsh_amg_amd import problems
-from conftest import C0_MATRIX, C0_RHS, hist_tolerance
+from conftest import hist_tolerance
 
 # oracle-vs-MKL tolerance: summation orders differ (MKL's are unknown), so allow 100x the
 # reference's own run-to-run noise (Appendix A.4) and never tighter than 1e-11.
@@ -24,12 +24,10 @@ def c0(c0_arrays):
     return oracle.Csr(rp, ci, v), b
 
 
-def test_c0_fixture_is_the_reference_file(have_c0, c0_arrays):
+def test_c0_fixture_is_the_reference_file(c0_files, c0_arrays):
     """tests/golden/c0_matrix.npz holds exactly what the reference's reader makes of its bundled
-    files (checked wherever /root/reference exists; the fixture alone travels to the GPU box)."""
-    if not have_c0:
-        pytest.skip("/root/reference exists in the build container only")
-    A, b = oracle.readcoo(C0_MATRIX, C0_RHS)
+    files (tests/golden/matrix_poisson_P1*_14401.gz)."""
+    A, b = oracle.readcoo(*c0_files)
     rp, ci, v = A.arrays()
     assert np.array_equal(rp, c0_arrays[0]) and np.array_equal(ci, c0_arrays[1])
     assert np.array_equal(v, c0_arrays[2]) and np.array_equal(b, c0_arrays[3])

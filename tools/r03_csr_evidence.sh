@@ -10,7 +10,7 @@ export TMPDIR=/tmp
 cd /tmp
 for v in 32 16; do
   if [ $v = 16 ]; then export SPARSH_BENCH_IDX16=2; else unset SPARSH_BENCH_IDX16; fi
-  SPARSH_BENCH_KCFG=0,3,-1,-1 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_idx$v -- python3 $R/bench.py --no-cpu --no-pmc --no-families \
+  SPARSH_BENCH_KCFG=0,3,-1,-1 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_idx$v -- python3 $R/bench.py --full --no-cpu --no-pmc --no-families \
      > $O/bench_idx$v.json 2> $O/bench_idx$v.err || exit 1
   find $O/stats_idx$v -name "*kernel_trace.csv" -size +4M -delete
   echo "stats idx$v done"

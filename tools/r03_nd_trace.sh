@@ -16,7 +16,7 @@ done
 cd $R
 # 216^3: where the extended hierarchy stops (round 2: <= 4000 rows, 13 levels; now: <= coarse_limit, nested dissection on 39 366 rows)
 for u in 4000 0; do
-  SPARSH_EXTEND_UNTIL=$u python bench.py --no-cpu --no-pmc --no-families > $O/bench216_extend_$u.json 2> $O/bench216_extend_$u.err; echo "bench extend_until=$u rc=$?"
+  SPARSH_EXTEND_UNTIL=$u python bench.py --full --no-cpu --no-pmc --no-families > $O/bench216_extend_$u.json 2> $O/bench216_extend_$u.err; echo "bench extend_until=$u rc=$?"
   python - <<PY
 import json
 d=json.loads(open("$O/bench216_extend_$u.json").read().strip().splitlines()[-1])
