@@ -37,6 +37,12 @@ extern "C" {
 #define SPARSH_BICG 3   /* Solver_BiCG_1                    (src/AMG_main_solvers.cpp:271-355) */
 #define SPARSH_PBICG 4  /* Solver_PBiCG_1..4                (src/AMG_main_solvers.cpp:358-458) */
 
+/* Smoother of the V-cycle (sparsh_set_smoother). */
+#define SPARSH_SMOOTH_JACOBI 0  /* weighted Jacobi, parallel::jacobi_smoother (default) */
+#define SPARSH_SMOOTH_SOR 1     /* multicolour SOR, parallel::sor_smoother (src/AMG_smoothers.cpp:78-102) */
+#define SPARSH_SOR_FORWARD 0    /* post-smoothing takes the colours 1..C, as AMG_solve_SOR (src/AMG_phases.cpp:234-306) */
+#define SPARSH_SOR_SYMMETRIC 1  /* post-smoothing takes the colours C..1: a symmetric preconditioner (required by SPARSH_PCG) */
+
 /* Runtime form of the compile-time macros of the reference's include/AMG.hpp:15-27.
  * sparsh_default_params() fills the reference values; the env variables in brackets
  * override them inside sparsh_default_params(). */
@@ -386,8 +392,38 @@ int sparsh_op_axpby(sparsh_handle h, int n, double a, const double *x, double bc
  * sweep, 2 residual, 3 restrict, 4 prolong, 5 coarse GEMV, 6 dot, 7 axpby, 8 int32 copy (4-byte
  * stream, calibrates the profiler's byte counters), 9 fused Jacobi sweeps ping-ponging between two vectors (the
  * access pattern of a smoothing leg), 10 the same on the level's own resident x / x2 / r buffers, 11 double sweeps
- * (sparsh_set_double_sweep) ping-ponging on those buffers: seconds per launch = per PAIR of sweeps. */
+ * (sparsh_set_double_sweep) ping-ponging on those buffers: seconds per launch = per PAIR of sweeps, 12 one SOR sweep (all
+ * colours) on the level's own x with r as the right-hand side, issued as a smoothing leg issues it (sparsh_set_sor_path). */
 int sparsh_bench_op(sparsh_handle h, int op, int level, int reps, double *avg_seconds);
+
+/* ---- multicolour SOR smoother ----
+ * sparsh_set_smoother: kind SPARSH_SMOOTH_JACOBI (default) or SPARSH_SMOOTH_SOR; sweeps per leg (0: the default -- 6 for SOR,
+ * the count AMG_solve_SOR hard-codes, params.sweeps for Jacobi); order SPARSH_SOR_FORWARD / SPARSH_SOR_SYMMETRIC (SOR only).
+ * May be called before or after sparsh_setup, also between sparsh_krylov_init_dev and sparsh_krylov_step_dev (the steps then
+ * use the new smoother); selecting Jacobi again restores the Jacobi cycle exactly.  SOR is refused (SPARSH_EINVAL) on
+ * partitioned (multi-GPU) handles and with params.precond_fp32, as is a Jacobi sweep count on a partitioned handle after its
+ * setup; SPARSH_PCG requires SPARSH_SOR_SYMMETRIC (sparsh_solve*, sparsh_krylov_init_dev and sparsh_krylov_step_dev return
+ * SPARSH_EINVAL otherwise).
+ * Colouring: greedy first-fit over the rows in ascending order on the pattern of A + A^T without the diagonal, colours from 1.
+ * One sweep: for c = 1..C (C..1 reversed), all rows i of colour c at once, in place: s = sum_j a_ij x_j in stored order,
+ * h = s - b_i, x_i = x_i - (omega*h)/d_i.  The V-cycle keeps the Jacobi hierarchy and order of operations: pre-smoothing
+ * forward, coarse levels from x = 0, post-smoothing in the chosen order. */
+int sparsh_set_smoother(sparsh_handle h, int kind, int sweeps, int order);
+/* colour classes of a level (after sparsh_setup_host; no device needed): number of colours, rows of colour c at
+ * rows_per_color[c - 1] (may be NULL) */
+int sparsh_level_colors(sparsh_handle h, int level, int *ncolors, int *rows_per_color);
+/* colour (1..C) of every row of the level (nrow ints) */
+int sparsh_level_color_of_rows(sparsh_handle h, int level, int *color);
+/* `sweeps` SOR sweeps of a level on host vectors, colours C..1 when reverse; x_is_zero: x is taken as 0 (not read) */
+int sparsh_op_sor(sparsh_handle h, int level, const double *b, double *x, int sweeps, int reverse, int x_is_zero);
+/* Debug / measurement knob of the SOR legs: 0 (default) the level policy -- one launch per colour and sweep on every level,
+ * since the single-workgroup launch of a whole leg measured slower on every level tried; 1 per-colour launches
+ * on every level; 2 the single launch on every level.  Both paths give the same bits. */
+int sparsh_set_sor_path(sparsh_handle h, int mode);
+/* SOR layout of a level: colours, whether a leg is one launch under the current path, device bytes of the colour-compacted
+ * copy.  The smoothed levels (all but the coarsest, which is solved directly) get theirs at sparsh_setup when SOR was selected
+ * before it, else at the first SOR solve; any level at its first sparsh_op_sor.  SPARSH_ESTATE when it is not built. */
+int sparsh_level_sor_layout(sparsh_handle h, int level, int *ncolors, int *single_launch, long *bytes);
 
 /* device memory helpers so a host language needs no HIP binding of its own */
 int sparsh_dev_alloc(sparsh_handle h, long nbytes, void **out);

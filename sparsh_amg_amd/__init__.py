@@ -24,6 +24,10 @@ LIB_PATH = os.path.join(_HERE, "libsparsh_amg.so")
 
 SPARSH_AMG, SPARSH_CG, SPARSH_PCG, SPARSH_BICG, SPARSH_PBICG = 0, 1, 2, 3, 4
 METHODS = {"amg": SPARSH_AMG, "cg": SPARSH_CG, "pcg": SPARSH_PCG, "bicg": SPARSH_BICG, "pbicg": SPARSH_PBICG}
+SPARSH_SMOOTH_JACOBI, SPARSH_SMOOTH_SOR = 0, 1
+SPARSH_SOR_FORWARD, SPARSH_SOR_SYMMETRIC = 0, 1
+SMOOTHERS = {"jacobi": SPARSH_SMOOTH_JACOBI, "sor": SPARSH_SMOOTH_SOR}
+SOR_ORDERS = {"forward": SPARSH_SOR_FORWARD, "symmetric": SPARSH_SOR_SYMMETRIC}
 SPARSH_OK, SPARSH_EINVAL, SPARSH_ENODEV, SPARSH_ESTATE, SPARSH_ENUMERIC, SPARSH_ENOCONV, SPARSH_ECOMM = 0, -1, -2, -3, -4, -5, -6
 
 c_int_p = C.POINTER(C.c_int)
@@ -178,6 +182,12 @@ def _load():
         "sparsh_d2h": (C.c_int, [H, C.c_void_p, C.c_void_p, C.c_long]),
         "sparsh_sync": (C.c_int, [H]),
         "sparsh_profile": (C.c_int, [H, C.c_int]),
+        "sparsh_set_smoother": (C.c_int, [H, C.c_int, C.c_int, C.c_int]),
+        "sparsh_level_colors": (C.c_int, [H, C.c_int, c_int_p, c_int_p]),
+        "sparsh_level_color_of_rows": (C.c_int, [H, C.c_int, c_int_p]),
+        "sparsh_op_sor": (C.c_int, [H, C.c_int, c_dbl_p, c_dbl_p, C.c_int, C.c_int, C.c_int]),
+        "sparsh_set_sor_path": (C.c_int, [H, C.c_int]),
+        "sparsh_level_sor_layout": (C.c_int, [H, C.c_int, c_int_p, c_int_p, C.POINTER(C.c_long)]),
         "sparsh_profile_read": (C.c_int, [H, c_dbl_p]),
     }
     for name, (res, args) in sig.items():
@@ -441,6 +451,35 @@ class sp_matrix_mg:
         r = C.c_int(0)
         _check(lib.sparsh_level_tile_rows(self._h, level, C.byref(r)))
         return r.value
+
+    # -- smoother ------------------------------------------------------------------------------
+    def set_smoother(self, kind="jacobi", sweeps=0, order="forward"):
+        """Smoother of the V-cycle: "jacobi" (default) or "sor" (multicolour SOR); sweeps per leg (0: params.sweeps for
+        Jacobi, 6 for SOR); order of the SOR post-smoothing: "forward" or "symmetric" (SPARSH_PCG needs "symmetric")."""
+        k = SMOOTHERS[kind] if isinstance(kind, str) else int(kind)
+        o = SOR_ORDERS[order] if isinstance(order, str) else int(order)
+        _check(lib.sparsh_set_smoother(self._h, k, int(sweeps), o))
+        return self
+
+    def level_colors(self, level):
+        """(ncolors, rows per colour, colour of every row) of the SOR colouring of a level; colours are numbered from 1."""
+        nc = C.c_int(0)
+        _check(lib.sparsh_level_colors(self._h, level, C.byref(nc), None))
+        counts = np.zeros(max(nc.value, 1), dtype=np.int32)
+        _check(lib.sparsh_level_colors(self._h, level, C.byref(nc), _ip(counts)))
+        color = np.zeros(self.level_info(level)["nrow"], dtype=np.int32)
+        _check(lib.sparsh_level_color_of_rows(self._h, level, _ip(color)))
+        return nc.value, counts[: nc.value], color
+
+    def set_sor_path(self, mode=0):
+        """Debug knob of the SOR legs: 0 level policy, 1 per-colour launches everywhere, 2 one launch per leg everywhere."""
+        _check(lib.sparsh_set_sor_path(self._h, int(mode)))
+        return self
+
+    def level_sor_layout(self, level):
+        nc, single, nbytes = C.c_int(), C.c_int(), C.c_long()
+        _check(lib.sparsh_level_sor_layout(self._h, level, C.byref(nc), C.byref(single), C.byref(nbytes)))
+        return dict(ncolors=nc.value, single_launch=bool(single.value), bytes=nbytes.value)
 
     def set_kernel_config(self, kind=3, vec=3, nt=-1, remap=-1):
         """Select the SpMV-type kernel family of this handle; see sparsh_set_kernel_config."""
@@ -753,7 +792,7 @@ class sp_matrix_mg:
 
     def bench_op(self, op, level=0, reps=20):
         ops = {"spmv": 0, "jacobi": 1, "residual": 2, "restrict": 3, "prolong": 4, "coarse": 5, "dot": 6, "axpby": 7, "copy_int": 8,
-               "jacobi_pingpong": 9, "jacobi_pingpong_resident": 10, "jacobi_double": 11}
+               "jacobi_pingpong": 9, "jacobi_pingpong_resident": 10, "jacobi_double": 11, "sor": 12}
         sec = C.c_double()
         _check(lib.sparsh_bench_op(self._h, ops[op] if isinstance(op, str) else op, level, reps, C.byref(sec)))
         return sec.value
@@ -769,6 +808,12 @@ class sp_matrix_mg:
         b = np.ascontiguousarray(b, dtype=np.float64)
         x = np.array(x, dtype=np.float64)
         _check(lib.sparsh_op_jacobi(self._h, level, _dp(b), _dp(x), sweeps, 1 if x_is_zero else 0))
+        return x
+
+    def op_sor(self, level, b, x, sweeps, reverse=False, x_is_zero=False):
+        b = np.ascontiguousarray(b, dtype=np.float64)
+        x = np.array(x, dtype=np.float64)
+        _check(lib.sparsh_op_sor(self._h, level, _dp(b), _dp(x), int(sweeps), 1 if reverse else 0, 1 if x_is_zero else 0))
         return x
 
     def op_residual(self, level, b, x):

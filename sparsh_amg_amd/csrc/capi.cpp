@@ -79,6 +79,11 @@ struct DBuf {
 #define REQUIRE_SINGLE(h) \
     if ((h)->eng->distributed()) return fail(SPARSH_ESTATE, "operator-level entry points are single-GPU test hooks (host vectors carry no halo)")
 
+// checked before REQUIRE_READY: a combination that no setup can make valid is a bad argument, with or without a device
+#define REQUIRE_SMOOTHER_FITS(h, method)                                                                                        \
+    if ((h) && (h)->eng && (method) == SPARSH_PCG && (h)->eng->sor_on() && (h)->eng->sor_order() != SPARSH_SOR_SYMMETRIC) \
+    return fail(SPARSH_EINVAL, "SPARSH_PCG needs a symmetric preconditioner: the SOR smoother must use SPARSH_SOR_SYMMETRIC")
+
 #define REQUIRE_HOST(h)                                               \
     if (!(h) || !(h)->eng) return fail(SPARSH_EINVAL, "null handle"); \
     if (!(h)->eng->host_ready()) return fail(SPARSH_ESTATE, "sparsh_setup / sparsh_setup_host has not been called (or failed)")
@@ -552,6 +557,69 @@ int sparsh_level_index16(sparsh_handle h, int level, long *blocks16, long *block
     return SPARSH_OK;
 }
 
+int sparsh_set_smoother(sparsh_handle h, int kind, int sweeps, int order)
+{
+    if (!h || !h->eng) return fail(SPARSH_EINVAL, "null handle");
+    Engine &E = *h->eng;
+    if (kind != SPARSH_SMOOTH_JACOBI && kind != SPARSH_SMOOTH_SOR)
+        return fail(SPARSH_EINVAL, "kind must be SPARSH_SMOOTH_JACOBI (0) or SPARSH_SMOOTH_SOR (1)");
+    if (sweeps < 0) return fail(SPARSH_EINVAL, "sweeps < 0");
+    if (order != SPARSH_SOR_FORWARD && order != SPARSH_SOR_SYMMETRIC)
+        return fail(SPARSH_EINVAL, "order must be SPARSH_SOR_FORWARD (0) or SPARSH_SOR_SYMMETRIC (1)");
+    if (kind == SPARSH_SMOOTH_JACOBI && sweeps > 0 && E.ready() && E.distributed())
+        return fail(SPARSH_EINVAL, "a partitioned handle sizes its ghost layers for the sweep count of its setup: change params.sweeps and call sparsh_setup");
+    if (kind == SPARSH_SMOOTH_SOR) {
+        if (E.distributed() || (E.comm() && E.comm()->size > 1))
+            return fail(SPARSH_EINVAL, "the SOR smoother is not available on a partitioned (multi-GPU) handle");
+        if ((E.host_ready() || E.ready()) && E.params().precond_fp32)
+            return fail(SPARSH_EINVAL, "the SOR smoother has no fp32 hierarchy: unset params.precond_fp32");
+    }
+    E.set_smoother(kind, sweeps, order);
+    return SPARSH_OK;
+}
+
+int sparsh_level_colors(sparsh_handle h, int level, int *ncolors, int *rows_per_color)
+{
+    REQUIRE_HOST(h);
+    REQUIRE_LEVEL(h, level);
+    const ColorClasses &cc = h->eng->level_colors(level);
+    if (ncolors) *ncolors = cc.ncolors;
+    if (rows_per_color)
+        for (int c = 0; c < cc.ncolors; ++c) rows_per_color[c] = cc.start[c + 1] - cc.start[c];
+    return SPARSH_OK;
+}
+
+int sparsh_level_color_of_rows(sparsh_handle h, int level, int *color)
+{
+    REQUIRE_HOST(h);
+    REQUIRE_LEVEL(h, level);
+    if (!color) return fail(SPARSH_EINVAL, "null color");
+    const ColorClasses &cc = h->eng->level_colors(level);
+    std::copy(cc.color.begin(), cc.color.end(), color);
+    return SPARSH_OK;
+}
+
+int sparsh_set_sor_path(sparsh_handle h, int mode)
+{
+    if (!h || !h->eng) return fail(SPARSH_EINVAL, "null handle");
+    if (mode < 0 || mode > 2) return fail(SPARSH_EINVAL, "mode must be 0 (level policy), 1 (per-colour launches) or 2 (one launch per leg)");
+    h->eng->set_sor_path(mode);
+    h->eng->config_changed();
+    return SPARSH_OK;
+}
+
+int sparsh_level_sor_layout(sparsh_handle h, int level, int *ncolors, int *single_launch, long *bytes)
+{
+    REQUIRE_READY(h);
+    REQUIRE_LEVEL(h, level);
+    const SorLevel *S = h->eng->sor_level(level);
+    if (!S) return fail(SPARSH_ESTATE, "the SOR layouts are not built (select SOR before sparsh_setup, or solve / call sparsh_op_sor)");
+    if (ncolors) *ncolors = S->ncolors;
+    if (single_launch) *single_launch = h->eng->sor_single(level) ? 1 : 0;
+    if (bytes) *bytes = (long)S->bytes;
+    return SPARSH_OK;
+}
+
 int sparsh_num_levels(sparsh_handle h)
 {
     if (!h || !h->eng || !h->eng->host_ready()) return 0;
@@ -693,6 +761,7 @@ int sparsh_vcycle_dev(sparsh_handle h, const double *b_dev, double *x_dev, int i
 
 int sparsh_solve(sparsh_handle h, int method, const double *b, double *x, double *hist, int hist_cap, int *iters)
 {
+    REQUIRE_SMOOTHER_FITS(h, method);
     REQUIRE_READY(h);
     Engine &E = *h->eng;
     const size_t n = (size_t)E.local_n0();  // multi-GPU: this rank's block of level 0
@@ -707,6 +776,7 @@ int sparsh_solve(sparsh_handle h, int method, const double *b, double *x, double
 int sparsh_solve_dev(sparsh_handle h, int method, const double *b_dev, double *x_dev, int max_iters, double *hist, int hist_cap,
                      int *iters, double *seconds)
 {
+    REQUIRE_SMOOTHER_FITS(h, method);
     REQUIRE_READY(h);
     int rc = h->eng->solve_dev(method, b_dev, x_dev, max_iters, hist, hist_cap, iters, seconds);
     if (rc != SPARSH_OK) return fail(rc, h->eng->error);
@@ -1005,6 +1075,7 @@ int sparsh_dist_deep_op_get(sparsh_handle h, int *rowptr, int *col, double *val,
 
 int sparsh_krylov_init_dev(sparsh_handle h, int method, const double *b_dev, double *x_dev)
 {
+    REQUIRE_SMOOTHER_FITS(h, method);
     REQUIRE_READY(h);
     if (method != SPARSH_CG && method != SPARSH_PCG) return fail(SPARSH_EINVAL, "stepwise interface covers SPARSH_CG and SPARSH_PCG");
     int rc = h->eng->pcg_init(b_dev, x_dev, method == SPARSH_PCG);
@@ -1051,6 +1122,20 @@ int sparsh_op_jacobi(sparsh_handle h, int level, const double *b, double *x, int
     const size_t n = (size_t)E.level(level).n;
     DBuf db(E, n, b), dx(E, n, x), dt(E, n);
     E.op_jacobi(level, db.p, dx.p, dt.p, sweeps, x_is_zero != 0);
+    return done(E, dx.get(x));
+}
+
+int sparsh_op_sor(sparsh_handle h, int level, const double *b, double *x, int sweeps, int reverse, int x_is_zero)
+{
+    REQUIRE_READY(h);
+    REQUIRE_SINGLE(h);
+    REQUIRE_LEVEL(h, level);
+    if (sweeps < 0) return fail(SPARSH_EINVAL, "sweeps < 0");
+    Engine &E = *h->eng;
+    const size_t n = (size_t)E.level(level).n;
+    DBuf db(E, n, b), dx(E, n, x);
+    if (!db.p || !dx.p) return fail(SPARSH_ENODEV, E.error);
+    if (!E.op_sor(level, db.p, dx.p, sweeps, reverse != 0, x_is_zero != 0)) return fail(E.fault() != SPARSH_OK ? E.fault() : SPARSH_ENODEV, E.error);
     return done(E, dx.get(x));
 }
 
@@ -1235,6 +1320,7 @@ int sparsh_bench_op(sparsh_handle h, int op, int level, int reps, double *avg_se
             ++flip;
             launch_csr(L.A, OP_JACOBI, a, L.fine, st, E.kernel_cfg());
         } break;
+        case 12: E.sor_leg(level, L.r, L.x, 1, false); break;  // one SOR sweep, as a leg issues it
         case 11: {  // double sweeps (sdia_box2_kernel) ping-ponging on the level's resident buffers, as a smoothing leg issues them
             static thread_local int flip2 = 0;
             double *xa = (flip2 & 1) ? L.x2 : L.x, *xb = (flip2 & 1) ? L.x : L.x2;
@@ -1244,7 +1330,8 @@ int sparsh_bench_op(sparsh_handle h, int op, int level, int reps, double *avg_se
         default: break;
         }
     };
-    if (op < 0 || op > 11) return fail(SPARSH_EINVAL, "unknown op");
+    if (op < 0 || op > 12) return fail(SPARSH_EINVAL, "unknown op");
+    if (op == 12 && (E.distributed() || !E.build_sor_level(level))) return fail(SPARSH_ESTATE, "no SOR layout on this handle");
     if (op == 11 && (E.distributed() || !box2_applies(L.A, E.kernel_cfg()))) return fail(SPARSH_ESTATE, "the level does not run double sweeps (sparsh_level_double_sweep)");
     for (int i = 0; i < 3; ++i) run();
     hipEvent_t e0, e1;

@@ -492,8 +492,12 @@ int partial_count(const DevCsr &D) { return std::max(D.nblk, std::max((D.nwblk +
 int Engine::setup_host(const sparsh_params &p)
 {
     prm_ = p;
+    base_sweeps_ = p.sweeps;
+    adopt_sweeps();
     ready_ = false;
     host_ready_ = false;
+    colors_.clear();
+    sor_.clear();
     SetupParams sp;
     sp.max_levels = p.max_levels;
     sp.limit_upper = p.limit_upper;
@@ -538,6 +542,8 @@ int Engine::setup_host(const sparsh_params &p)
         setup_seconds = H_.seconds;
     }
     host_ready_ = true;
+    if (sor_on())  // the smoother was chosen before the setup: colour every level now
+        for (int l = 0; l < (int)H_.levels.size(); ++l) level_colors(l);
     return SPARSH_OK;
 }
 
@@ -1160,6 +1166,7 @@ int Engine::setup(const sparsh_params &p)
     if (!st_ && !check(hipStreamCreateWithFlags(&st_, hipStreamNonBlocking), "hipStreamCreate")) return SPARSH_ENODEV;
     for (void *q : allocs_) (void)hipFree(q);  // a second setup replaces the resident hierarchy
     allocs_.clear();
+    sor_.clear();
     coarse_.release();
     if (!comm_) comm_ = make_self_comm();
     const int G = comm_->size, me = comm_->rank;
@@ -1170,6 +1177,9 @@ int Engine::setup(const sparsh_params &p)
     image_bytes_ = 0;
     if (int rc = (G > 1 && share_setup_) ? setup_host_shared(hp) : setup_host(hp); rc != SPARSH_OK) return rc;
     prm_ = p;
+    base_sweeps_ = p.sweeps;
+    adopt_sweeps();
+    if (!built_locally_) colors_.clear();  // (setup_host_shared: the hierarchy of another rank)
 
     // ---- row partition of every level (multi-GPU).  Levels at or below replicate_rows, and always
     // the coarsest one (dense direct solve), are held and computed by every rank -- or, with more than one rank and the
@@ -1419,6 +1429,7 @@ int Engine::setup(const sparsh_params &p)
             !check(hipEventCreateWithFlags(&ev_halo_, hipEventDisableTiming), "hipEventCreate"))
             return SPARSH_ENODEV;
     }
+    if (sor_on() && !dist_ && !p.precond_fp32 && !build_sor_layouts()) return SPARSH_ENODEV;  // (otherwise refused at the solve)
     if (!check(hipStreamSynchronize(st_), "setup sync")) return SPARSH_ENODEV;
     if (!comm_->barrier(st_)) {
         error = "comm barrier after setup failed: " + comm_->error;
@@ -1875,9 +1886,183 @@ void Engine::op_jacobi(int l, const double *b, double *x, double *tmp, int sweep
     L.x2 = sx2;
 }
 
+// ---------------------------------------------------------------------------- multicolour SOR smoother
+
+void Engine::adopt_sweeps() { prm_.sweeps = (smoother_ == SPARSH_SMOOTH_JACOBI && sm_sweeps_ > 0) ? sm_sweeps_ : base_sweeps_; }
+
+void Engine::set_smoother(int kind, int sweeps, int order)
+{
+    smoother_ = kind;
+    sm_sweeps_ = sweeps;
+    sor_order_ = order;
+    if (host_ready_) adopt_sweeps();  // (before the first setup, setup_host adopts them)
+    config_changed();
+}
+
+const ColorClasses &Engine::level_colors(int l)
+{
+    if (colors_.size() < H_.levels.size()) colors_.resize(H_.levels.size());
+    if (colors_[l].color.empty() && H_.levels[l].A.nrow > 0) colors_[l] = greedy_colors(H_.levels[l].A);
+    return colors_[l];
+}
+
+// Level l's colour-compacted copy of A_l, its diagonal in colour order and the row-block records of every colour.
+bool Engine::build_sor_level(int l)
+{
+    if (sor_.size() != lev_.size()) sor_.assign(lev_.size(), SorLevel());
+    if (sor_[l].rows) return true;
+    {
+        const HostLevel &h = H_.levels[l];
+        const ColorClasses &cc = level_colors(l);
+        SorLevel S;
+        const int n = h.A.nrow;
+        S.n = n;
+        S.ncolors = cc.ncolors;
+        S.cstart = cc.start;
+        std::vector<int> rp((size_t)n + 1, 0);
+        for (int k = 0; k < n; ++k) {
+            const int i = cc.rows[k];
+            rp[(size_t)k + 1] = rp[k] + (h.A.rowptr[i + 1] - h.A.rowptr[i]);
+        }
+        const size_t nnz = (size_t)rp[n];
+        std::vector<int> col(nnz);
+        std::vector<double> val(nnz), diag((size_t)n);
+#pragma omp parallel for schedule(static)
+        for (int k = 0; k < n; ++k) {
+            const int i = cc.rows[k];
+            const int j0 = h.A.rowptr[i], len = h.A.rowptr[i + 1] - j0;
+            std::copy(h.A.col + j0, h.A.col + j0 + len, col.begin() + rp[k]);
+            std::copy(h.A.val + j0, h.A.val + j0 + len, val.begin() + rp[k]);
+            diag[k] = h.diag[i];
+        }
+        std::vector<int> rec;
+        S.blk_first.assign((size_t)S.ncolors + 1, 0);
+        for (int c = 0; c < S.ncolors; ++c) {
+            int nb = 0;
+            const int r0 = S.cstart[c], r1 = S.cstart[c + 1];
+            std::vector<int> rc = rowblock_records(r1 - r0, rp.data() + r0, &nb);
+            for (int q = 0; q < nb; ++q) {  // records of the colour's slice -> compacted row numbers (entries are absolute already)
+                rc[(size_t)4 * q] += r0;
+                rc[(size_t)4 * q + 1] += r0;
+            }
+            rec.insert(rec.end(), rc.begin(), rc.begin() + (size_t)4 * nb);
+            S.blk_first[c + 1] = S.blk_first[c] + nb;
+        }
+        if (rec.empty()) rec.assign(4, 0);
+        S.dcstart = upload(*this, S.cstart.data(), S.cstart.size());
+        S.rows = upload(*this, cc.rows.data(), (size_t)n);
+        S.rowptr = upload(*this, rp.data(), rp.size());
+        S.col = upload_padded(*this, col.data(), nnz);
+        S.val = upload_padded(*this, val.data(), nnz);
+        S.diag = upload(*this, diag.data(), (size_t)n);
+        S.rec = upload(*this, rec.data(), rec.size());
+        if (!S.dcstart || !S.rows || !S.rowptr || !S.col || !S.val || !S.diag || !S.rec) return false;
+        S.bytes = S.cstart.size() * 4 + (size_t)n * 4 + rp.size() * 4 + (nnz + kCsrPad) * 12 + (size_t)n * 8 + rec.size() * 4;
+        S.nt = nnz * 12 + (size_t)n * 36 > (240u << 20);  // the CSR-stream policy (csr_placement): the sweep's bytes exceed the Infinity Cache
+        S.single = (long)nnz <= kSorSingleNnz;
+        sor_[l] = std::move(S);
+    }
+    return true;
+}
+
+// the levels a V-cycle smooths (every level but the coarsest, which is solved directly)
+bool Engine::build_sor_layouts()
+{
+    for (int l = 0; l + 1 < (int)lev_.size(); ++l)
+        if (!build_sor_level(l)) return false;
+    return true;
+}
+
+int Engine::sor_prepare()
+{
+    if (!sor_on()) return SPARSH_OK;
+    if (dist_) {
+        error = "the SOR smoother is not available on a partitioned (multi-GPU) handle";
+        return SPARSH_EINVAL;
+    }
+    if (prm_.precond_fp32) {
+        error = "the SOR smoother has no fp32 hierarchy: unset params.precond_fp32";
+        return SPARSH_EINVAL;
+    }
+    if (!build_sor_layouts()) return fault_ != SPARSH_OK ? fault_ : SPARSH_ENODEV;
+    return SPARSH_OK;
+}
+
+void Engine::sor_leg(int l, const double *b, double *x, int sweeps, bool reverse)
+{
+    if (sweeps <= 0) return;
+    if (l < 0 || l >= (int)sor_.size() || !sor_[l].rows) {
+        // every caller builds the layouts first (sor_prepare / build_sor_level): nothing may run on a missing layout
+        error = "SOR sweep on level " + std::to_string(l) + " without its colour layout";
+        if (fault_ == SPARSH_OK) fault_ = SPARSH_ESTATE;
+        return;
+    }
+    const SorLevel &S = sor_[l];
+    if (S.ncolors == 0) return;
+    SorArgs a;
+    a.rows = S.rows;
+    a.rowptr = S.rowptr;
+    a.col = S.col;
+    a.val = S.val;
+    a.diag = S.diag;
+    a.b = b;
+    a.x = x;
+    a.omega = prm_.omega;
+    if (sor_single(l)) {
+        launch_sor_level(S.dcstart, S.ncolors, sweeps, reverse, a, st_);
+        return;
+    }
+    for (int s = 0; s < sweeps; ++s)
+        for (int q = 0; q < S.ncolors; ++q) {
+            const int c = reverse ? S.ncolors - 1 - q : q;
+            launch_sor_colour(S.rec + (size_t)4 * S.blk_first[c], S.blk_first[c + 1] - S.blk_first[c], S.nt, a, st_);
+        }
+}
+
+bool Engine::op_sor(int l, const double *b, double *x, int sweeps, bool reverse, bool x_is_zero)
+{
+    if (!build_sor_level(l)) return false;
+    if (x_is_zero && sweeps > 0) launch_fill(lev_[l].n, 0.0, x, st_);
+    sor_leg(l, b, x, sweeps, reverse);
+    return true;
+}
+
+// AMG_solve_SOR (src/AMG_phases.cpp:234-306): the Jacobi cycle's hierarchy and order of operations, with plain residual,
+// restriction, coarse-solve and prolongation launches and nothing of the Jacobi smoother fused into them.
+void Engine::vcycle_sor(const double *b0, bool x0_zero, double *dot_partial, int *dot_nblk)
+{
+    const int last = (int)lev_.size() - 1;
+    const int nu = sor_sweeps();
+    lev_[0].b = const_cast<double *>(b0);
+    if (last == 0) {
+        op_coarse(b0, lev_[0].x);
+        if (dot_partial) launch_dot(lev_[0].n, lev_[0].x, b0, dot_partial, dot_nblk, st_);
+        return;
+    }
+    for (int l = 0; l < last; ++l) {
+        DevLevel &L = lev_[l];
+        if (l > 0 || x0_zero) launch_fill(L.n, 0.0, L.x, st_);  // fill(Xv[l1+1], ..., 0.0)
+        sor_leg(l, L.b, L.x, nu, false);                        // pre-smoothing: colours 1..C
+        op_residual(l, L.b, L.x, L.r);                           // store_residual
+        op_restrict(l, L.r, lev_[l + 1].b, false);               // transfer_residual
+    }
+    op_coarse(lev_[last].b, lev_[last].x);  // Direct_Solver_Pardiso_solve
+    const bool rev = sor_order_ == SPARSH_SOR_SYMMETRIC;
+    for (int l = last; l > 0; --l) {
+        DevLevel &F = lev_[l - 1];
+        op_prolong(l - 1, lev_[l].x, F.x);  // transfer_solution
+        sor_leg(l - 1, F.b, F.x, nu, rev);
+    }
+    if (dot_partial) launch_dot(lev_[0].n, lev_[0].x, b0, dot_partial, dot_nblk, st_);
+}
+
 // One V(nu,nu) cycle (body of the while loops in AMG_solve_jacobi, src/AMG_phases.cpp:198-216).
 void Engine::vcycle(const double *b0, bool x0_zero, double *dot_partial, int *dot_nblk, bool zero_done0)
 {
+    if (sor_on()) {
+        vcycle_sor(b0, x0_zero, dot_partial, dot_nblk);
+        return;
+    }
     const int last = (int)lev_.size() - 1;
     const int nu = prm_.sweeps;
     lev_[0].b = const_cast<double *>(b0);
@@ -1950,6 +2135,7 @@ void Engine::vcycle(const double *b0, bool x0_zero, double *dot_partial, int *do
 int Engine::amg_solve_dev(const double *b, double *x, int iterations, double *hist, int hist_cap, int *ncycles)
 {
     if (!ready_) return SPARSH_ESTATE;
+    if (int rc = sor_prepare(); rc != SPARSH_OK) return rc;
     DevLevel &L0 = lev_[0];
     const int n = L0.n;
     HIPCHK(hipMemcpyAsync(L0.x, x, (size_t)n * 8, hipMemcpyDeviceToDevice, st_));
@@ -1993,8 +2179,21 @@ int Engine::amg_solve_dev(const double *b, double *x, int iterations, double *hi
 // Solver_CG_1 (precond = false) / Solver_PCG_1 (precond = true), split into the part before
 // the while loop (pcg_init: r0, ||r0||, z0 = V(r0), p = z0; src/AMG_main_solvers.cpp:124-133)
 // and the loop body (pcg_steps: :136-159) so a caller can time exactly k iterations.
+// AMG-PCG with the smoother selected now: SOR needs the symmetric order and its layouts (the smoother may change between
+// krylov_init and krylov_step)
+int Engine::pcg_smoother_check()
+{
+    if (sor_on() && sor_order_ != SPARSH_SOR_SYMMETRIC) {
+        error = "SPARSH_PCG needs a symmetric preconditioner: the SOR smoother must use SPARSH_SOR_SYMMETRIC";
+        return SPARSH_EINVAL;
+    }
+    return sor_prepare();
+}
+
 int Engine::pcg_init(const double *b, double *x, bool precond)
 {
+    if (precond)
+        if (int rc = pcg_smoother_check(); rc != SPARSH_OK) return rc;
     const int n = lev_[0].n;
     double *r = work_[0], *p = work_[1];
     int nb = 0;
@@ -2046,7 +2245,7 @@ void Engine::pcg_body(bool precond, int slot)
     // are reduced together with z.r after the V-cycle: one finalize launch (one all-reduce) less
     // with the fp64 V-cycle behind it the update also writes the cycle's zero-guess sweep of level 0 (z0 = omega r / d)
     // (... unless the cycle's first launch on level 0 is the three-sweep one, which reads r alone)
-    const bool fuse_zero = cfg_.fuse_cg_zero && precond && !f32_ready_ && lev_.size() > 1 && !lev_[0].deep && prm_.sweeps > 0 &&
+    const bool fuse_zero = cfg_.fuse_cg_zero && precond && !f32_ready_ && !sor_on() && lev_.size() > 1 && !lev_[0].deep && prm_.sweeps > 0 &&
                            !(prm_.sweeps >= 3 && zero_start(lev_[0]));
     // with the fp64 V-cycle behind it x += alpha p waits for the direction update at the end of this iteration (one read of p for both)
     const bool defer_x = cfg_.defer_x && precond && !f32_ready_;
@@ -2109,6 +2308,11 @@ int Engine::pcg_steps(int nsteps, int *done)
         return SPARSH_ESTATE;
     }
     const bool precond = ks_.precond;
+    if (precond)
+        if (int rc = pcg_smoother_check(); rc != SPARSH_OK) {
+            if (done) *done = 0;
+            return rc;
+        }
     int rc = SPARSH_OK;
     int did = 0;
     const int check_every = std::max(1, prm_.check_every);
@@ -2162,6 +2366,8 @@ int Engine::pcg(const double *b, double *x, int max_iters, double *hist, int his
 // Solver_BiCG_1 (precond = false) / Solver_PBiCG_1 (precond = true).
 int Engine::bicg(const double *b, double *x, int max_iters, double *hist, int hist_cap, int *iters, bool precond)
 {
+    if (precond)
+        if (int rc = sor_prepare(); rc != SPARSH_OK) return rc;
     const int n = lev_[0].n;
     double *r0 = work_[0], *r = work_[1], *p = work_[2], *Ap = work_[3], *s = work_[4], *As = work_[5], *p1buf = work_[6];
     int nb = 0;

@@ -50,6 +50,19 @@ struct DevLevel {
     bool fine = false;                   // finest level of the hierarchy
 };
 
+// Device layout of one level for the multicolour SOR smoother: a colour-compacted copy of the operator (rows colour by colour,
+// ascending inside a colour; col / val in stored order), so that each colour's launch streams one contiguous block.
+struct SorLevel {
+    int n = 0, ncolors = 0;
+    std::vector<int> cstart;     // host copy: ncolors + 1 compacted row offsets
+    std::vector<int> blk_first;  // ncolors + 1: first row-block record of every colour
+    int *dcstart = nullptr, *rows = nullptr, *rowptr = nullptr, *col = nullptr, *rec = nullptr;
+    double *val = nullptr, *diag = nullptr;
+    bool nt = false;      // the per-colour launches stream the matrix past the caches (level larger than the Infinity Cache)
+    bool single = false;  // small level: a whole leg is one launch (launch_sor_level)
+    size_t bytes = 0;     // device bytes of the layout
+};
+
 struct KrylovState {
     bool active = false, precond = false;
     const double *b = nullptr;
@@ -104,6 +117,30 @@ public:
     const CoarseSolver &coarse() const { return coarse_; }
     CoarseSolver &coarse_mut() { return coarse_; }
     const sparsh_params &params() const { return prm_; }
+    // ---- smoother (SPARSH_SMOOTH_JACOBI default / SPARSH_SMOOTH_SOR): sweeps 0 = default (params.sweeps / 6)
+    void set_smoother(int kind, int sweeps, int order);
+    int smoother() const { return smoother_; }
+    bool sor_on() const { return smoother_ == SPARSH_SMOOTH_SOR; }
+    int sor_sweeps() const { return sm_sweeps_ > 0 ? sm_sweeps_ : kSorDefaultSweeps; }
+    int sor_order() const { return sor_order_; }
+    // debug knob: 0 the level policy (single launch up to kSorSingleNnz entries), 1 per-colour launches on every level, 2 one launch on every level
+    void set_sor_path(int mode) { sor_path_ = mode; }
+    // colour classes of level l (host; computed on first use after setup_host)
+    const ColorClasses &level_colors(int l);
+    // SOR layouts ready for a solve on this handle (built now if the smoother was chosen after setup); SPARSH_* code
+    int sor_prepare();
+    const SorLevel *sor_level(int l) const { return l >= 0 && l < (int)sor_.size() && sor_[l].rows ? &sor_[l] : nullptr; }
+    bool sor_single(int l) const { return sor_path_ == 2 || (sor_path_ == 0 && sor_[l].single); }  // a leg of level l is one launch
+    // `sweeps` SOR sweeps of level l on x in place (colours C..1 when reverse), issued as a smoothing leg issues them
+    void sor_leg(int l, const double *b, double *x, int sweeps, bool reverse);
+    // the same as a test hook on any level whatever the smoother (x_is_zero: x is taken as 0); false if the layouts cannot be built
+    bool op_sor(int l, const double *b, double *x, int sweeps, bool reverse, bool x_is_zero);
+    bool build_sor_layouts();     // layouts of the smoothed levels (all but the coarsest); no-op once built for the current setup
+    bool build_sor_level(int l);  // layout of level l alone (op_sor / bench on any level, the coarsest included)
+    static constexpr int kSorDefaultSweeps = 6;  // AMG_solve_SOR's count (src/AMG_phases.cpp:252)
+    // levels with at most this many entries run a leg as one launch: 0, the single launch was slower than the per-colour launches on
+    // every level measured on the MI355X, down to 3 774 rows / 25 940 entries
+    static constexpr long kSorSingleNnz = 0;
     // kernel-family / layout choices of THIS handle (const_slots is read when the layouts are built)
     // (mutable access is for the C ABI's setters, which call config_changed() afterwards)
     KernelConfig &kernel_cfg() { return cfg_; }
@@ -259,6 +296,17 @@ private:
     double read_scalar(int slot);
     double read_hist(int it);
 
+    // one V(nu,nu) cycle with the SOR smoother: the Jacobi cycle's order of operations without any fused Jacobi step
+    void vcycle_sor(const double *b0, bool x0_zero, double *dot_partial, int *dot_nblk);
+    void adopt_sweeps();
+    int pcg_smoother_check();  // SPARSH_PCG under the current smoother: symmetric SOR order, layouts built  // prm_.sweeps = the Jacobi sweep count this handle's smoother selection asks for
+    int smoother_ = SPARSH_SMOOTH_JACOBI;
+    int sm_sweeps_ = 0;       // sweeps of sparsh_set_smoother (0: the default)
+    int sor_order_ = SPARSH_SOR_FORWARD;
+    int sor_path_ = 0;
+    int base_sweeps_ = 0;     // params.sweeps of the last setup
+    std::vector<ColorClasses> colors_;  // per level, filled on first use
+    std::vector<SorLevel> sor_;         // per level device layouts (empty until built)
     bool setup_f32();
     // V(nu,nu) cycle on the float hierarchy from a zero guess: z64 = V32(r64), partial sums of z.r
     void vcycle_f32(const double *r64, double *z64, double *partial, int *nblk);

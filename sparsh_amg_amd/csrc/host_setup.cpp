@@ -210,6 +210,47 @@ HostCsr transpose(const HostCsr &A)
     return T;
 }
 
+ColorClasses greedy_colors(const HostCsr &A)
+{
+    const int n = A.nrow;
+    ColorClasses C;
+    C.color.assign((size_t)n, 0);
+    // pattern of A^T (rows of A that refer to column i), so that row i also sees the rows that refer to it
+    std::vector<int> tp((size_t)n + 1, 0);
+    for (int i = 0; i < n; ++i)
+        for (int j = A.rowptr[i]; j < A.rowptr[i + 1]; ++j)
+            if (A.col[j] < n) tp[(size_t)A.col[j] + 1]++;
+    for (int i = 0; i < n; ++i) tp[(size_t)i + 1] += tp[i];
+    std::vector<int> tc((size_t)tp[n]);
+    {
+        std::vector<int> cur(tp.begin(), tp.end() - 1);
+        for (int i = 0; i < n; ++i)
+            for (int j = A.rowptr[i]; j < A.rowptr[i + 1]; ++j)
+                if (A.col[j] < n) tc[(size_t)cur[A.col[j]]++] = i;
+    }
+    std::vector<int> mark(2, -1);  // mark[c] == i: colour c is taken by a neighbour of row i
+    for (int i = 0; i < n; ++i) {
+        auto take = [&](int j) {
+            if (j != i && j < n && C.color[j] != 0) mark[C.color[j]] = i;
+        };
+        for (int j = A.rowptr[i]; j < A.rowptr[i + 1]; ++j) take(A.col[j]);
+        for (int j = tp[i]; j < tp[i + 1]; ++j) take(tc[j]);
+        int c = 1;
+        while (c < (int)mark.size() && mark[c] == i) ++c;
+        if (c + 1 >= (int)mark.size()) mark.resize((size_t)c + 2, -1);
+        C.color[i] = c;
+        C.ncolors = std::max(C.ncolors, c);
+    }
+    // colour c (1-based) occupies rows[start[c - 1] .. start[c])
+    C.start.assign((size_t)C.ncolors + 1, 0);
+    for (int i = 0; i < n; ++i) C.start[C.color[i]]++;
+    for (int c = 1; c <= C.ncolors; ++c) C.start[c] += C.start[c - 1];
+    C.rows.resize((size_t)n);
+    std::vector<int> cur(C.start.begin(), C.start.end() - 1);
+    for (int i = 0; i < n; ++i) C.rows[(size_t)cur[C.color[i] - 1]++] = i;
+    return C;
+}
+
 namespace {
 
 // C = A * B, row-parallel with a dense accumulator per thread; all structural entries kept

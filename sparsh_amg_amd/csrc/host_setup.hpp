@@ -94,6 +94,18 @@ std::vector<int> rcm_order(const HostCsr &A);
 // dense inverse of a sparse matrix through RCM + banded LU (partial pivoting); false if singular
 bool sparse_inverse(const HostCsr &A, std::vector<double> &inv);
 
+// Colour classes of the multicolour SOR smoother: greedy first-fit over the rows in ascending order on the pattern of
+// A + A^T without the diagonal (no two rows of one colour refer to each other, also for an unsymmetric pattern).  Colours are
+// numbered from 1; for a structurally symmetric A the classes equal those of the reference's color_matrix_and_reorder
+// (src/AMG_cpu_matrix.cpp:81-130).
+struct ColorClasses {
+    int ncolors = 0;
+    std::vector<int> color;  // per row, 1 .. ncolors
+    std::vector<int> start;  // ncolors + 1 offsets: colour c occupies rows[start[c - 1] .. start[c])
+    std::vector<int> rows;   // the rows colour by colour, ascending inside a colour
+};
+ColorClasses greedy_colors(const HostCsr &A);
+
 // rough size of the nested-dissection factors of A (nd_plan.cpp; one breadth-first search, no dissection)
 size_t nd_estimate_factor_bytes(const HostCsr &A);
 

@@ -2929,4 +2929,120 @@ void launch_cvt_f2d_dot(int n, const float *z32, const double *r64, double *z64,
     hipLaunchKernelGGL(cvt_f2d_dot_kernel, dim3(g), dim3(kBlock), 0, st, n, z32, r64, z64, partial);
 }
 
+// ------------------------------------------------------------------ multicolour SOR (Gauss-Seidel) smoother
+//
+// parallel::sor_smoother (src/AMG_smoothers.cpp:78-102) on the original row order: the rows of one colour are
+// independent in the pattern of A + A^T, so a launch updates all of them in place at once.  Per row:
+//   s = sum_j a_ij x_j (products rounded, added one by one in stored order, from 0.0) ; h = s - b_i ; x_i = x_i - (omega*h)/d_i.
+// The operands come from the colour-compacted copy of the level (SorArgs): rows[k] is the level row of compacted row k, rowptr /
+// col / val / diag follow the compacted order, b and x are indexed by level row.
+
+namespace {
+
+// Per-colour kernel: the product-park-then-row-sum scheme of csr_block_kernel on one colour's row blocks (records
+// {first, end compacted row, first, end entry}).  Rows of this colour never read each other's x (a row's own x_i is read by its
+// own workgroup before it is written), so the in-place update needs no second buffer.
+template <bool NT>
+__global__ __launch_bounds__(kBlock) void sor_colour_kernel(const int4 *__restrict__ rec, int nblk, int remap, SorArgs a)
+{
+    __shared__ double prod[kStreamNnz];
+    const int bid = remap ? xcd_remap(blockIdx.x, nblk, remap) : blockIdx.x;
+    if (bid >= nblk) return;  // whole workgroup leaves together
+    const int4 br = rec[bid];
+    const int nrows = br.y - br.x;
+    const int j0 = br.z, j1 = br.w;
+    const int tid = threadIdx.x;
+    const bool has_row = tid < nrows;
+    const int k = br.x + tid;
+    int i = 0, s = 0, e = 0;
+    double bi = 0.0, di = 1.0, xi = 0.0;
+    if (has_row) {  // row operands first: their latency hides under the product stream
+        i = a.rows[k];
+        s = a.rowptr[k] - j0;
+        e = a.rowptr[k + 1] - j0;
+        bi = a.b[i];
+        di = a.diag[k];
+        xi = a.x[i];
+    }
+    double sum = 0.0;
+    if (j1 - j0 <= kStreamNnz) {
+        stream_products<NT, 1>(a.col, a.val, a.x, j0, j1, tid, kBlock, prod);
+        __syncthreads();
+        if (has_row) sum = row_sum_lds(prod, s, e);
+    } else {
+        // a single row longer than the LDS buffer: its products are parked chunk by chunk and added in order by its thread
+        for (int c0 = j0; c0 < j1; c0 += kStreamNnz) {
+            const int c1 = c0 + kStreamNnz < j1 ? c0 + kStreamNnz : j1;
+            stream_products<NT, 1>(a.col, a.val, a.x, c0, c1, tid, kBlock, prod);
+            __syncthreads();
+            if (tid == 0)
+                for (int q = 0; q < c1 - c0; ++q) sum = sum + prod[q];
+            __syncthreads();
+        }
+    }
+    if (has_row) {
+        const double h = sum - bi;
+        a.x[i] = xi - a.omega * h / di;
+    }
+}
+
+// Small-level kernel: one workgroup runs every colour of every sweep of a leg; a barrier separates the colours (the waves of one
+// workgroup share a CU, so its stores are visible to the other waves after the barrier).  Thread = row; the loads of a row are
+// issued eight entries at a time (clamped index), the adds stay in stored order -- bitwise the per-colour launches.
+__global__ __launch_bounds__(kBlock) void sor_level_kernel(const int *__restrict__ cstart, int ncolors, int sweeps, int reverse, SorArgs a)
+{
+    for (int sw = 0; sw < sweeps; ++sw) {
+        for (int q = 0; q < ncolors; ++q) {
+            const int c = reverse ? ncolors - 1 - q : q;
+            const int k1 = cstart[c + 1];
+            for (int k = cstart[c] + (int)threadIdx.x; k < k1; k += kBlock) {
+                const int i = a.rows[k];
+                const int j0 = a.rowptr[k], j1 = a.rowptr[k + 1];
+                const double bi = a.b[i], di = a.diag[k], xi = a.x[i];
+                double sum = 0.0;
+                for (int j = j0; j < j1; j += 8) {
+                    int cc[8];
+                    double v[8], xv[8];
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) {
+                        const int jj = j + u < j1 ? j + u : j1 - 1;
+                        cc[u] = a.col[jj];
+                        v[u] = a.val[jj];
+                    }
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) xv[u] = a.x[cc[u]];
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) {
+                        const double t = v[u] * xv[u];
+                        sum = (j + u < j1) ? sum + t : sum;
+                    }
+                }
+                const double h = sum - bi;
+                a.x[i] = xi - a.omega * h / di;
+            }
+            __syncthreads();
+        }
+    }
+}
+
+}  // namespace
+
+void launch_sor_colour(const int *rec, int nblk, bool nt, const SorArgs &a, hipStream_t st)
+{
+    if (nblk <= 0) return;
+    const int remap = 1;
+    const dim3 g(remap_grid(nblk, remap));
+    const int4 *r = reinterpret_cast<const int4 *>(rec);
+    if (nt)
+        hipLaunchKernelGGL(sor_colour_kernel<true>, g, dim3(kBlock), 0, st, r, nblk, remap, a);
+    else
+        hipLaunchKernelGGL(sor_colour_kernel<false>, g, dim3(kBlock), 0, st, r, nblk, remap, a);
+}
+
+void launch_sor_level(const int *cstart, int ncolors, int sweeps, bool reverse, const SorArgs &a, hipStream_t st)
+{
+    if (ncolors <= 0 || sweeps <= 0) return;
+    hipLaunchKernelGGL(sor_level_kernel, dim3(1), dim3(kBlock), 0, st, cstart, ncolors, sweeps, reverse ? 1 : 0, a);
+}
+
 }  // namespace sparsh

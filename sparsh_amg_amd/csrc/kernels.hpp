@@ -236,6 +236,23 @@ void launch_restrict_agg_zero(int nc, const int *rowptr, const int *col, const d
 // x = A^{-1} b with the explicit row-major inverse (coarsest level)
 void launch_gemv(int n, const double *M, const double *b, double *x, hipStream_t st);
 
+// ---- multicolour SOR smoother (parallel::sor_smoother, src/AMG_smoothers.cpp:78-102) on a level's colour-compacted copy
+struct SorArgs {
+    const int *rows = nullptr;     // level row of every compacted row (colour by colour, ascending inside a colour)
+    const int *rowptr = nullptr;   // compacted CSR: rowptr / col / val (col and val carry kCsrPad zeroed tail entries)
+    const int *col = nullptr;
+    const double *val = nullptr;
+    const double *diag = nullptr;  // diagonal entry of every compacted row
+    const double *b = nullptr;     // right-hand side, by level row
+    double *x = nullptr;           // iterate, by level row, updated in place
+    double omega = 0.0;
+};
+// one colour: rec = that colour's row-block records (4 ints each, rowblock_records over the compacted rowptr); nt: non-temporal
+// loads of the matrix stream
+void launch_sor_colour(const int *rec, int nblk, bool nt, const SorArgs &a, hipStream_t st);
+// every colour (C..1 when reverse) of `sweeps` sweeps in one single-workgroup launch; cstart = ncolors + 1 compacted row offsets
+void launch_sor_level(const int *cstart, int ncolors, int sweeps, bool reverse, const SorArgs &a, hipStream_t st);
+
 // ---- BLAS-1 (daxpby/daxpbyc kernels, cublasDaxpy/Ddot/Dnrm2, thrust::fill of the reference)
 void launch_fill(int n, double v, double *x, hipStream_t st);
 void launch_copy(int n, const double *x, double *y, hipStream_t st);
