@@ -226,6 +226,14 @@ int sparsh_set_zero_start(sparsh_handle h, int enable);
  * updates (one n-vector stream less per iteration).  Same expressions, same bits.  enable: 1 (default) / 0 (A/B). */
 int sparsh_set_deferred_x(sparsh_handle h, int enable);
 int sparsh_level_marching_ops(sparsh_handle h, int level, int *on, int *plan, double *table_us, double *marching_us);
+/* Test hook: the launch plan {points per thread q, lines per tile ty, planes per chunk cz} of a box-grid level's double sweep
+ * (kernel 2) or plane-marching kernel (kernel 1) instead of the planner's; (0, 0, 0) restores the planner's plan (box2_plan /
+ * box1_plan), kernel 3 with (0, 0, 0) takes the marching kernel's shared-CU plan without timing it.  SPARSH_EINVAL for a level that
+ * is not a box grid and for a plan the kernel cannot run: q outside {2, 3, 4}, ty outside 1 .. ny, cz outside 1 .. nz, a tile region
+ * ((ty + 4) nx points for kernel 2, (ty + 2) nx for kernel 1) larger than q 1024 threads cover or than 64 KiB of LDS, a marching
+ * launch with more workgroups than the reduction buffers hold.  Does not switch a kernel on (sparsh_set_double_sweep /
+ * sparsh_set_marching_ops); drops a captured graph.  sparsh_level_double_sweep / sparsh_level_marching_ops report the plan in force. */
+int sparsh_set_box_plan(sparsh_handle h, int level, int kernel, int q, int ty, int cz);
 int sparsh_level_double_sweep(sparsh_handle h, int level, int *on, int *dims, int *plan, double *single_us, double *double_us);
 int sparsh_level_constant_diagonal(sparsh_handle h, int level, int *is_const, double *value);
 int sparsh_level_prolong_fused(sparsh_handle h, int level, int *fused);
@@ -379,6 +387,10 @@ int sparsh_op_prolong(sparsh_handle h, int level, const double *xc, double *xf);
 /* levels sparsh_level_prolong_fused reports: xf (level - 1, in/out) += P_{level-1} J(x), J = one Jacobi sweep of `level`
  * from x with right-hand side b -- the one launch the V-cycle's up-leg uses there */
 int sparsh_op_jacobi_prolong(sparsh_handle h, int level, const double *b, const double *x, double *xf);
+/* the launches with a fused dot product, as PCG and the V-cycle's last post-sweep run them on the level (table or plane-marching
+ * kernel, then the same final reduction): y = A_l x and *dot = x.y; y = one Jacobi sweep of x and *dot = y.b */
+int sparsh_op_spmv_dot(sparsh_handle h, int level, const double *x, double *y, double *dot);
+int sparsh_op_jacobi_dot(sparsh_handle h, int level, const double *b, const double *x, double *y, double *dot);
 int sparsh_op_coarse(sparsh_handle h, const double *b, double *x);
 /* z = V32(r): one application of the opt-in fp32 preconditioner (params.precond_fp32 = 1): a V(nu,nu) cycle from a
  * zero guess on the float copy of the hierarchy, fp64 in/out.  Checked against oracle_vcycle_f32. */

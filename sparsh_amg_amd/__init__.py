@@ -108,6 +108,9 @@ def _load():
         "sparsh_level_constant_diagonal": (C.c_int, [H, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double)]),
         "sparsh_level_prolong_fused": (C.c_int, [H, C.c_int, C.POINTER(C.c_int)]),
         "sparsh_op_jacobi_prolong": (C.c_int, [H, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p]),
+        "sparsh_set_box_plan": (C.c_int, [H, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+        "sparsh_op_spmv_dot": (C.c_int, [H, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p]),
+        "sparsh_op_jacobi_dot": (C.c_int, [H, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p]),
         "sparsh_level_paired": (C.c_int, [H, C.c_int, C.POINTER(C.c_int)]),
         "sparsh_set_fused_zero_sweep": (C.c_int, [H, C.c_int]),
         "sparsh_set_placement_search": (C.c_int, [H, C.c_int]),
@@ -389,6 +392,19 @@ class sp_matrix_mg:
         _check(lib.sparsh_level_marching_ops(self._h, int(level), C.byref(on), plan, C.byref(t1), C.byref(t2)))
         return {"on": bool(on.value), "points_per_thread": plan[0], "lines_per_tile": plan[1], "planes_per_chunk": plan[2],
                 "table_kernel_us": round(t1.value, 2), "marching_kernel_us": round(t2.value, 2)}
+
+    def set_box_plan(self, level, kernel, q=0, ty=0, cz=0, shared_cu=False):
+        """Test hook: launch plan (points per thread, lines per tile, planes per chunk) of box-grid level `level`'s double sweep
+        (kernel 2 or "double") or plane-marching kernel (1 or "marching"); q = ty = cz = 0 restores the planner's plan, with
+        shared_cu (marching kernel) its shared-CU plan.  Does not switch the kernel on; the plan in force shows in level_double_sweep /
+        level_marching_ops.  SparshError (EINVAL) for a plan the kernel cannot run."""
+        k = {"double": 2, "marching": 1}.get(kernel, kernel)
+        if shared_cu:
+            if k != 1:
+                raise ValueError("shared_cu is a plan of the marching kernel")
+            k = 3
+        _check(lib.sparsh_set_box_plan(self._h, int(level), int(k), int(q), int(ty), int(cz)))
+        return self
 
     def set_constant_diagonal(self, enable=True):
         """Levels with one constant diagonal: the zero-guess sweeps take it as an argument instead of streaming diag[]."""
@@ -829,6 +845,23 @@ class sp_matrix_mg:
         out = C.c_double()
         _check(lib.sparsh_op_resnorm(self._h, level, _dp(b), _dp(x), C.byref(out)))
         return out.value
+
+    def op_spmv_dot(self, level, x):
+        """(A_l x, x . A_l x) through the launch PCG uses for A p and p.Ap on this level."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        y = np.zeros(self.level_info(level)["nrow"])
+        dot = C.c_double()
+        _check(lib.sparsh_op_spmv_dot(self._h, int(level), _dp(x), _dp(y), C.byref(dot)))
+        return y, dot.value
+
+    def op_jacobi_dot(self, level, b, x):
+        """(y, y . b), y = one Jacobi sweep of x, through the launch of the V-cycle's last post-sweep with its fused dot."""
+        b = np.ascontiguousarray(b, dtype=np.float64)
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        y = np.zeros_like(b)
+        dot = C.c_double()
+        _check(lib.sparsh_op_jacobi_dot(self._h, int(level), _dp(b), _dp(x), _dp(y), C.byref(dot)))
+        return y, dot.value
 
     def op_restrict(self, level, r):
         r = np.ascontiguousarray(r, dtype=np.float64)

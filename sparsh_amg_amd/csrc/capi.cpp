@@ -486,6 +486,14 @@ int sparsh_level_marching_ops(sparsh_handle h, int level, int *on, int *plan, do
     return SPARSH_OK;
 }
 
+int sparsh_set_box_plan(sparsh_handle h, int level, int kernel, int q, int ty, int cz)
+{
+    REQUIRE_READY(h);
+    REQUIRE_LEVEL(h, level);
+    const int rc = h->eng->set_box_plan(level, kernel, q, ty, cz);
+    return rc == SPARSH_OK ? SPARSH_OK : fail(rc, h->eng->error);
+}
+
 int sparsh_set_constant_diagonal(sparsh_handle h, int enable)
 {
     if (!h || !h->eng) return fail(SPARSH_EINVAL, "null handle");
@@ -1161,6 +1169,34 @@ int sparsh_op_resnorm(sparsh_handle h, int level, const double *b, const double 
     DBuf db(E, n, b), dx(E, n, x);
     *nrm = E.op_resnorm(level, db.p, dx.p);
     return SPARSH_OK;
+}
+
+int sparsh_op_spmv_dot(sparsh_handle h, int level, const double *x, double *y, double *dot)
+{
+    REQUIRE_READY(h);
+    REQUIRE_SINGLE(h);
+    REQUIRE_LEVEL(h, level);
+    Engine &E = *h->eng;
+    const DevLevel &L = E.level(level);
+    DBuf dx(E, (size_t)L.A.ncol, x), dy(E, (size_t)L.n);
+    if (!dx.p || !dy.p) return fail(SPARSH_ENODEV, E.error);
+    const double d = E.op_spmv_dot(level, dx.p, dy.p);
+    if (dot) *dot = d;
+    return done(E, dy.get(y));
+}
+
+int sparsh_op_jacobi_dot(sparsh_handle h, int level, const double *b, const double *x, double *y, double *dot)
+{
+    REQUIRE_READY(h);
+    REQUIRE_SINGLE(h);
+    REQUIRE_LEVEL(h, level);
+    Engine &E = *h->eng;
+    const DevLevel &L = E.level(level);
+    DBuf db(E, (size_t)L.n, b), dx(E, (size_t)L.A.ncol, x), dy(E, (size_t)L.n);
+    if (!db.p || !dx.p || !dy.p) return fail(SPARSH_ENODEV, E.error);
+    const double d = E.op_jacobi_dot(level, db.p, dx.p, dy.p);
+    if (dot) *dot = d;
+    return done(E, dy.get(y));
 }
 
 int sparsh_op_restrict(sparsh_handle h, int level, const double *r, double *bc)

@@ -485,7 +485,8 @@ bool upload_csr(Engine &E, const HostCsr &A, DevCsr &D, bool with_sell, const st
     return true;
 }
 
-int partial_count(const DevCsr &D) { return std::max(D.nblk, std::max((D.nwblk + 3) / 4, (D.nslice + 3) / 4)); }
+// partials of a reducing launch on D: one per row block / four wave blocks / four slices, one per workgroup of the plane-marching kernel
+int partial_count(const DevCsr &D) { return std::max(std::max(D.nblk, box1_workgroups(D)), std::max((D.nwblk + 3) / 4, (D.nslice + 3) / 4)); }
 
 }  // namespace
 
@@ -714,8 +715,9 @@ void Engine::tune_box_kernels()
             L.box1_table_us = timed1(false);
             L.box1_us = timed1(true);
             {  // the plan that lets two workgroups share a CU, if it is another one: keep the faster
+                // (more workgroups than the partial buffers hold: not a candidate)
                 const int q0 = L.A.box1_q, ty0 = L.A.box1_ty, cz0 = L.A.box1_cz;
-                if (box1_plan(L.A, true) && (L.A.box1_q != q0 || L.A.box1_ty != ty0 || L.A.box1_cz != cz0)) {
+                if (box1_plan(L.A, true) && (L.A.box1_q != q0 || L.A.box1_ty != ty0 || L.A.box1_cz != cz0) && box1_workgroups(L.A) <= part_cap_) {
                     const double t_alt = timed1(true);
                     if (t_alt < L.box1_us) {
                         L.box1_us = t_alt;
@@ -1707,6 +1709,68 @@ void Engine::op_jacobi_prolong(int l, const double *b, const double *x, double *
     a.members = F.pair_aggregates ? nullptr : F.members;
     a.nfine = F.n;
     apply_A(lev_[l], OP_JACOBI_PROLONG, a);
+}
+
+double Engine::op_spmv_dot(int l, const double *x, double *y)
+{
+    CsrArgs a;
+    a.x = x;
+    a.y = y;
+    a.partial = part0_;
+    const int np = apply_A(lev_[l], OP_SPMV_DOT, a);
+    finalize(FIN_STORE, part0_, nullptr, np, S_TMP, nullptr, 0);
+    return read_scalar(S_TMP);
+}
+
+double Engine::op_jacobi_dot(int l, const double *b, const double *x, double *y)
+{
+    CsrArgs a;
+    a.x = x;
+    a.b = b;
+    a.y = y;
+    a.d = lev_[l].diag;
+    a.omega = prm_.omega;
+    a.partial = part0_;
+    const int np = apply_A(lev_[l], OP_JACOBI_DOT, a);
+    finalize(FIN_STORE, part0_, nullptr, np, S_TMP, nullptr, 0);
+    return read_scalar(S_TMP);
+}
+
+int Engine::set_box_plan(int l, int kernel, int q, int ty, int cz)
+{
+    auto refuse = [&](const std::string &why) {
+        error = why;
+        return SPARSH_EINVAL;
+    };
+    DevCsr &A = lev_[l].A;
+    if (A.box_nx <= 0) return refuse("level " + std::to_string(l) + " is not a box grid");
+    if (kernel < 1 || kernel > 3) return refuse("kernel must be 2 (double sweep), 1 (plane-marching kernel) or 3 (its shared-CU plan)");
+    const bool planner = q == 0 && ty == 0 && cz == 0;
+    if (kernel == 3 && !planner) return refuse("kernel 3 takes the planner's shared-CU plan: q, ty and cz must be 0");
+    DevCsr T = A;  // (the planners write their plan into the operator: try it on a copy)
+    if (planner) {
+        if (!(kernel == 2 ? box2_plan(T) : box1_plan(T, kernel == 3))) return refuse("the planner has no plan for this grid");
+        q = kernel == 2 ? T.box_q : T.box1_q;
+        ty = kernel == 2 ? T.box_ty : T.box1_ty;
+        cz = kernel == 2 ? T.box_cz : T.box1_cz;
+    }
+    if (const char *why = box_plan_refusal(A, kernel == 2 ? 2 : 1, q, ty, cz)) return refuse(why);
+    if (kernel == 2) {
+        A.box_q = q;
+        A.box_ty = ty;
+        A.box_cz = cz;
+    } else {
+        T.box1_q = q;
+        T.box1_ty = ty;
+        T.box1_cz = cz;
+        if (box1_workgroups(T) > part_cap_)
+            return refuse("the plan launches " + std::to_string(box1_workgroups(T)) + " workgroups; the partial buffers hold " + std::to_string(part_cap_));
+        A.box1_q = q;
+        A.box1_ty = ty;
+        A.box1_cz = cz;
+    }
+    config_changed();
+    return SPARSH_OK;
 }
 
 double Engine::op_resnorm(int l, const double *b, const double *x)

@@ -239,6 +239,13 @@ public:
     void op_jacobi(int l, const double *b, double *x, double *tmp, int sweeps, bool x_is_zero);  // result in x
     void op_residual(int l, const double *b, const double *x, double *r);
     double op_resnorm(int l, const double *b, const double *x);
+    // y = A_l x and x.y / y = J(x) and y.b, through the launches PCG and the V-cycle's last post-sweep use (fused dot, part0_)
+    double op_spmv_dot(int l, const double *x, double *y);
+    double op_jacobi_dot(int l, const double *b, const double *x, double *y);
+    // test hook: the launch plan of box-grid level l's double sweep (kernel 2) or plane-marching kernel (1); (0, 0, 0) = the planner's
+    // plan, kernel 3 = the marching kernel's shared-CU plan.  Refuses (SPARSH_EINVAL, reason in error) what the kernel cannot run or
+    // what writes more partials than part0_ / part1_ hold; does not switch the kernel on
+    int set_box_plan(int l, int kernel, int q, int ty, int cz);
     // fuse_zero: also write the coarse level's zero-guess sweep (aggregation P, no gather step); returns whether it did
     bool op_restrict(int l, const double *r, double *bc, bool fuse_zero = false);
     // level_paired(l) levels: b_{l+1} = R (b - A x) and x_{l+1} = omega b_{l+1} / d_{l+1} in one launch

@@ -1899,6 +1899,7 @@ int launch_csr_tagged(const DevCsr &A, const CsrArgs &a, bool nt, int remap, hip
 
 namespace {
 size_t box2_lds_bytes(int nx, int TY) { return (size_t)2 * ((size_t)(TY + 4) * (nx + 1) + 1) * sizeof(double); }
+size_t box1_lds_bytes(int nx, int TY) { return ((size_t)(TY + 2) * (nx + 1) + 1) * sizeof(double); }
 }  // namespace
 
 // Plan of the double sweep: Q points per thread, TY lines per tile, CZ planes per chunk.  Cost model (checked against
@@ -1946,7 +1947,7 @@ bool box1_plan(DevCsr &A, bool shared_cu)
     long best = -1;
     for (int Q = 2; Q <= 4; ++Q) {
         int TY = std::min(ny, Q * kBoxBlock / nx - 2);
-        while (TY >= 1 && ((size_t)(TY + 2) * (nx + 1) + 1) * sizeof(double) > 65536) --TY;
+        while (TY >= 1 && box1_lds_bytes(nx, TY) > 65536) --TY;
         if (TY < 1) continue;
         const int ytiles = (ny + TY - 1) / TY;
         for (int zch = 1; zch <= nz; ++zch) {
@@ -1965,6 +1966,26 @@ bool box1_plan(DevCsr &A, bool shared_cu)
         }
     }
     return A.box1_q > 0;
+}
+
+int box1_workgroups(const DevCsr &A)
+{
+    if (A.box1_q <= 0 || A.box1_ty <= 0 || A.box1_cz <= 0) return 0;
+    return ((A.box_ny + A.box1_ty - 1) / A.box1_ty) * ((A.box_nz + A.box1_cz - 1) / A.box1_cz);
+}
+
+const char *box_plan_refusal(const DevCsr &A, int kernel, int Q, int TY, int CZ)
+{
+    const int nx = A.box_nx, ny = A.box_ny, nz = A.box_nz;
+    if (nx <= 0) return "the level is not a box grid";
+    if (kernel != 1 && kernel != 2) return "kernel must be 2 (double sweep) or 1 (plane-marching kernel)";
+    if (Q < 2 || Q > 4) return "points per thread must be 2, 3 or 4";
+    if (TY < 1 || TY > ny) return "lines per tile must lie in 1 .. ny";
+    if (CZ < 1 || CZ > nz) return "planes per chunk must lie in 1 .. nz";
+    const int halo = kernel == 2 ? 4 : 2;  // region = TY + 4 (double sweep) / TY + 2 lines, one point per thread and q
+    if ((long)(TY + halo) * nx > (long)Q * kBoxBlock) return "the tile's region has more points than the workgroup's threads hold";
+    if ((kernel == 2 ? box2_lds_bytes(nx, TY) : box1_lds_bytes(nx, TY)) > 65536) return "the tile's region does not fit the 64 KiB of LDS";
+    return nullptr;
 }
 
 bool box1_applies(const DevCsr &A, const KernelConfig &c)
@@ -1996,7 +2017,7 @@ int launch_box1(const DevCsr &A, int epi, const CsrArgs &a, bool finest, hipStre
     const int chunks = (g.nz + g.CZ - 1) / g.CZ;
     const int nwg = g.ytiles * chunks;
     const dim3 grid(nwg), block(kBoxBlock);
-    const size_t lds = ((size_t)(g.TY + 2) * (g.nx + 1) + 1) * sizeof(double);
+    const size_t lds = box1_lds_bytes(g.nx, g.TY);
 #define SPARSH_LAUNCH_BOX1(Q_, E_)                                                                  \
     do {                                                                                            \
         if (finest) hipLaunchKernelGGL((sdia_box1_kernel<Q_, E_, 1>), grid, block, lds, st, g, b);  \

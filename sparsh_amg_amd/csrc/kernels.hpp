@@ -211,6 +211,11 @@ void launch_box_resid_pair(const DevCsr &A, int axis, const double *x, const dou
 // that runs double sweeps).  Returns the number of partial sums written.
 bool box1_plan(DevCsr &A, bool shared_cu = false);
 bool box1_applies(const DevCsr &A, const KernelConfig &cfg);
+// workgroups of a sdia_box1_kernel launch under the level's plan = the partial sums its reducing epilogues write (0: no plan)
+int box1_workgroups(const DevCsr &A);
+// why sdia_box2_kernel (kernel 2) / sdia_box1_kernel (kernel 1) cannot run the plan (Q, TY, CZ) on box-grid level A: a message, or
+// nullptr where it can (the planners' bounds: one point per thread and q of the tile's region, 64 KiB of LDS)
+const char *box_plan_refusal(const DevCsr &A, int kernel, int Q, int TY, int CZ);
 int launch_box1(const DevCsr &A, int epi, const CsrArgs &a, bool finest, hipStream_t st);
 // OP_RESID_PAIR over the whole of A (a.y = coarse rhs, a.y2 = coarse iterate, a.d = coarse diagonal); applies to operators
 // that run the table kernel under cfg -- resid_pair_applies says whether launch_resid_pair may be called
