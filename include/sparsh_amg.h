@@ -36,6 +36,8 @@ extern "C" {
 #define SPARSH_PCG 2    /* Solver_PCG_1..4                  (src/AMG_main_solvers.cpp:107-167, .cu:269-413) */
 #define SPARSH_BICG 3   /* Solver_BiCG_1                    (src/AMG_main_solvers.cpp:271-355) */
 #define SPARSH_PBICG 4  /* Solver_PBiCG_1..4                (src/AMG_main_solvers.cpp:358-458) */
+#define SPARSH_GMRES 5  /* restarted GMRES without a preconditioner (sparsh_set_gmres) */
+#define SPARSH_PGMRES 6 /* restarted GMRES, right-preconditioned with one V-cycle from a zero guess: the z = M v of SPARSH_PBICG */
 
 /* Smoother of the V-cycle (sparsh_set_smoother). */
 #define SPARSH_SMOOTH_JACOBI 0  /* weighted Jacobi, parallel::jacobi_smoother (default) */
@@ -395,6 +397,9 @@ int sparsh_op_coarse(sparsh_handle h, const double *b, double *x);
 /* z = V32(r): one application of the opt-in fp32 preconditioner (params.precond_fp32 = 1): a V(nu,nu) cycle from a
  * zero guess on the float copy of the hierarchy, fp64 in/out.  Checked against oracle_vcycle_f32. */
 int sparsh_op_precond_f32(sparsh_handle h, const double *r, double *z);
+/* z = M r exactly as the Krylov loops (SPARSH_PBICG, SPARSH_PGMRES) apply it: the V-cycle of the current smoother from a zero
+ * guess with the launches a zero start takes, or the fp32 cycle under params.precond_fp32 */
+int sparsh_op_precond(sparsh_handle h, const double *r, double *z);
 int sparsh_op_dot(sparsh_handle h, int n, const double *x, const double *y, double *out);
 int sparsh_op_nrm2(sparsh_handle h, int n, const double *x, double *out);
 int sparsh_op_axpby(sparsh_handle h, int n, double a, const double *x, double bcoef, double *y);
@@ -405,8 +410,32 @@ int sparsh_op_axpby(sparsh_handle h, int n, double a, const double *x, double bc
  * stream, calibrates the profiler's byte counters), 9 fused Jacobi sweeps ping-ponging between two vectors (the
  * access pattern of a smoothing leg), 10 the same on the level's own resident x / x2 / r buffers, 11 double sweeps
  * (sparsh_set_double_sweep) ping-ponging on those buffers: seconds per launch = per PAIR of sweeps, 12 one SOR sweep (all
- * colours) on the level's own x with r as the right-hand side, issued as a smoothing leg issues it (sparsh_set_sor_path). */
+ * colours) on the level's own x with r as the right-hand side, issued as a smoothing leg issues it (sparsh_set_sor_path),
+ * 13 one GMRES orthogonalisation step on level 0 (`level` must be 0): the last step of a restart cycle, w against
+ * restart basis vectors filled with a fixed pattern, through the fused kernels (two dot / update passes, reductions, rotation,
+ * normalisation; plus one copy that stands for the store of w), 14 the same step through one launch_dot + reduction and one
+ * launch_axpby per basis vector and pass, which is what the fused kernels replace. */
 int sparsh_bench_op(sparsh_handle h, int op, int level, int reps, double *avg_seconds);
+
+/* ---- restarted GMRES (SPARSH_GMRES, SPARSH_PGMRES) ----
+ * GMRES(m) with right preconditioning: x_k = x_0 + M V_k y_k, so the recurrence residual |g_{k+1}| that is stored in the history and
+ * compared with tol is the norm of the true residual b - A x up to rounding.  M is one V-cycle from a zero guess under the handle's
+ * smoother (Jacobi, SOR in either order -- GMRES needs no symmetric preconditioner) or the fp32 cycle; the identity for SPARSH_GMRES.
+ * Orthogonalisation is classical Gram-Schmidt applied twice, fused into one pass over the basis per sweep; the Hessenberg column,
+ * the Givens rotations, g and y stay in device memory and the host reads one history entry every check_every iterations (so up to
+ * check_every - 1 steps may run past convergence).  Every restart cycle starts from the true residual, whose norm is the stopping
+ * test of the solve and is not appended to the history.  SPARSH_ENOCONV at the iteration cap with x updated from the steps taken,
+ * SPARSH_ENUMERIC on a NaN.  A lucky breakdown (h_{j+1} not > 0) writes v_{j+1} = 0 without dividing; the cycle ends at its next check.
+ * params.use_graph = 1 is accepted and ignored: GMRES launches eagerly, because kernel arguments change with the step index.
+ * Refused with SPARSH_EINVAL on a partitioned (multi-GPU) handle: the j + 2 sums of a step need an all-reduce wider than the
+ * 16-byte one the engine has; that is a later change.
+ * sparsh_set_gmres: restart length 1..64, 0 restores the default of 30, anything else SPARSH_EINVAL.  Callable before or after
+ * sparsh_setup, needs no device.  A changed length frees the basis; the next GMRES solve reallocates it.
+ * sparsh_gmres_info: the restart length and the device bytes now held for the basis (restart + 1 vectors of level 0 and their
+ * per-workgroup partial sums): 0 until the first GMRES solve of the handle, after sparsh_setup and after a changed restart length.
+ * Any pointer may be NULL. */
+int sparsh_set_gmres(sparsh_handle h, int restart);
+int sparsh_gmres_info(sparsh_handle h, int *restart, long *basis_bytes);
 
 /* ---- multicolour SOR smoother ----
  * sparsh_set_smoother: kind SPARSH_SMOOTH_JACOBI (default) or SPARSH_SMOOTH_SOR; sweeps per leg (0: the default -- 6 for SOR,

@@ -23,7 +23,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsparsh_amg.so")
 
 SPARSH_AMG, SPARSH_CG, SPARSH_PCG, SPARSH_BICG, SPARSH_PBICG = 0, 1, 2, 3, 4
-METHODS = {"amg": SPARSH_AMG, "cg": SPARSH_CG, "pcg": SPARSH_PCG, "bicg": SPARSH_BICG, "pbicg": SPARSH_PBICG}
+SPARSH_GMRES, SPARSH_PGMRES = 5, 6
+METHODS = {"amg": SPARSH_AMG, "cg": SPARSH_CG, "pcg": SPARSH_PCG, "bicg": SPARSH_BICG, "pbicg": SPARSH_PBICG,
+           "gmres": SPARSH_GMRES, "pgmres": SPARSH_PGMRES}
 SPARSH_SMOOTH_JACOBI, SPARSH_SMOOTH_SOR = 0, 1
 SPARSH_SOR_FORWARD, SPARSH_SOR_SYMMETRIC = 0, 1
 SMOOTHERS = {"jacobi": SPARSH_SMOOTH_JACOBI, "sor": SPARSH_SMOOTH_SOR}
@@ -192,6 +194,9 @@ def _load():
         "sparsh_set_sor_path": (C.c_int, [H, C.c_int]),
         "sparsh_level_sor_layout": (C.c_int, [H, C.c_int, c_int_p, c_int_p, C.POINTER(C.c_long)]),
         "sparsh_profile_read": (C.c_int, [H, c_dbl_p]),
+        "sparsh_set_gmres": (C.c_int, [H, C.c_int]),
+        "sparsh_gmres_info": (C.c_int, [H, c_int_p, C.POINTER(C.c_long)]),
+        "sparsh_op_precond": (C.c_int, [H, c_dbl_p, c_dbl_p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here = header/library mismatch: fail loudly
@@ -476,6 +481,18 @@ class sp_matrix_mg:
         o = SOR_ORDERS[order] if isinstance(order, str) else int(order)
         _check(lib.sparsh_set_smoother(self._h, k, int(sweeps), o))
         return self
+
+    # -- restarted GMRES -----------------------------------------------------------------------
+    def set_gmres(self, restart=0):
+        """Restart length of "gmres" / "pgmres": 1..64, 0 = the default of 30.  A changed length frees the basis."""
+        _check(lib.sparsh_set_gmres(self._h, int(restart)))
+        return self
+
+    def gmres_info(self):
+        """dict(restart, basis_bytes): basis_bytes = device bytes now held for the Krylov basis (0 until the first GMRES solve)."""
+        m, nbytes = C.c_int(), C.c_long()
+        _check(lib.sparsh_gmres_info(self._h, C.byref(m), C.byref(nbytes)))
+        return dict(restart=m.value, basis_bytes=nbytes.value)
 
     def level_colors(self, level):
         """(ncolors, rows per colour, colour of every row) of the SOR colouring of a level; colours are numbered from 1."""
@@ -808,7 +825,8 @@ class sp_matrix_mg:
 
     def bench_op(self, op, level=0, reps=20):
         ops = {"spmv": 0, "jacobi": 1, "residual": 2, "restrict": 3, "prolong": 4, "coarse": 5, "dot": 6, "axpby": 7, "copy_int": 8,
-               "jacobi_pingpong": 9, "jacobi_pingpong_resident": 10, "jacobi_double": 11, "sor": 12}
+               "jacobi_pingpong": 9, "jacobi_pingpong_resident": 10, "jacobi_double": 11, "sor": 12,
+               "gmres_orth": 13, "gmres_orth_unfused": 14}
         sec = C.c_double()
         _check(lib.sparsh_bench_op(self._h, ops[op] if isinstance(op, str) else op, level, reps, C.byref(sec)))
         return sec.value
@@ -897,6 +915,13 @@ class sp_matrix_mg:
         _check(lib.sparsh_op_precond_f32(self._h, _dp(r), _dp(z)))
         return z
 
+    def op_precond(self, r):
+        """z = M r as "pbicg" / "pgmres" apply it: the V-cycle of the current smoother from a zero guess, or the fp32 cycle."""
+        r = np.ascontiguousarray(r, dtype=np.float64)
+        z = np.zeros_like(r)
+        _check(lib.sparsh_op_precond(self._h, _dp(r), _dp(z)))
+        return z
+
     def op_dot(self, x, y):
         x = np.ascontiguousarray(x, dtype=np.float64)
         y = np.ascontiguousarray(y, dtype=np.float64)
@@ -937,6 +962,8 @@ Solver_CG_1 = Solver_CG_2 = _entry("cg")
 Solver_PCG_1 = Solver_PCG_2 = Solver_PCG_3 = Solver_PCG_4 = _entry("pcg")
 Solver_BiCG_1 = _entry("bicg")
 Solver_PBiCG_1 = Solver_PBiCG_2 = Solver_PBiCG_3 = Solver_PBiCG_4 = _entry("pbicg")
+Solver_GMRES_1 = _entry("gmres")
+Solver_PGMRES_1 = _entry("pgmres")
 
 
 def readcoo(matrixfile: str, rhsfile: str):

@@ -84,6 +84,12 @@ struct DBuf {
     if ((h) && (h)->eng && (method) == SPARSH_PCG && (h)->eng->sor_on() && (h)->eng->sor_order() != SPARSH_SOR_SYMMETRIC) \
     return fail(SPARSH_EINVAL, "SPARSH_PCG needs a symmetric preconditioner: the SOR smoother must use SPARSH_SOR_SYMMETRIC")
 
+// likewise: GMRES on a handle that a multi-GPU transport has been installed on
+#define REQUIRE_GMRES_FITS(h, method)                                                                                              \
+    if ((h) && (h)->eng && ((method) == SPARSH_GMRES || (method) == SPARSH_PGMRES) &&                                              \
+        ((h)->eng->distributed() || ((h)->eng->comm() && (h)->eng->comm()->size > 1)))                                             \
+    return fail(SPARSH_EINVAL, "GMRES is not available on a partitioned (multi-GPU) handle: its j + 2 sums per step need a wider all-reduce")
+
 #define REQUIRE_HOST(h)                                               \
     if (!(h) || !(h)->eng) return fail(SPARSH_EINVAL, "null handle"); \
     if (!(h)->eng->host_ready()) return fail(SPARSH_ESTATE, "sparsh_setup / sparsh_setup_host has not been called (or failed)")
@@ -770,6 +776,7 @@ int sparsh_vcycle_dev(sparsh_handle h, const double *b_dev, double *x_dev, int i
 int sparsh_solve(sparsh_handle h, int method, const double *b, double *x, double *hist, int hist_cap, int *iters)
 {
     REQUIRE_SMOOTHER_FITS(h, method);
+    REQUIRE_GMRES_FITS(h, method);
     REQUIRE_READY(h);
     Engine &E = *h->eng;
     const size_t n = (size_t)E.local_n0();  // multi-GPU: this rank's block of level 0
@@ -785,6 +792,7 @@ int sparsh_solve_dev(sparsh_handle h, int method, const double *b_dev, double *x
                      int *iters, double *seconds)
 {
     REQUIRE_SMOOTHER_FITS(h, method);
+    REQUIRE_GMRES_FITS(h, method);
     REQUIRE_READY(h);
     int rc = h->eng->solve_dev(method, b_dev, x_dev, max_iters, hist, hist_cap, iters, seconds);
     if (rc != SPARSH_OK) return fail(rc, h->eng->error);
@@ -1270,6 +1278,33 @@ int sparsh_op_precond_f32(sparsh_handle h, const double *r, double *z)
     return done(E, dz.get(z));
 }
 
+int sparsh_op_precond(sparsh_handle h, const double *r, double *z)
+{
+    REQUIRE_READY(h);
+    REQUIRE_SINGLE(h);
+    Engine &E = *h->eng;
+    const size_t n = (size_t)E.level(0).n;
+    DBuf dr(E, n, r), dz(E, n);
+    if (!dr.p || !dz.p) return fail(SPARSH_ENODEV, E.error);
+    if (int rc = E.op_precond(dr.p, dz.p); rc != SPARSH_OK) return fail(rc, E.error);
+    return done(E, dz.get(z));
+}
+
+int sparsh_set_gmres(sparsh_handle h, int restart)
+{
+    if (!h || !h->eng) return fail(SPARSH_EINVAL, "null handle");
+    if (int rc = h->eng->set_gmres(restart); rc != SPARSH_OK) return fail(rc, h->eng->error);
+    return SPARSH_OK;
+}
+
+int sparsh_gmres_info(sparsh_handle h, int *restart, long *basis_bytes)
+{
+    if (!h || !h->eng) return fail(SPARSH_EINVAL, "null handle");
+    if (restart) *restart = h->eng->gmres_restart();
+    if (basis_bytes) *basis_bytes = (long)h->eng->gmres_basis_bytes();
+    return SPARSH_OK;
+}
+
 int sparsh_op_dot(sparsh_handle h, int n, const double *x, const double *y, double *out)
 {
     REQUIRE_READY(h);
@@ -1363,10 +1398,16 @@ int sparsh_bench_op(sparsh_handle h, int op, int level, int reps, double *avg_se
             ++flip2;
             launch_box2(L.A, xa, L.r, xb, E.params().omega, L.fine, st);
         } break;
+        case 13: E.gmres_bench_step(true); break;
+        case 14: E.gmres_bench_step(false); break;
         default: break;
         }
     };
-    if (op < 0 || op > 12) return fail(SPARSH_EINVAL, "unknown op");
+    if (op < 0 || op > 14) return fail(SPARSH_EINVAL, "unknown op");
+    if (op == 13 || op == 14) {
+        if (level != 0 || E.distributed()) return fail(SPARSH_EINVAL, "the GMRES orthogonalisation step runs on level 0 of a single-GPU handle");
+        if (int rc = E.gmres_bench_prepare(); rc != SPARSH_OK) return fail(rc, E.error);
+    }
     if (op == 12 && (E.distributed() || !E.build_sor_level(level))) return fail(SPARSH_ESTATE, "no SOR layout on this handle");
     if (op == 11 && (E.distributed() || !box2_applies(L.A, E.kernel_cfg()))) return fail(SPARSH_ESTATE, "the level does not run double sweeps (sparsh_level_double_sweep)");
     for (int i = 0; i < 3; ++i) run();

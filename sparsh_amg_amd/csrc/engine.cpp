@@ -1168,6 +1168,8 @@ int Engine::setup(const sparsh_params &p)
     if (!st_ && !check(hipStreamCreateWithFlags(&st_, hipStreamNonBlocking), "hipStreamCreate")) return SPARSH_ENODEV;
     for (void *q : allocs_) (void)hipFree(q);  // a second setup replaces the resident hierarchy
     allocs_.clear();
+    gm_basis_ = gm_part_ = gm_state_ = nullptr;  // (freed with the rest: the next GMRES solve reallocates the basis)
+    gm_bytes_ = 0;
     sor_.clear();
     coarse_.release();
     if (!comm_) comm_ = make_self_comm();
@@ -2502,6 +2504,197 @@ int Engine::bicg(const double *b, double *x, int max_iters, double *hist, int hi
     return fault_ != SPARSH_OK ? fault_ : rc;
 }
 
+// z = M r, the preconditioner of SPARSH_PBICG / SPARSH_PGMRES: one V-cycle of the current smoother from a zero guess, or the fp32 cycle.
+int Engine::op_precond(const double *r, double *z)
+{
+    if (int rc = sor_prepare(); rc != SPARSH_OK) return rc;
+    int nb = 0;
+    if (f32_ready_) {
+        vcycle_f32(r, z, part0_, &nb);
+    } else {
+        vcycle(r, true, nullptr, nullptr);
+        launch_copy(lev_[0].n, lev_[0].x, z, st_);
+    }
+    return fault_;
+}
+
+// ---- restarted GMRES, right-preconditioned
+int Engine::set_gmres(int restart)
+{
+    if (restart < 0 || restart > kGmresMaxRestart) {
+        error = "restart must be in 1.." + std::to_string(kGmresMaxRestart) + " (0: the default of " + std::to_string(kGmresDefaultRestart) + ")";
+        return SPARSH_EINVAL;
+    }
+    const int m = restart == 0 ? kGmresDefaultRestart : restart;
+    if (m != gm_restart_) gmres_release();
+    gm_restart_ = m;
+    return SPARSH_OK;
+}
+
+void Engine::gmres_release()
+{
+    if (gm_basis_ && st_) (void)hipStreamSynchronize(st_);
+    dfree(gm_basis_);
+    dfree(gm_part_);
+    dfree(gm_state_);
+    gm_basis_ = gm_part_ = gm_state_ = nullptr;
+    gm_bytes_ = 0;
+}
+
+int Engine::gmres_reserve()
+{
+    if (gm_basis_) return SPARSH_OK;
+    const int n = lev_[0].n, m = gm_restart_;
+    gm_stride_ = ((long)n + 1) & ~1L;  // 16-byte aligned vectors
+    const size_t basis = (size_t)(m + 1) * (size_t)gm_stride_ * 8;
+    const size_t part = (size_t)(m + 1) * (size_t)gs_grid(n) * 8;  // m sums against the basis + w.w, gs_grid(n) workgroups each
+    gm_basis_ = static_cast<double *>(dalloc(basis));
+    gm_part_ = static_cast<double *>(dalloc(part));
+    gm_state_ = static_cast<double *>(dalloc((size_t)kGmresStateDoubles * 8));
+    if (!gm_basis_ || !gm_part_ || !gm_state_) {
+        gmres_release();
+        error = "GMRES basis of " + std::to_string(m + 1) + " vectors (" + std::to_string(basis >> 20) + " MiB) does not fit the device: " + error;
+        return SPARSH_ENODEV;
+    }
+    if (!check(hipMemsetAsync(gm_state_, 0, (size_t)kGmresStateDoubles * 8, st_), "hipMemsetAsync")) return SPARSH_ENODEV;
+    gm_bytes_ = basis + part;
+    double *q = gm_state_;
+    gm_.hcol = q, q += kGmresMaxRestart + 2;
+    gm_.ccol = q, q += kGmresMaxRestart + 2;
+    gm_.R = q, q += kGmresMaxRestart * kGmresMaxRestart;
+    gm_.cs = q, q += kGmresMaxRestart;
+    gm_.sn = q, q += kGmresMaxRestart;
+    gm_.g = q, q += kGmresMaxRestart + 1;
+    gm_.ny = q, q += kGmresMaxRestart;
+    gm_.hnext = q;
+    return SPARSH_OK;
+}
+
+// Classical Gram-Schmidt twice on w = v_{j+1} against v_0..v_j: V^T w, w -= V h and V^T w_new in one pass, w -= V c and ||w||^2 in
+// one pass; then the one-workgroup kernel that rotates the column, and the normalisation as a launch of its own.
+void Engine::gmres_orthogonalise(int j, int slot)
+{
+    const int n = lev_[0].n, nv = j + 1, g = gs_grid(n), m = gm_restart_;
+    double *w = gm_vec(j + 1), *ww = gm_part_ + (size_t)m * g;
+    launch_gs_dot(n, gm_stride_, gm_basis_, nv, w, gm_part_, nullptr, st_);
+    launch_gs_finalize(gm_part_, g, nv, gm_.hcol, st_);
+    launch_gs_update(n, gm_stride_, gm_basis_, nv, gm_.hcol, w, w, gm_part_, nullptr, st_);
+    launch_gs_finalize(gm_part_, g, nv, gm_.ccol, st_);
+    launch_gs_update(n, gm_stride_, gm_basis_, nv, gm_.ccol, w, w, nullptr, ww, st_);
+    launch_gmres_step(j, ww, g, gm_, scal_ + S_RES, hist_dev_, slot, st_);
+    launch_gs_scale(n, w, gm_.hnext, st_);
+}
+
+int Engine::gmres(const double *b, double *x, int max_iters, double *hist, int hist_cap, int *iters, bool precond)
+{
+    if (dist_) {
+        error = "GMRES is not available on a partitioned (multi-GPU) handle";
+        return SPARSH_EINVAL;
+    }
+    if (precond)
+        if (int rc = sor_prepare(); rc != SPARSH_OK) return rc;
+    if (int rc = gmres_reserve(); rc != SPARSH_OK) return rc;
+    const int n = lev_[0].n, m = gm_restart_;
+    const int check_every = std::max(1, prm_.check_every);
+    double *u = work_[0], *z32 = work_[4];
+    int nb = 0, it = 0, rc = SPARSH_OK;
+    // z = M v (nullptr: the identity); the fp64 cycle leaves z in lev_[0].x, which belongs to the cycle: consumed by the next launch
+    auto apply_M = [&](const double *v) -> const double * {
+        if (!precond) return v;
+        if (f32_ready_) {
+            vcycle_f32(v, z32, part0_, &nb);
+            return z32;
+        }
+        vcycle(v, true, nullptr, nullptr);
+        return lev_[0].x;
+    };
+    for (;;) {  // one restart cycle
+        if (fault_ != SPARSH_OK) break;
+        op_residual(0, b, x, gm_vec(0));  // true residual
+        launch_dot(n, gm_vec(0), gm_vec(0), part0_, &nb, st_);
+        finalize(FIN_SQRT, part0_, nullptr, nb, S_RES, nullptr, 0);
+        const double beta = read_scalar(S_RES);
+        if (!(beta == beta)) {
+            rc = SPARSH_ENUMERIC;
+            break;
+        }
+        if (beta <= prm_.tol) break;
+        if (it >= max_iters) {
+            rc = SPARSH_ENOCONV;
+            break;
+        }
+        launch_gs_scale(n, gm_vec(0), scal_ + S_RES, st_);  // v_0 = r / beta
+        int steps = 0;
+        for (int j = 0; j < m && it < max_iters; ++j) {
+            op_spmv(0, apply_M(gm_vec(j)), gm_vec(j + 1));  // w = A M v_j
+            const int slot = std::min(it, hist_cap_dev_ - 1);
+            gmres_orthogonalise(j, slot);
+            ++it;
+            ++steps;
+            if (it % check_every == 0 || it >= max_iters) {
+                const double res = read_hist(slot);
+                if (prm_.print_solve) std::printf("%d\t%g\n", it, res);
+                if (!(res == res)) {
+                    rc = SPARSH_ENUMERIC;
+                    break;
+                }
+                if (res <= prm_.tol) break;
+            }
+            if (fault_ != SPARSH_OK) break;
+        }
+        if (rc != SPARSH_OK || fault_ != SPARSH_OK) break;
+        // x += M (V y), y = R^{-1} g over the steps taken
+        launch_gmres_solve(steps, gm_, st_);
+        launch_gs_update(n, gm_stride_, gm_basis_, steps, gm_.ny, nullptr, u, nullptr, nullptr, st_);  // u = 0 - V (-y)
+        launch_axpby(n, 1.0, apply_M(u), 1.0, x, st_);
+    }
+    HIPCHK(hipStreamSynchronize(st_));
+    if (hist) {
+        const int cnt = std::min(std::min(it, hist_cap), hist_cap_dev_);
+        if (cnt > 0) HIPCHK(hipMemcpy(hist, hist_dev_, (size_t)cnt * 8, hipMemcpyDeviceToHost));
+    }
+    if (iters) *iters = it;
+    return fault_ != SPARSH_OK ? fault_ : rc;
+}
+
+int Engine::gmres_bench_prepare()
+{
+    if (dist_) return SPARSH_EINVAL;
+    if (int rc = gmres_reserve(); rc != SPARSH_OK) return rc;
+    const int n = lev_[0].n, m = gm_restart_;
+    std::vector<double> pat((size_t)n + m + 1);
+    const double scale = 1.0 / (6.0 * std::sqrt((double)n));
+    for (size_t i = 0; i < pat.size(); ++i) pat[i] = (double)((long)((i * 7919) % 13) - 6) * scale;
+    for (int k = 0; k <= m; ++k)
+        if (!check(hipMemcpy(gm_vec(k), pat.data() + k, (size_t)n * 8, hipMemcpyHostToDevice), "hipMemcpy")) return SPARSH_ENODEV;
+    if (!check(hipMemcpy(work_[1], pat.data() + m + 1, (size_t)n * 8, hipMemcpyHostToDevice), "hipMemcpy")) return SPARSH_ENODEV;
+    return SPARSH_OK;
+}
+
+void Engine::gmres_bench_step(bool fused)
+{
+    const int n = lev_[0].n, j = gm_restart_ - 1, nv = j + 1;  // the last step of a cycle
+    double *w = gm_vec(j + 1);
+    launch_copy(n, work_[1], w, st_);  // (stands for the SpMV's store of w; keeps the values bounded over repetitions)
+    if (fused) {
+        gmres_orthogonalise(j, hist_cap_dev_ - 1);
+        return;
+    }
+    // what the fused kernels replace: a launch_dot + reduction per coefficient and an axpby per basis vector, twice, then the norm
+    // and the scaling (coefficients through the host would add a read-back each; a fixed one stands in)
+    int nb = 0;
+    for (int pass = 0; pass < 2; ++pass) {
+        for (int k = 0; k < nv; ++k) {
+            launch_dot(n, gm_vec(k), w, part0_, &nb, st_);
+            finalize(FIN_STORE, part0_, nullptr, nb, S_TMP, nullptr, 0);
+        }
+        for (int k = 0; k < nv; ++k) launch_axpby(n, -1e-3, gm_vec(k), 1.0, w, st_);
+    }
+    launch_dot(n, w, w, part0_, &nb, st_);
+    finalize(FIN_STORE, part0_, nullptr, nb, S_TMP, nullptr, 0);
+    launch_axpby(n, 0.0, gm_vec(0), 0.5, w, st_);
+}
+
 void Engine::profile_begin()
 {
     if (prof.ev.empty()) {
@@ -2553,6 +2746,8 @@ int Engine::solve_dev(int method, const double *b, double *x, int max_iters, dou
     case SPARSH_PCG: rc = pcg(b, x, max_iters, hist, hist_cap, iters, true); break;
     case SPARSH_BICG: rc = bicg(b, x, max_iters, hist, hist_cap, iters, false); break;
     case SPARSH_PBICG: rc = bicg(b, x, max_iters, hist, hist_cap, iters, true); break;
+    case SPARSH_GMRES: rc = gmres(b, x, max_iters, hist, hist_cap, iters, false); break;
+    case SPARSH_PGMRES: rc = gmres(b, x, max_iters, hist, hist_cap, iters, true); break;
     default: error = "unknown method"; return SPARSH_EINVAL;
     }
     if (seconds) {

@@ -256,6 +256,17 @@ public:
     void op_coarse(const double *b, double *x);
     // z = V32(r): one application of the opt-in fp32 preconditioner (fp64 in/out); needs precond_fp32
     bool op_precond_f32(const double *r, double *z);
+    // z = M r as the Krylov loops apply it: the V-cycle of the current smoother from a zero guess, or the fp32 cycle; SPARSH_* code
+    int op_precond(const double *r, double *z);
+    // ---- restarted GMRES: restart length (0 = kGmresDefaultRestart); a changed length frees the basis
+    static constexpr int kGmresDefaultRestart = 30;
+    int set_gmres(int restart);
+    int gmres_restart() const { return gm_restart_; }
+    size_t gmres_basis_bytes() const { return gm_bytes_; }  // basis + its partial sums; 0 until the first GMRES solve
+    // bench: one orthogonalisation step of w = level-0 work vector against restart - 1 basis vectors (fixed pattern), through the
+    // fused kernels (true) or through launch_dot / launch_axpby pairs with a read-back of each coefficient replaced by a fixed one (false)
+    int gmres_bench_prepare();
+    void gmres_bench_step(bool fused);
     double op_dot(int n, const double *x, const double *y);
 
     // device memory helpers
@@ -322,6 +333,17 @@ private:
     void drop_graph();
     int pcg(const double *b, double *x, int max_iters, double *hist, int hist_cap, int *iters, bool precond);
     int bicg(const double *b, double *x, int max_iters, double *hist, int hist_cap, int *iters, bool precond);
+    int gmres(const double *b, double *x, int max_iters, double *hist, int hist_cap, int *iters, bool precond);
+    int gmres_reserve();   // basis, partial sums and device state of the current restart length (no-op once held)
+    void gmres_release();
+    // w = v_{j+1} (holding A M v_j) orthogonalised against v_0..v_j twice, column j rotated, hist_dev_[slot] = |g_{j+1}|, v_{j+1} normalised
+    void gmres_orthogonalise(int j, int slot);
+    double *gm_vec(int k) const { return gm_basis_ + (size_t)k * gm_stride_; }
+    int gm_restart_ = kGmresDefaultRestart;
+    double *gm_basis_ = nullptr, *gm_part_ = nullptr, *gm_state_ = nullptr;
+    GmresState gm_;
+    long gm_stride_ = 0;
+    size_t gm_bytes_ = 0;
 
     std::unique_ptr<Comm> comm_;
     std::vector<Partition> parts_;  // row partition of every level

@@ -344,4 +344,37 @@ void launch_bicg_xr(int n, const double *scal, const double *p1, const double *s
 // BiCGStab: p = r + beta*(p - omega1*Ap)
 void launch_bicg_p(int n, const double *scal, const double *r, const double *Ap, double *p, hipStream_t st);
 
+// ---- restarted GMRES (krylov_kernels.hip): block Gram-Schmidt against the basis v_k = V + k * stride and the device-resident
+// small problem.  Partial sums are per workgroup, gs_grid(n) of them per sum: sum k at partial[k * gs_grid(n) + workgroup].
+constexpr int kGmresMaxRestart = 64;  // restart lengths 1..64
+constexpr int kGsMaxK = 16;           // basis vectors one launch orthogonalises against (partial sums a thread keeps in registers)
+int gs_grid(int n);
+// partial[k] <- v_k . w for k < nv; ww_partial (nullptr: not wanted) <- w . w.  nv > kGsMaxK: one launch per chunk.
+void launch_gs_dot(int n, long stride, const double *V, int nv, const double *w, double *partial, double *ww_partial, hipStream_t st);
+// w_out = w_in - sum_k h[k] v_k, k ascending, h in device memory (w_in == nullptr: from zero; w_in may be w_out);
+// partial (nullptr: not wanted)[k] <- v_k . w_out, ww_partial (nullptr: not wanted) <- w_out . w_out.
+// nv > kGsMaxK: update-only launches per chunk, then launch_gs_dot -- the same values.
+void launch_gs_update(int n, long stride, const double *V, int nv, const double *h, const double *w_in, double *w_out, double *partial,
+                      double *ww_partial, hipStream_t st);
+// out[k] = partial[k * nblk .. + nblk) added in a fixed order, one workgroup per k < rows
+void launch_gs_finalize(const double *partial, int nblk, int rows, double *out, hipStream_t st);
+// v = v / *d ; v = 0 when *d is not > 0
+void launch_gs_scale(int n, double *v, const double *d, hipStream_t st);
+// device-resident state of one restart cycle
+struct GmresState {
+    double *hcol = nullptr, *ccol = nullptr;  // V^T w of the first / second Gram-Schmidt pass (kGmresMaxRestart + 2 each)
+    double *R = nullptr;                      // rotated Hessenberg columns, column j at R + j * kGmresMaxRestart
+    double *cs = nullptr, *sn = nullptr;      // Givens rotations
+    double *g = nullptr;                      // rotated right-hand side (kGmresMaxRestart + 1)
+    double *ny = nullptr;                     // -y of the last launch_gmres_solve
+    double *hnext = nullptr;                  // h_{j+1} of the last step
+};
+constexpr int kGmresStateDoubles = 2 * (kGmresMaxRestart + 2) + kGmresMaxRestart * kGmresMaxRestart + 4 * kGmresMaxRestart + 2;
+// end of inner iteration j: column h = hcol + ccol, h_{j+1} = sqrt(sum of ww_partial[0, nblk)), rotations, hist[slot] = |g_{j+1}|;
+// j == 0 takes g_0 from *beta
+void launch_gmres_step(int j, const double *ww_partial, int nblk, const GmresState &s, const double *beta, double *hist, int slot,
+                       hipStream_t st);
+// ny = -R^{-1} g over the first k columns (zero pivot: that y is 0)
+void launch_gmres_solve(int k, const GmresState &s, hipStream_t st);
+
 }  // namespace sparsh

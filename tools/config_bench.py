@@ -6,7 +6,11 @@ tests/test_gpu_configs.py; this prints their rates for DESIGN.md / profiles/):
   CU   unstructured P1-FEM M + dt K stand-in, 525 825 rows: AMG-PBiCGStab iterations/s
 SPARSH_MTX=/path/to/file.mtx adds that MatrixMarket file as a further CU case.
 All rates are solve-phase only (hierarchy resident, vectors in HBM), full solves to 1e-8.
-Usage: python tools/config_bench.py > profiles/r02_configs.json"""
+Usage: python tools/config_bench.py > profiles/r02_configs.json
+Options: --methods=a,b replaces the method list of every case that runs (any of amg cg pcg bicg pbicg gmres pgmres);
+--restart=m sets the GMRES restart length; --reps=k solves per method (default 3, the fastest is reported); --no-orth-ab leaves the orthogonalisation A/B out (kernel traces).
+Cases that run only when named: GMRES_poisson3d_216 (pgmres against pcg, and the fused orthogonalisation step against the
+unfused one, alternated) and GMRES_convdiff_2000 (pgmres against pbicg on the 2000^2 convection-diffusion grid)."""
 import json
 import os
 import sys
@@ -19,8 +23,23 @@ import sparsh_amg_amd as sa
 from sparsh_amg_amd import problems
 
 
-def run(name, rp, ci, v, methods, rhs="ones", **params):
+OPTS = {"methods": None, "restart": 0, "reps": 3, "orth_ab": True}
+
+
+def convdiff(m):
+    """poisson2d(m) with first-order upwind convection from the south-west (tests/test_gpu_gmres.py)"""
+    rp, ci, v = problems.poisson2d(m)
+    rows = np.repeat(np.arange(len(rp) - 1), np.diff(rp))
+    v = v.copy()
+    v[(ci == rows - 1) | (ci == rows - m)] -= 0.6
+    v[ci == rows] += 1.2
+    return rp, ci, v
+
+
+def run(name, rp, ci, v, methods, rhs="ones", orth_ab=False, **params):
     n = len(rp) - 1
+    if OPTS["methods"]:
+        methods = OPTS["methods"]
     out = {"rows": n, "nnz": int(rp[-1])}
     A = sa.sp_matrix_mg(rp, ci, v)
     if os.environ.get("SPARSH_COARSE_BLOCK"):  # A/B of the block-tridiagonal coarse solver's block size
@@ -29,6 +48,7 @@ def run(name, rp, ci, v, methods, rhs="ones", **params):
         f = os.environ["SPARSH_COARSE_FORM"].split(",")
         A.set_coarse_form(f[0], int(f[1]) if len(f) > 1 else 0, int(f[2]) if len(f) > 2 else -1, int(f[3]) if len(f) > 3 else -1)
     A.setup(sa.default_params(print_setup=0, print_solve=0, **params))
+    A.set_gmres(OPTS["restart"])
     out["levels"] = [A.level_info(l)["nrow"] for l in range(A.nlevels)]
     out["level_kernels"] = [A.level_kernel(l) for l in range(A.nlevels - 1)]
     out["coarsest"] = A.coarse_info()
@@ -43,7 +63,7 @@ def run(name, rp, ci, v, methods, rhs="ones", **params):
     for m in methods:
         best = None
         err = None
-        for rep in range(3):
+        for rep in range(OPTS["reps"]):
             A.h2d(xd, np.zeros(n))
             try:
                 h, it, sec, rc = A.solve_dev(m, bd, xd)
@@ -60,6 +80,13 @@ def run(name, rp, ci, v, methods, rhs="ones", **params):
         unit = "V-cycles/s" if m == "amg" else "iterations/s"
         out[m] = {"count": it, "seconds": round(sec, 5), "rate": round(it / sec, 1), "unit": unit, "final_residual": res, "rc": rc}
         print(f"[{name}] {m}: {it} in {sec:.4f}s = {it / sec:.1f} {unit}, residual {res:.3e}", file=sys.stderr, flush=True)
+    if orth_ab and OPTS["orth_ab"]:  # one orthogonalisation step against `restart` basis vectors: fused kernels / dot + axpby pairs, alternated
+        out["gmres"] = A.gmres_info()
+        out["orth_step_us"] = {"fused": [], "unfused": []}
+        for rep in range(5):
+            out["orth_step_us"]["fused"].append(round(A.bench_op("gmres_orth", 0, 10) * 1e6, 1))
+            out["orth_step_us"]["unfused"].append(round(A.bench_op("gmres_orth_unfused", 0, 10) * 1e6, 1))
+        print(f"[{name}] orthogonalisation step (us): {out['orth_step_us']}", file=sys.stderr, flush=True)
     A.close()
     return out
 
@@ -67,6 +94,18 @@ def run(name, rp, ci, v, methods, rhs="ones", **params):
 def main():
     res = {}
     only = [a for a in sys.argv[1:] if not a.startswith("-")]  # substrings of case names to run (default: all)
+    for a in sys.argv[1:]:
+        if a.startswith("--methods="):
+            OPTS["methods"] = a.split("=", 1)[1].split(",")
+            unknown = [m for m in OPTS["methods"] if m not in sa.METHODS]
+            if unknown:
+                sys.exit(f"unknown method(s) {unknown}: one of {sorted(sa.METHODS)}")
+        elif a.startswith("--restart="):
+            OPTS["restart"] = int(a.split("=", 1)[1])
+        elif a.startswith("--reps="):
+            OPTS["reps"] = int(a.split("=", 1)[1])
+        elif a == "--no-orth-ab":
+            OPTS["orth_ab"] = False
 
     def want(name):
         return not only or any(o in name for o in only)
@@ -116,6 +155,10 @@ def main():
         res["BIG_fem_unstructured_2M"] = run("FEM 2M", *problems.fem_unstructured(2000000, seed=3), ["pcg"], rhs="random")
     if only and want("BIG_fem_unstructured_2M_reference_policy"):
         res["BIG_fem_unstructured_2M_reference_policy"] = run("FEM 2M ref", *problems.fem_unstructured(2000000, seed=3), ["pcg"], rhs="random", coarse_limit=1 << 30)
+    if only and want("GMRES_poisson3d_216"):
+        res["GMRES_poisson3d_216"] = run("GMRES 216^3", *problems.poisson3d(216), ["pcg", "pgmres"], orth_ab=True)
+    if only and want("GMRES_convdiff_2000"):
+        res["GMRES_convdiff_2000"] = run("GMRES convdiff 2000^2", *convdiff(2000), ["pbicg", "pgmres"])
     mtx = os.environ.get("SPARSH_MTX")  # e.g. SuiteSparse parabolic_fem.mtx when it is on the box
     if mtx and os.path.exists(mtx):
         if want("CU_"):
