@@ -414,7 +414,9 @@ int sparsh_op_axpby(sparsh_handle h, int n, double a, const double *x, double bc
  * 13 one GMRES orthogonalisation step on level 0 (`level` must be 0): the last step of a restart cycle, w against
  * restart basis vectors filled with a fixed pattern, through the fused kernels (two dot / update passes, reductions, rotation,
  * normalisation; plus one copy that stands for the store of w), 14 the same step through one launch_dot + reduction and one
- * launch_axpby per basis vector and pass, which is what the fused kernels replace. */
+ * launch_axpby per basis vector and pass, which is what the fused kernels replace (13 and 14 want SPARSH_BASIS_FP64 on the handle,
+ * SPARSH_ESTATE otherwise), 15 the fused step of 13 on a float basis: the same fill pattern rounded to float (`level` must be 0; wants
+ * SPARSH_BASIS_FP32 on the handle, SPARSH_ESTATE otherwise). */
 int sparsh_bench_op(sparsh_handle h, int op, int level, int reps, double *avg_seconds);
 
 /* ---- restarted GMRES (SPARSH_GMRES, SPARSH_PGMRES) ----
@@ -433,9 +435,24 @@ int sparsh_bench_op(sparsh_handle h, int op, int level, int reps, double *avg_se
  * sparsh_setup, needs no device.  A changed length frees the basis; the next GMRES solve reallocates it.
  * sparsh_gmres_info: the restart length and the device bytes now held for the basis (restart + 1 vectors of level 0 and their
  * per-workgroup partial sums): 0 until the first GMRES solve of the handle, after sparsh_setup and after a changed restart length.
- * Any pointer may be NULL. */
+ * Any pointer may be NULL.
+ * sparsh_set_gmres_basis: how the basis vectors are stored.  SPARSH_BASIS_FP64 (the default) is the path described above.
+ * SPARSH_BASIS_FP32 stores every v_k as the fp64 value rounded once to float (compressed-basis GMRES) and keeps all arithmetic in
+ * fp64: w lives in one fp64 vector of its own, the orthogonalisation, the Hessenberg column and V y use the vectors as stored, and
+ * the vector handed to M / A is the stored one widened back.  The basis then takes 0.53 of the memory (restart 30) and by byte count 0.55 - 0.6 of a step's traffic.  The
+ * history entry |g_{j+1}| becomes an estimate of the true residual (the rounded basis is orthonormal to about 6e-8 only); the solve
+ * still ends with SPARSH_OK only when the true residual b - A x of a cycle start is <= tol, and a cycle that ends on |g_{j+1}| <=
+ * tol while the true residual is larger is followed by another cycle.  Works with every preconditioner GMRES accepts.  Callable
+ * before or after sparsh_setup, needs no device; a changed precision frees the basis like a changed restart length; anything
+ * other than the two constants is SPARSH_EINVAL and changes nothing.  Under SPARSH_BASIS_FP32 sparsh_gmres_info counts
+ * (restart + 1) vectors of n rounded up to 4 floats, the partial sums and the fp64 vector of w (n rounded up to 4 doubles).
+ * sparsh_gmres_basis reads the precision back. */
+#define SPARSH_BASIS_FP64 0 /* default: basis vectors stored as double */
+#define SPARSH_BASIS_FP32 1 /* basis vectors stored as float, all arithmetic fp64 */
 int sparsh_set_gmres(sparsh_handle h, int restart);
 int sparsh_gmres_info(sparsh_handle h, int *restart, long *basis_bytes);
+int sparsh_set_gmres_basis(sparsh_handle h, int precision);
+int sparsh_gmres_basis(sparsh_handle h, int *precision);
 
 /* ---- multicolour SOR smoother ----
  * sparsh_set_smoother: kind SPARSH_SMOOTH_JACOBI (default) or SPARSH_SMOOTH_SOR; sweeps per leg (0: the default -- 6 for SOR,

@@ -28,6 +28,8 @@ METHODS = {"amg": SPARSH_AMG, "cg": SPARSH_CG, "pcg": SPARSH_PCG, "bicg": SPARSH
            "gmres": SPARSH_GMRES, "pgmres": SPARSH_PGMRES}
 SPARSH_SMOOTH_JACOBI, SPARSH_SMOOTH_SOR = 0, 1
 SPARSH_SOR_FORWARD, SPARSH_SOR_SYMMETRIC = 0, 1
+SPARSH_BASIS_FP64, SPARSH_BASIS_FP32 = 0, 1
+GMRES_BASES = {"fp64": SPARSH_BASIS_FP64, "fp32": SPARSH_BASIS_FP32}
 SMOOTHERS = {"jacobi": SPARSH_SMOOTH_JACOBI, "sor": SPARSH_SMOOTH_SOR}
 SOR_ORDERS = {"forward": SPARSH_SOR_FORWARD, "symmetric": SPARSH_SOR_SYMMETRIC}
 SPARSH_OK, SPARSH_EINVAL, SPARSH_ENODEV, SPARSH_ESTATE, SPARSH_ENUMERIC, SPARSH_ENOCONV, SPARSH_ECOMM = 0, -1, -2, -3, -4, -5, -6
@@ -196,6 +198,8 @@ def _load():
         "sparsh_profile_read": (C.c_int, [H, c_dbl_p]),
         "sparsh_set_gmres": (C.c_int, [H, C.c_int]),
         "sparsh_gmres_info": (C.c_int, [H, c_int_p, C.POINTER(C.c_long)]),
+        "sparsh_set_gmres_basis": (C.c_int, [H, C.c_int]),
+        "sparsh_gmres_basis": (C.c_int, [H, c_int_p]),
         "sparsh_op_precond": (C.c_int, [H, c_dbl_p, c_dbl_p]),
     }
     for name, (res, args) in sig.items():
@@ -483,16 +487,31 @@ class sp_matrix_mg:
         return self
 
     # -- restarted GMRES -----------------------------------------------------------------------
-    def set_gmres(self, restart=0):
-        """Restart length of "gmres" / "pgmres": 1..64, 0 = the default of 30.  A changed length frees the basis."""
+    def set_gmres(self, restart=0, basis=None):
+        """Restart length of "gmres" / "pgmres": 1..64, 0 = the default of 30.  basis: "fp64" (the default of a handle) or "fp32" =
+        basis vectors stored as float with all arithmetic in fp64 (sparsh_set_gmres_basis); None leaves the precision alone.
+        A changed length or precision frees the basis."""
         _check(lib.sparsh_set_gmres(self._h, int(restart)))
+        if basis is not None:
+            _check(lib.sparsh_set_gmres_basis(self._h, GMRES_BASES[basis] if isinstance(basis, str) else int(basis)))
         return self
 
+    def gmres_basis(self):
+        """ "fp64" or "fp32": how the Krylov basis is stored"""
+        p = C.c_int()
+        _check(lib.sparsh_gmres_basis(self._h, C.byref(p)))
+        return {v: k for k, v in GMRES_BASES.items()}[p.value]
+
     def gmres_info(self):
-        """dict(restart, basis_bytes): basis_bytes = device bytes now held for the Krylov basis (0 until the first GMRES solve)."""
+        """dict(restart, basis_bytes): basis_bytes = device bytes now held for the Krylov basis (0 until the first GMRES solve).
+        A handle whose basis is stored as float reports basis="fp32" as a third entry; the default fp64 basis adds none, so the
+        dict of a handle that never chose a precision is the one it has always been (gmres_basis() names either)."""
         m, nbytes = C.c_int(), C.c_long()
         _check(lib.sparsh_gmres_info(self._h, C.byref(m), C.byref(nbytes)))
-        return dict(restart=m.value, basis_bytes=nbytes.value)
+        info = dict(restart=m.value, basis_bytes=nbytes.value)
+        if self.gmres_basis() != "fp64":
+            info["basis"] = self.gmres_basis()
+        return info
 
     def level_colors(self, level):
         """(ncolors, rows per colour, colour of every row) of the SOR colouring of a level; colours are numbered from 1."""
@@ -826,7 +845,7 @@ class sp_matrix_mg:
     def bench_op(self, op, level=0, reps=20):
         ops = {"spmv": 0, "jacobi": 1, "residual": 2, "restrict": 3, "prolong": 4, "coarse": 5, "dot": 6, "axpby": 7, "copy_int": 8,
                "jacobi_pingpong": 9, "jacobi_pingpong_resident": 10, "jacobi_double": 11, "sor": 12,
-               "gmres_orth": 13, "gmres_orth_unfused": 14}
+               "gmres_orth": 13, "gmres_orth_unfused": 14, "gmres_orth_fp32_basis": 15}
         sec = C.c_double()
         _check(lib.sparsh_bench_op(self._h, ops[op] if isinstance(op, str) else op, level, reps, C.byref(sec)))
         return sec.value

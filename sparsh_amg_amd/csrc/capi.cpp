@@ -1305,6 +1305,20 @@ int sparsh_gmres_info(sparsh_handle h, int *restart, long *basis_bytes)
     return SPARSH_OK;
 }
 
+int sparsh_set_gmres_basis(sparsh_handle h, int precision)
+{
+    if (!h || !h->eng) return fail(SPARSH_EINVAL, "null handle");
+    if (int rc = h->eng->set_gmres_basis(precision); rc != SPARSH_OK) return fail(rc, h->eng->error);
+    return SPARSH_OK;
+}
+
+int sparsh_gmres_basis(sparsh_handle h, int *precision)
+{
+    if (!h || !h->eng) return fail(SPARSH_EINVAL, "null handle");
+    if (precision) *precision = h->eng->gmres_basis();
+    return SPARSH_OK;
+}
+
 int sparsh_op_dot(sparsh_handle h, int n, const double *x, const double *y, double *out)
 {
     REQUIRE_READY(h);
@@ -1400,12 +1414,15 @@ int sparsh_bench_op(sparsh_handle h, int op, int level, int reps, double *avg_se
         } break;
         case 13: E.gmres_bench_step(true); break;
         case 14: E.gmres_bench_step(false); break;
+        case 15: E.gmres_bench_step(true); break;  // (the handle's float basis)
         default: break;
         }
     };
-    if (op < 0 || op > 14) return fail(SPARSH_EINVAL, "unknown op");
-    if (op == 13 || op == 14) {
+    if (op < 0 || op > 15) return fail(SPARSH_EINVAL, "unknown op");
+    if (op == 13 || op == 14 || op == 15) {
         if (level != 0 || E.distributed()) return fail(SPARSH_EINVAL, "the GMRES orthogonalisation step runs on level 0 of a single-GPU handle");
+        if ((op == 15) != (E.gmres_basis() == SPARSH_BASIS_FP32))
+            return fail(SPARSH_ESTATE, "ops 13 and 14 run on a double basis, op 15 on a float basis (sparsh_set_gmres_basis)");
         if (int rc = E.gmres_bench_prepare(); rc != SPARSH_OK) return fail(rc, E.error);
     }
     if (op == 12 && (E.distributed() || !E.build_sor_level(level))) return fail(SPARSH_ESTATE, "no SOR layout on this handle");

@@ -1168,7 +1168,8 @@ int Engine::setup(const sparsh_params &p)
     if (!st_ && !check(hipStreamCreateWithFlags(&st_, hipStreamNonBlocking), "hipStreamCreate")) return SPARSH_ENODEV;
     for (void *q : allocs_) (void)hipFree(q);  // a second setup replaces the resident hierarchy
     allocs_.clear();
-    gm_basis_ = gm_part_ = gm_state_ = nullptr;  // (freed with the rest: the next GMRES solve reallocates the basis)
+    gm_basis_ = gm_part_ = gm_state_ = gm_w_ = nullptr;  // (freed with the rest: the next GMRES solve reallocates the basis)
+    gm_basisf_ = nullptr;
     gm_bytes_ = 0;
     sor_.clear();
     coarse_.release();
@@ -2531,33 +2532,59 @@ int Engine::set_gmres(int restart)
     return SPARSH_OK;
 }
 
+int Engine::set_gmres_basis(int precision)
+{
+    if (precision != SPARSH_BASIS_FP64 && precision != SPARSH_BASIS_FP32) {
+        error = "basis precision must be SPARSH_BASIS_FP64 (0) or SPARSH_BASIS_FP32 (1)";
+        return SPARSH_EINVAL;
+    }
+    if (precision != gm_prec_) gmres_release();
+    gm_prec_ = precision;
+    return SPARSH_OK;
+}
+
 void Engine::gmres_release()
 {
-    if (gm_basis_ && st_) (void)hipStreamSynchronize(st_);
+    if ((gm_basis_ || gm_basisf_) && st_) (void)hipStreamSynchronize(st_);
     dfree(gm_basis_);
+    dfree(gm_basisf_);
+    dfree(gm_w_);
     dfree(gm_part_);
     dfree(gm_state_);
-    gm_basis_ = gm_part_ = gm_state_ = nullptr;
+    gm_basis_ = gm_part_ = gm_state_ = gm_w_ = nullptr;
+    gm_basisf_ = nullptr;
     gm_bytes_ = 0;
 }
 
 int Engine::gmres_reserve()
 {
-    if (gm_basis_) return SPARSH_OK;
+    if (gm_basis_ || gm_basisf_) return SPARSH_OK;
     const int n = lev_[0].n, m = gm_restart_;
-    gm_stride_ = ((long)n + 1) & ~1L;  // 16-byte aligned vectors
-    const size_t basis = (size_t)(m + 1) * (size_t)gm_stride_ * 8;
+    const bool f32b = gm_prec_ == SPARSH_BASIS_FP32;
+    // 16-byte aligned vectors: n rounded up to 2 doubles or to 4 floats
+    gm_stride_ = f32b ? ((long)n + 3) & ~3L : ((long)n + 1) & ~1L;
+    const size_t basis = (size_t)(m + 1) * (size_t)gm_stride_ * (f32b ? 4 : 8);
+    const size_t wvec = f32b ? (size_t)gm_stride_ * 8 : 0;
     const size_t part = (size_t)(m + 1) * (size_t)gs_grid(n) * 8;  // m sums against the basis + w.w, gs_grid(n) workgroups each
-    gm_basis_ = static_cast<double *>(dalloc(basis));
+    if (f32b) {
+        gm_basisf_ = static_cast<float *>(dalloc(basis));
+        gm_w_ = static_cast<double *>(dalloc(wvec));
+    } else {
+        gm_basis_ = static_cast<double *>(dalloc(basis));
+    }
     gm_part_ = static_cast<double *>(dalloc(part));
     gm_state_ = static_cast<double *>(dalloc((size_t)kGmresStateDoubles * 8));
-    if (!gm_basis_ || !gm_part_ || !gm_state_) {
+    if (!(f32b ? gm_basisf_ && gm_w_ : gm_basis_ != nullptr) || !gm_part_ || !gm_state_) {
         gmres_release();
         error = "GMRES basis of " + std::to_string(m + 1) + " vectors (" + std::to_string(basis >> 20) + " MiB) does not fit the device: " + error;
         return SPARSH_ENODEV;
     }
     if (!check(hipMemsetAsync(gm_state_, 0, (size_t)kGmresStateDoubles * 8, st_), "hipMemsetAsync")) return SPARSH_ENODEV;
-    gm_bytes_ = basis + part;
+    if (f32b) {  // the float kernels load whole groups of 4 rows: zeros behind row n, which no kernel overwrites with anything else
+        if (!check(hipMemsetAsync(gm_basisf_, 0, basis, st_), "hipMemsetAsync")) return SPARSH_ENODEV;
+        if (!check(hipMemsetAsync(gm_w_, 0, wvec, st_), "hipMemsetAsync")) return SPARSH_ENODEV;
+    }
+    gm_bytes_ = basis + part + wvec;
     double *q = gm_state_;
     gm_.hcol = q, q += kGmresMaxRestart + 2;
     gm_.ccol = q, q += kGmresMaxRestart + 2;
@@ -2572,10 +2599,24 @@ int Engine::gmres_reserve()
 
 // Classical Gram-Schmidt twice on w = v_{j+1} against v_0..v_j: V^T w, w -= V h and V^T w_new in one pass, w -= V c and ||w||^2 in
 // one pass; then the one-workgroup kernel that rotates the column, and the normalisation as a launch of its own.
-void Engine::gmres_orthogonalise(int j, int slot)
+// Float basis: w is gm_w_, the sums run against the stored (rounded) vectors, and the normalisation writes the float v_{j+1} and its
+// widened copy `feed`, the input of the next step's M / A.
+void Engine::gmres_orthogonalise(int j, int slot, double *feed)
 {
     const int n = lev_[0].n, nv = j + 1, g = gs_grid(n), m = gm_restart_;
-    double *w = gm_vec(j + 1), *ww = gm_part_ + (size_t)m * g;
+    double *ww = gm_part_ + (size_t)m * g;
+    if (gm_prec_ == SPARSH_BASIS_FP32) {
+        double *w = gm_w_;
+        launch_gs_dot(n, gm_stride_, gm_basisf_, nv, w, gm_part_, nullptr, st_);
+        launch_gs_finalize(gm_part_, g, nv, gm_.hcol, st_);
+        launch_gs_update(n, gm_stride_, gm_basisf_, nv, gm_.hcol, w, w, gm_part_, nullptr, st_);
+        launch_gs_finalize(gm_part_, g, nv, gm_.ccol, st_);
+        launch_gs_update(n, gm_stride_, gm_basisf_, nv, gm_.ccol, w, w, nullptr, ww, st_);
+        launch_gmres_step(j, ww, g, gm_, scal_ + S_RES, hist_dev_, slot, st_);
+        launch_gs_scale(n, w, gm_vecf(j + 1), feed, gm_.hnext, st_);
+        return;
+    }
+    double *w = gm_vec(j + 1);
     launch_gs_dot(n, gm_stride_, gm_basis_, nv, w, gm_part_, nullptr, st_);
     launch_gs_finalize(gm_part_, g, nv, gm_.hcol, st_);
     launch_gs_update(n, gm_stride_, gm_basis_, nv, gm_.hcol, w, w, gm_part_, nullptr, st_);
@@ -2595,8 +2636,10 @@ int Engine::gmres(const double *b, double *x, int max_iters, double *hist, int h
         if (int rc = sor_prepare(); rc != SPARSH_OK) return rc;
     if (int rc = gmres_reserve(); rc != SPARSH_OK) return rc;
     const int n = lev_[0].n, m = gm_restart_;
+    const bool f32b = gm_prec_ == SPARSH_BASIS_FP32;
     const int check_every = std::max(1, prm_.check_every);
     double *u = work_[0], *z32 = work_[4];
+    double *feed = work_[2];  // float basis: v_j as stored, widened to double
     int nb = 0, it = 0, rc = SPARSH_OK;
     // z = M v (nullptr: the identity); the fp64 cycle leaves z in lev_[0].x, which belongs to the cycle: consumed by the next launch
     auto apply_M = [&](const double *v) -> const double * {
@@ -2608,10 +2651,13 @@ int Engine::gmres(const double *b, double *x, int max_iters, double *hist, int h
         vcycle(v, true, nullptr, nullptr);
         return lev_[0].x;
     };
+    // The only exit with SPARSH_OK is the true residual of a cycle start being <= tol.  |g_{j+1}| <= tol only ends the cycle, which
+    // matters under a float basis, where |g_{j+1}| is an estimate of the residual: the next cycle start decides.
     for (;;) {  // one restart cycle
         if (fault_ != SPARSH_OK) break;
-        op_residual(0, b, x, gm_vec(0));  // true residual
-        launch_dot(n, gm_vec(0), gm_vec(0), part0_, &nb, st_);
+        double *r = f32b ? gm_w_ : gm_vec(0);
+        op_residual(0, b, x, r);  // true residual
+        launch_dot(n, r, r, part0_, &nb, st_);
         finalize(FIN_SQRT, part0_, nullptr, nb, S_RES, nullptr, 0);
         const double beta = read_scalar(S_RES);
         if (!(beta == beta)) {
@@ -2623,12 +2669,14 @@ int Engine::gmres(const double *b, double *x, int max_iters, double *hist, int h
             rc = SPARSH_ENOCONV;
             break;
         }
-        launch_gs_scale(n, gm_vec(0), scal_ + S_RES, st_);  // v_0 = r / beta
+        // v_0 = r / beta
+        if (f32b) launch_gs_scale(n, r, gm_vecf(0), feed, scal_ + S_RES, st_);
+        else launch_gs_scale(n, r, scal_ + S_RES, st_);
         int steps = 0;
         for (int j = 0; j < m && it < max_iters; ++j) {
-            op_spmv(0, apply_M(gm_vec(j)), gm_vec(j + 1));  // w = A M v_j
+            op_spmv(0, apply_M(f32b ? feed : gm_vec(j)), f32b ? gm_w_ : gm_vec(j + 1));  // w = A M v_j
             const int slot = std::min(it, hist_cap_dev_ - 1);
-            gmres_orthogonalise(j, slot);
+            gmres_orthogonalise(j, slot, feed);
             ++it;
             ++steps;
             if (it % check_every == 0 || it >= max_iters) {
@@ -2643,9 +2691,10 @@ int Engine::gmres(const double *b, double *x, int max_iters, double *hist, int h
             if (fault_ != SPARSH_OK) break;
         }
         if (rc != SPARSH_OK || fault_ != SPARSH_OK) break;
-        // x += M (V y), y = R^{-1} g over the steps taken
+        // x += M (V y), y = R^{-1} g over the steps taken; u = 0 - V (-y)
         launch_gmres_solve(steps, gm_, st_);
-        launch_gs_update(n, gm_stride_, gm_basis_, steps, gm_.ny, nullptr, u, nullptr, nullptr, st_);  // u = 0 - V (-y)
+        if (f32b) launch_gs_update(n, gm_stride_, gm_basisf_, steps, gm_.ny, nullptr, u, nullptr, nullptr, st_);
+        else launch_gs_update(n, gm_stride_, gm_basis_, steps, gm_.ny, nullptr, u, nullptr, nullptr, st_);
         launch_axpby(n, 1.0, apply_M(u), 1.0, x, st_);
     }
     HIPCHK(hipStreamSynchronize(st_));
@@ -2661,12 +2710,21 @@ int Engine::gmres_bench_prepare()
 {
     if (dist_) return SPARSH_EINVAL;
     if (int rc = gmres_reserve(); rc != SPARSH_OK) return rc;
+    // gmres_reserve zeroes a new float basis on st_, which the copies below (null stream) are not ordered against
+    if (!check(hipStreamSynchronize(st_), "hipStreamSynchronize")) return SPARSH_ENODEV;
     const int n = lev_[0].n, m = gm_restart_;
     std::vector<double> pat((size_t)n + m + 1);
     const double scale = 1.0 / (6.0 * std::sqrt((double)n));
     for (size_t i = 0; i < pat.size(); ++i) pat[i] = (double)((long)((i * 7919) % 13) - 6) * scale;
-    for (int k = 0; k <= m; ++k)
-        if (!check(hipMemcpy(gm_vec(k), pat.data() + k, (size_t)n * 8, hipMemcpyHostToDevice), "hipMemcpy")) return SPARSH_ENODEV;
+    if (gm_prec_ == SPARSH_BASIS_FP32) {
+        std::vector<float> patf(pat.size());
+        for (size_t i = 0; i < pat.size(); ++i) patf[i] = (float)pat[i];
+        for (int k = 0; k <= m; ++k)
+            if (!check(hipMemcpy(gm_vecf(k), patf.data() + k, (size_t)n * 4, hipMemcpyHostToDevice), "hipMemcpy")) return SPARSH_ENODEV;
+    } else {
+        for (int k = 0; k <= m; ++k)
+            if (!check(hipMemcpy(gm_vec(k), pat.data() + k, (size_t)n * 8, hipMemcpyHostToDevice), "hipMemcpy")) return SPARSH_ENODEV;
+    }
     if (!check(hipMemcpy(work_[1], pat.data() + m + 1, (size_t)n * 8, hipMemcpyHostToDevice), "hipMemcpy")) return SPARSH_ENODEV;
     return SPARSH_OK;
 }
@@ -2674,10 +2732,10 @@ int Engine::gmres_bench_prepare()
 void Engine::gmres_bench_step(bool fused)
 {
     const int n = lev_[0].n, j = gm_restart_ - 1, nv = j + 1;  // the last step of a cycle
-    double *w = gm_vec(j + 1);
+    double *w = gm_prec_ == SPARSH_BASIS_FP32 ? gm_w_ : gm_vec(j + 1);
     launch_copy(n, work_[1], w, st_);  // (stands for the SpMV's store of w; keeps the values bounded over repetitions)
     if (fused) {
-        gmres_orthogonalise(j, hist_cap_dev_ - 1);
+        gmres_orthogonalise(j, hist_cap_dev_ - 1, work_[2]);
         return;
     }
     // what the fused kernels replace: a launch_dot + reduction per coefficient and an axpby per basis vector, twice, then the norm

@@ -262,9 +262,14 @@ public:
     static constexpr int kGmresDefaultRestart = 30;
     int set_gmres(int restart);
     int gmres_restart() const { return gm_restart_; }
-    size_t gmres_basis_bytes() const { return gm_bytes_; }  // basis + its partial sums; 0 until the first GMRES solve
+    // storage of the basis vectors (SPARSH_BASIS_FP64 / SPARSH_BASIS_FP32; arithmetic is fp64 either way); a changed one frees the basis
+    int set_gmres_basis(int precision);
+    int gmres_basis() const { return gm_prec_; }
+    // basis + its partial sums (+ the fp64 vector that holds w under a float basis); 0 until the first GMRES solve
+    size_t gmres_basis_bytes() const { return gm_bytes_; }
     // bench: one orthogonalisation step of w = level-0 work vector against restart - 1 basis vectors (fixed pattern), through the
-    // fused kernels (true) or through launch_dot / launch_axpby pairs with a read-back of each coefficient replaced by a fixed one (false)
+    // fused kernels (true) or through launch_dot / launch_axpby pairs with a read-back of each coefficient replaced by a fixed one (false,
+    // double basis only).  The basis is of the handle's precision; under a float basis the pattern is rounded to float.
     int gmres_bench_prepare();
     void gmres_bench_step(bool fused);
     double op_dot(int n, const double *x, const double *y);
@@ -337,10 +342,14 @@ private:
     int gmres_reserve();   // basis, partial sums and device state of the current restart length (no-op once held)
     void gmres_release();
     // w = v_{j+1} (holding A M v_j) orthogonalised against v_0..v_j twice, column j rotated, hist_dev_[slot] = |g_{j+1}|, v_{j+1} normalised
-    void gmres_orthogonalise(int j, int slot);
+    void gmres_orthogonalise(int j, int slot, double *feed);  // feed: written under a float basis only
     double *gm_vec(int k) const { return gm_basis_ + (size_t)k * gm_stride_; }
+    float *gm_vecf(int k) const { return gm_basisf_ + (size_t)k * gm_stride_; }
     int gm_restart_ = kGmresDefaultRestart;
+    int gm_prec_ = SPARSH_BASIS_FP64;
     double *gm_basis_ = nullptr, *gm_part_ = nullptr, *gm_state_ = nullptr;
+    float *gm_basisf_ = nullptr;  // the basis under SPARSH_BASIS_FP32 (gm_basis_ stays nullptr); stride a multiple of 4, zeros behind row n
+    double *gm_w_ = nullptr;      // ... and w of the current step, which a double basis keeps in the slot of v_{j+1}
     GmresState gm_;
     long gm_stride_ = 0;
     size_t gm_bytes_ = 0;

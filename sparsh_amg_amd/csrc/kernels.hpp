@@ -346,20 +346,28 @@ void launch_bicg_p(int n, const double *scal, const double *r, const double *Ap,
 
 // ---- restarted GMRES (krylov_kernels.hip): block Gram-Schmidt against the basis v_k = V + k * stride and the device-resident
 // small problem.  Partial sums are per workgroup, gs_grid(n) of them per sum: sum k at partial[k * gs_grid(n) + workgroup].
+// The basis is of double or of float (SPARSH_BASIS_FP32: stored values widened to double before use, every product and sum fp64).
+// A float basis wants stride % 4 == 0, 16-byte aligned vectors and zeros in [n, stride) of every vector: its loads are float2 / float4
+// and run to the end of the last group of rows.  w, w_in, w_out of the float overloads are 16-byte aligned and hold n doubles.
 constexpr int kGmresMaxRestart = 64;  // restart lengths 1..64
 constexpr int kGsMaxK = 16;           // basis vectors one launch orthogonalises against (partial sums a thread keeps in registers)
 int gs_grid(int n);
 // partial[k] <- v_k . w for k < nv; ww_partial (nullptr: not wanted) <- w . w.  nv > kGsMaxK: one launch per chunk.
 void launch_gs_dot(int n, long stride, const double *V, int nv, const double *w, double *partial, double *ww_partial, hipStream_t st);
+void launch_gs_dot(int n, long stride, const float *V, int nv, const double *w, double *partial, double *ww_partial, hipStream_t st);
 // w_out = w_in - sum_k h[k] v_k, k ascending, h in device memory (w_in == nullptr: from zero; w_in may be w_out);
 // partial (nullptr: not wanted)[k] <- v_k . w_out, ww_partial (nullptr: not wanted) <- w_out . w_out.
 // nv > kGsMaxK: update-only launches per chunk, then launch_gs_dot -- the same values.
 void launch_gs_update(int n, long stride, const double *V, int nv, const double *h, const double *w_in, double *w_out, double *partial,
                       double *ww_partial, hipStream_t st);
+void launch_gs_update(int n, long stride, const float *V, int nv, const double *h, const double *w_in, double *w_out, double *partial,
+                      double *ww_partial, hipStream_t st);
 // out[k] = partial[k * nblk .. + nblk) added in a fixed order, one workgroup per k < rows
 void launch_gs_finalize(const double *partial, int nblk, int rows, double *out, hipStream_t st);
 // v = v / *d ; v = 0 when *d is not > 0
 void launch_gs_scale(int n, double *v, const double *d, hipStream_t st);
+// float basis: v = (float)(w / *d), vd = that float widened back to double (n doubles); zeros when *d is not > 0
+void launch_gs_scale(int n, const double *w, float *v, double *vd, const double *d, hipStream_t st);
 // device-resident state of one restart cycle
 struct GmresState {
     double *hcol = nullptr, *ccol = nullptr;  // V^T w of the first / second Gram-Schmidt pass (kGmresMaxRestart + 2 each)

@@ -8,7 +8,9 @@ SPARSH_MTX=/path/to/file.mtx adds that MatrixMarket file as a further CU case.
 All rates are solve-phase only (hierarchy resident, vectors in HBM), full solves to 1e-8.
 Usage: python tools/config_bench.py > profiles/r02_configs.json
 Options: --methods=a,b replaces the method list of every case that runs (any of amg cg pcg bicg pbicg gmres pgmres);
---restart=m sets the GMRES restart length; --reps=k solves per method (default 3, the fastest is reported); --no-orth-ab leaves the orthogonalisation A/B out (kernel traces).
+--restart=m sets the GMRES restart length; --basis=fp64|fp32|both stores the GMRES basis as double (the default), as float, or
+runs gmres / pgmres and the fused orthogonalisation step under both, alternated in this process (results of the float basis under
+"<method>_fp32_basis" and orth_step_us["fused_fp32_basis"]); --reps=k solves per method (default 3, the fastest is reported); --no-orth-ab leaves the orthogonalisation A/B out (kernel traces).
 Cases that run only when named: GMRES_poisson3d_216 (pgmres against pcg, and the fused orthogonalisation step against the
 unfused one, alternated) and GMRES_convdiff_2000 (pgmres against pbicg on the 2000^2 convection-diffusion grid)."""
 import json
@@ -23,7 +25,7 @@ import sparsh_amg_amd as sa
 from sparsh_amg_amd import problems
 
 
-OPTS = {"methods": None, "restart": 0, "reps": 3, "orth_ab": True}
+OPTS = {"methods": None, "restart": 0, "reps": 3, "orth_ab": True, "basis": "fp64"}
 
 
 def convdiff(m):
@@ -48,7 +50,7 @@ def run(name, rp, ci, v, methods, rhs="ones", orth_ab=False, **params):
         f = os.environ["SPARSH_COARSE_FORM"].split(",")
         A.set_coarse_form(f[0], int(f[1]) if len(f) > 1 else 0, int(f[2]) if len(f) > 2 else -1, int(f[3]) if len(f) > 3 else -1)
     A.setup(sa.default_params(print_setup=0, print_solve=0, **params))
-    A.set_gmres(OPTS["restart"])
+    A.set_gmres(OPTS["restart"], basis=None if OPTS["basis"] == "both" else OPTS["basis"])
     out["levels"] = [A.level_info(l)["nrow"] for l in range(A.nlevels)]
     out["level_kernels"] = [A.level_kernel(l) for l in range(A.nlevels - 1)]
     out["coarsest"] = A.coarse_info()
@@ -60,32 +62,49 @@ def run(name, rp, ci, v, methods, rhs="ones", orth_ab=False, **params):
     b = np.ones(n) if rhs == "ones" else np.random.default_rng(4).standard_normal(n) * 1e-3
     bd, xd = A.dev_alloc(8 * n), A.dev_alloc(8 * n)
     A.h2d(bd, b)
+    bases = ["fp64", "fp32"] if OPTS["basis"] == "both" else [OPTS["basis"]]
     for m in methods:
-        best = None
+        variants = bases if m in ("gmres", "pgmres") else [None]  # the basis precision concerns GMRES alone
+        best = {bs: None for bs in variants}
         err = None
         for rep in range(OPTS["reps"]):
-            A.h2d(xd, np.zeros(n))
-            try:
-                h, it, sec, rc = A.solve_dev(m, bd, xd)
-            except sa.SparshError as e:  # e.g. BiCGStab breakdown (0/0), which the CPU oracle reproduces
-                err = str(e)
+            for bs in variants:  # alternated: both precisions see the same state of the machine
+                if bs is not None:
+                    A.set_gmres(OPTS["restart"], basis=bs)
+                A.h2d(xd, np.zeros(n))
+                try:
+                    h, it, sec, rc = A.solve_dev(m, bd, xd)
+                except sa.SparshError as e:  # e.g. BiCGStab breakdown (0/0), which the CPU oracle reproduces
+                    err = str(e)
+                    break
+                if best[bs] is None or sec < best[bs][1]:
+                    best[bs] = (it, sec, float(h[-1]), rc)
+            if err is not None:
                 break
-            if best is None or sec < best[1]:
-                best = (it, sec, float(h[-1]), rc)
         if err is not None:
             out[m] = {"error": err}
             print(f"[{name}] {m}: {err}", file=sys.stderr, flush=True)
             continue
-        it, sec, res, rc = best
-        unit = "V-cycles/s" if m == "amg" else "iterations/s"
-        out[m] = {"count": it, "seconds": round(sec, 5), "rate": round(it / sec, 1), "unit": unit, "final_residual": res, "rc": rc}
-        print(f"[{name}] {m}: {it} in {sec:.4f}s = {it / sec:.1f} {unit}, residual {res:.3e}", file=sys.stderr, flush=True)
-    if orth_ab and OPTS["orth_ab"]:  # one orthogonalisation step against `restart` basis vectors: fused kernels / dot + axpby pairs, alternated
-        out["gmres"] = A.gmres_info()
-        out["orth_step_us"] = {"fused": [], "unfused": []}
+        for bs in variants:
+            it, sec, res, rc = best[bs]
+            key = m + "_fp32_basis" if bs == "fp32" else m
+            unit = "V-cycles/s" if m == "amg" else "iterations/s"
+            out[key] = {"count": it, "seconds": round(sec, 5), "rate": round(it / sec, 1), "unit": unit, "final_residual": res, "rc": rc}
+            print(f"[{name}] {key}: {it} in {sec:.4f}s = {it / sec:.1f} {unit}, residual {res:.3e}", file=sys.stderr, flush=True)
+    if orth_ab and OPTS["orth_ab"]:
+        # one orthogonalisation step against `restart` basis vectors, alternated: fused kernels / dot + axpby pairs on the double
+        # basis, the fused kernels on the float basis (a change of precision reallocates and refills the basis, outside the timing)
+        out["gmres"] = {}
+        out["orth_step_us"] = {}
+        ops = {"fp64": (("fused", "gmres_orth"), ("unfused", "gmres_orth_unfused")), "fp32": (("fused_fp32_basis", "gmres_orth_fp32_basis"),)}
         for rep in range(5):
-            out["orth_step_us"]["fused"].append(round(A.bench_op("gmres_orth", 0, 10) * 1e6, 1))
-            out["orth_step_us"]["unfused"].append(round(A.bench_op("gmres_orth_unfused", 0, 10) * 1e6, 1))
+            for bs in bases:
+                A.set_gmres(OPTS["restart"], basis=bs)
+                for key, op in ops[bs]:
+                    out["orth_step_us"].setdefault(key, []).append(round(A.bench_op(op, 0, 10) * 1e6, 1))
+                out["gmres"][bs] = A.gmres_info()
+        if bases == ["fp64"]:
+            out["gmres"] = out["gmres"]["fp64"]
         print(f"[{name}] orthogonalisation step (us): {out['orth_step_us']}", file=sys.stderr, flush=True)
     A.close()
     return out
@@ -104,6 +123,10 @@ def main():
             OPTS["restart"] = int(a.split("=", 1)[1])
         elif a.startswith("--reps="):
             OPTS["reps"] = int(a.split("=", 1)[1])
+        elif a.startswith("--basis="):
+            OPTS["basis"] = a.split("=", 1)[1]
+            if OPTS["basis"] not in ("fp64", "fp32", "both"):
+                sys.exit("--basis is one of fp64 fp32 both")
         elif a == "--no-orth-ab":
             OPTS["orth_ab"] = False
 
