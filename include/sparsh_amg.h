@@ -236,6 +236,17 @@ int sparsh_level_marching_ops(sparsh_handle h, int level, int *on, int *plan, do
  * launch with more workgroups than the reduction buffers hold.  Does not switch a kernel on (sparsh_set_double_sweep /
  * sparsh_set_marching_ops); drops a captured graph.  sparsh_level_double_sweep / sparsh_level_marching_ops report the plan in force. */
 int sparsh_set_box_plan(sparsh_handle h, int level, int kernel, int q, int ty, int cz);
+/* The same with the workgroup size as a fourth dimension of the plan: threads = 256, 512 or 1024 (anything else: SPARSH_EINVAL), and the
+ * tile region must fit q * threads points.  sparsh_set_box_plan is this call with threads = 1024; (q, ty, cz) = (0, 0, 0) restores the
+ * planner's plan on 1024 threads whatever `threads` says. */
+int sparsh_set_box_plan_ex(sparsh_handle h, int level, int kernel, int threads, int q, int ty, int cz);
+/* Threads per workgroup of the plans in force on a box-grid level (0 where the kernel has no plan): the setup's timing may have chosen
+ * 256 or 512 (levels of >= 60 000 rows under the default modes of sparsh_set_double_sweep / sparsh_set_marching_ops). */
+int sparsh_level_box_threads(sparsh_handle h, int level, int *double_threads, int *marching_threads);
+/* Debug entry (no handle, no device): the launch plans the setup would time for kernel 2 / 1 on an nx x ny x nz box, {threads, q, ty, cz}
+ * each, the planner's first; part_cap > 0 bounds the marching kernel's workgroups.  Writes at most cap plans, returns their number
+ * (-1: bad kernel). */
+int sparsh_debug_box_plan_candidates(int kernel, int nx, int ny, int nz, int part_cap, int cap, int *plans);
 int sparsh_level_double_sweep(sparsh_handle h, int level, int *on, int *dims, int *plan, double *single_us, double *double_us);
 int sparsh_level_constant_diagonal(sparsh_handle h, int level, int *is_const, double *value);
 int sparsh_level_prolong_fused(sparsh_handle h, int level, int *fused);
@@ -416,7 +427,8 @@ int sparsh_op_axpby(sparsh_handle h, int n, double a, const double *x, double bc
  * normalisation; plus one copy that stands for the store of w), 14 the same step through one launch_dot + reduction and one
  * launch_axpby per basis vector and pass, which is what the fused kernels replace (13 and 14 want SPARSH_BASIS_FP64 on the handle,
  * SPARSH_ESTATE otherwise), 15 the fused step of 13 on a float basis: the same fill pattern rounded to float (`level` must be 0; wants
- * SPARSH_BASIS_FP32 on the handle, SPARSH_ESTATE otherwise). */
+ * SPARSH_BASIS_FP32 on the handle, SPARSH_ESTATE otherwise), 16 the last post-sweep with its dot through the plane-marching kernel on
+ * the level's resident buffers (SPARSH_ESTATE where the level does not run it). */
 int sparsh_bench_op(sparsh_handle h, int op, int level, int reps, double *avg_seconds);
 
 /* ---- restarted GMRES (SPARSH_GMRES, SPARSH_PGMRES) ----

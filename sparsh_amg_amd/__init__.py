@@ -113,6 +113,9 @@ def _load():
         "sparsh_level_prolong_fused": (C.c_int, [H, C.c_int, C.POINTER(C.c_int)]),
         "sparsh_op_jacobi_prolong": (C.c_int, [H, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p]),
         "sparsh_set_box_plan": (C.c_int, [H, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+        "sparsh_set_box_plan_ex": (C.c_int, [H, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+        "sparsh_level_box_threads": (C.c_int, [H, C.c_int, c_int_p, c_int_p]),
+        "sparsh_debug_box_plan_candidates": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_int_p]),
         "sparsh_op_spmv_dot": (C.c_int, [H, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p]),
         "sparsh_op_jacobi_dot": (C.c_int, [H, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p]),
         "sparsh_level_paired": (C.c_int, [H, C.c_int, C.POINTER(C.c_int)]),
@@ -276,6 +279,19 @@ def index16_roundtrip(rowptr, colindex):
     return a.value, b.value
 
 
+def box_plan_candidates(kernel, nx, ny, nz, part_cap=0):
+    """Debug hook (host only): the launch plans (threads, q, ty, cz) the setup would time for the double sweep (kernel 2 or "double")
+    or the plane-marching kernel (1 or "marching") on an nx x ny x nz box, the planner's plan first; part_cap > 0 bounds the marching
+    kernel's workgroups."""
+    k = {"double": 2, "marching": 1}.get(kernel, kernel)
+    cap = 64
+    buf = (C.c_int * (4 * cap))()
+    n = lib.sparsh_debug_box_plan_candidates(int(k), int(nx), int(ny), int(nz), int(part_cap), cap, buf)
+    if n < 0:
+        raise ValueError("kernel must be 2 (double sweep) or 1 (plane-marching kernel)")
+    return [tuple(buf[4 * i:4 * i + 4]) for i in range(min(n, cap))]
+
+
 def device_count() -> int:
     return lib.sparsh_device_count()
 
@@ -402,18 +418,24 @@ class sp_matrix_mg:
         return {"on": bool(on.value), "points_per_thread": plan[0], "lines_per_tile": plan[1], "planes_per_chunk": plan[2],
                 "table_kernel_us": round(t1.value, 2), "marching_kernel_us": round(t2.value, 2)}
 
-    def set_box_plan(self, level, kernel, q=0, ty=0, cz=0, shared_cu=False):
-        """Test hook: launch plan (points per thread, lines per tile, planes per chunk) of box-grid level `level`'s double sweep
-        (kernel 2 or "double") or plane-marching kernel (1 or "marching"); q = ty = cz = 0 restores the planner's plan, with
-        shared_cu (marching kernel) its shared-CU plan.  Does not switch the kernel on; the plan in force shows in level_double_sweep /
+    def set_box_plan(self, level, kernel, q=0, ty=0, cz=0, shared_cu=False, threads=1024):
+        """Test hook: launch plan (points per thread, lines per tile, planes per chunk; threads per workgroup: 256, 512 or 1024) of
+        box-grid level `level`'s double sweep (kernel 2 or "double") or plane-marching kernel (1 or "marching"); q = ty = cz = 0
+        restores the planner's plan (1024 threads), with shared_cu (marching kernel) its shared-CU plan.  Does not switch the kernel on; the plan in force shows in level_double_sweep /
         level_marching_ops.  SparshError (EINVAL) for a plan the kernel cannot run."""
         k = {"double": 2, "marching": 1}.get(kernel, kernel)
         if shared_cu:
             if k != 1:
                 raise ValueError("shared_cu is a plan of the marching kernel")
             k = 3
-        _check(lib.sparsh_set_box_plan(self._h, int(level), int(k), int(q), int(ty), int(cz)))
+        _check(lib.sparsh_set_box_plan_ex(self._h, int(level), int(k), int(threads), int(q), int(ty), int(cz)))
         return self
+
+    def level_box_threads(self, level):
+        """Threads per workgroup of the plans in force on `level`: (double sweep, marching kernel); 0 where the kernel has no plan."""
+        a, b = C.c_int(0), C.c_int(0)
+        _check(lib.sparsh_level_box_threads(self._h, int(level), C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def set_constant_diagonal(self, enable=True):
         """Levels with one constant diagonal: the zero-guess sweeps take it as an argument instead of streaming diag[]."""
@@ -845,7 +867,7 @@ class sp_matrix_mg:
     def bench_op(self, op, level=0, reps=20):
         ops = {"spmv": 0, "jacobi": 1, "residual": 2, "restrict": 3, "prolong": 4, "coarse": 5, "dot": 6, "axpby": 7, "copy_int": 8,
                "jacobi_pingpong": 9, "jacobi_pingpong_resident": 10, "jacobi_double": 11, "sor": 12,
-               "gmres_orth": 13, "gmres_orth_unfused": 14, "gmres_orth_fp32_basis": 15}
+               "gmres_orth": 13, "gmres_orth_unfused": 14, "gmres_orth_fp32_basis": 15, "jacobi_dot_marching": 16}
         sec = C.c_double()
         _check(lib.sparsh_bench_op(self._h, ops[op] if isinstance(op, str) else op, level, reps, C.byref(sec)))
         return sec.value

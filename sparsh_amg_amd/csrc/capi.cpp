@@ -492,12 +492,40 @@ int sparsh_level_marching_ops(sparsh_handle h, int level, int *on, int *plan, do
     return SPARSH_OK;
 }
 
-int sparsh_set_box_plan(sparsh_handle h, int level, int kernel, int q, int ty, int cz)
+int sparsh_set_box_plan_ex(sparsh_handle h, int level, int kernel, int threads, int q, int ty, int cz)
 {
     REQUIRE_READY(h);
     REQUIRE_LEVEL(h, level);
-    const int rc = h->eng->set_box_plan(level, kernel, q, ty, cz);
+    const int rc = h->eng->set_box_plan(level, kernel, threads, q, ty, cz);
     return rc == SPARSH_OK ? SPARSH_OK : fail(rc, h->eng->error);
+}
+
+int sparsh_set_box_plan(sparsh_handle h, int level, int kernel, int q, int ty, int cz)
+{
+    return sparsh_set_box_plan_ex(h, level, kernel, 1024, q, ty, cz);
+}
+
+int sparsh_level_box_threads(sparsh_handle h, int level, int *double_threads, int *marching_threads)
+{
+    REQUIRE_READY(h);
+    REQUIRE_LEVEL(h, level);
+    const DevLevel &L = h->eng->level(level);
+    if (double_threads) *double_threads = L.A.box_q > 0 ? L.A.box_bs : 0;
+    if (marching_threads) *marching_threads = L.A.box1_q > 0 ? L.A.box1_bs : 0;
+    return SPARSH_OK;
+}
+
+int sparsh_debug_box_plan_candidates(int kernel, int nx, int ny, int nz, int part_cap, int cap, int *plans)
+{
+    if (kernel != 1 && kernel != 2) return -1;
+    const std::vector<BoxPlan> c = box_plan_candidates(kernel, nx, ny, nz, part_cap);
+    for (size_t i = 0; i < c.size() && (int)i < cap && plans; ++i) {
+        plans[4 * i] = c[i].threads;
+        plans[4 * i + 1] = c[i].q;
+        plans[4 * i + 2] = c[i].ty;
+        plans[4 * i + 3] = c[i].cz;
+    }
+    return (int)c.size();
 }
 
 int sparsh_set_constant_diagonal(sparsh_handle h, int enable)
@@ -1412,13 +1440,25 @@ int sparsh_bench_op(sparsh_handle h, int op, int level, int reps, double *avg_se
             ++flip2;
             launch_box2(L.A, xa, L.r, xb, E.params().omega, L.fine, st);
         } break;
+        case 16: {  // last post-sweep + dot through the plane-marching kernel (sdia_box1_kernel), same buffers
+            static thread_local int flip3 = 0;
+            CsrArgs a;
+            a.x = (flip3 & 1) ? L.x2 : L.x;
+            a.y = (flip3 & 1) ? L.x : L.x2;
+            ++flip3;
+            a.b = L.r;
+            a.d = L.diag;
+            a.omega = E.params().omega;
+            a.partial = E.partials();
+            launch_box1(L.A, 1, a, L.fine, st);
+        } break;
         case 13: E.gmres_bench_step(true); break;
         case 14: E.gmres_bench_step(false); break;
         case 15: E.gmres_bench_step(true); break;  // (the handle's float basis)
         default: break;
         }
     };
-    if (op < 0 || op > 15) return fail(SPARSH_EINVAL, "unknown op");
+    if (op < 0 || op > 16) return fail(SPARSH_EINVAL, "unknown op");
     if (op == 13 || op == 14 || op == 15) {
         if (level != 0 || E.distributed()) return fail(SPARSH_EINVAL, "the GMRES orthogonalisation step runs on level 0 of a single-GPU handle");
         if ((op == 15) != (E.gmres_basis() == SPARSH_BASIS_FP32))
@@ -1427,6 +1467,10 @@ int sparsh_bench_op(sparsh_handle h, int op, int level, int reps, double *avg_se
     }
     if (op == 12 && (E.distributed() || !E.build_sor_level(level))) return fail(SPARSH_ESTATE, "no SOR layout on this handle");
     if (op == 11 && (E.distributed() || !box2_applies(L.A, E.kernel_cfg()))) return fail(SPARSH_ESTATE, "the level does not run double sweeps (sparsh_level_double_sweep)");
+    if (op == 16 && (E.distributed() || !box1_applies(L.A, E.kernel_cfg()))) return fail(SPARSH_ESTATE, "the level does not run the plane-marching kernel (sparsh_level_marching_ops)");
+    // (the ops on the level's own buffers, 10, 11 and 16: ones as the right-hand side, as in Engine::tune_box_kernels -- on zeros every quotient
+    // of div_const takes the plain-division branch)
+    if (op == 10 || op == 11 || op == 16) launch_fill(L.n, 1.0, L.r, st);
     for (int i = 0; i < 3; ++i) run();
     hipEvent_t e0, e1;
     (void)hipEventCreate(&e0);
@@ -1439,6 +1483,11 @@ int sparsh_bench_op(sparsh_handle h, int op, int level, int reps, double *avg_se
     (void)hipEventElapsedTime(&ms, e0, e1);
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
+    if (op == 10 || op == 11 || op == 16) {
+        (void)hipMemsetAsync(L.x, 0, n * 8, st);
+        (void)hipMemsetAsync(L.x2, 0, n * 8, st);
+        (void)hipMemsetAsync(L.r, 0, n * 8, st);
+    }
     *avg_seconds = ms * 1e-3 / reps;
     return SPARSH_OK;
 }

@@ -645,10 +645,16 @@ int Engine::setup_host_shared(const sparsh_params &p)
 // (x, x2, r of level 0 and the Krylov vectors), so it times the sweep on the candidate triples once and lets the best one
 // play the three roles -- an assignment of pointers, no extra memory, results unchanged.
 // Box-grid levels: does the double sweep (sdia_box2_kernel) beat two single sweeps here?  Timed on the level's own buffers
-// (KernelConfig::box2 = 1, levels of >= 400 000 rows: below that two launches of a cache-resident level win, tools/micro/box2_proto)
-// or switched on wherever a plan exists (box2 = 2: tests, A/B).
+// (KernelConfig::box2 = 1, levels of >= 60 000 rows) or switched on wherever a plan exists (box2 = 2: tests, A/B).  Where it times, it
+// also times the other launch plans of box_plan_candidates -- workgroups of 256 and 512 threads among them -- and a plan that is at
+// least 3 % faster than the planner's (the smaller of two timings each) takes its place; the verdict against the table kernel follows.
+// The finest level takes no candidate for either kernel: its double sweep stays on the planner's plan (the cost model was fitted there,
+// and at 216-point lines a smaller workgroup holds at most 5 lines of tile), and its marching kernel on the planner's or the shared-CU
+// plan as before -- the marching plan fixes the number of workgroups and hence the order in which PCG's fused dots are summed, and a
+// residual history must not depend on which of a dozen plans won a timing.  (Coarser levels carry no reducing epilogue.)
 void Engine::tune_box_kernels()
 {
+    auto same_plan = [](const BoxPlan &a, const BoxPlan &b) { return a.threads == b.threads && a.q == b.q && a.ty == b.ty && a.cz == b.cz; };
     for (size_t l = 0; l + 1 < lev_.size(); ++l) {
         DevLevel &L = lev_[l];
         L.A.box_on = L.A.box1_on = false;
@@ -660,7 +666,7 @@ void Engine::tune_box_kernels()
         if (cfg_.box1 >= 2) L.A.box1_on = L.A.box1_q > 0;
         const bool time2 = cfg_.box2 == 1, time1 = cfg_.box1 == 1 && L.A.box1_q > 0;
         if (!(time1 || time2)) continue;
-        if (L.n < 400000) continue;
+        if (L.n < 60000) continue;
         hipEvent_t e0 = nullptr, e1 = nullptr;
         if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) continue;
         CsrArgs a;
@@ -691,6 +697,36 @@ void Engine::tune_box_kernels()
         if (time2) {
             L.box_single_us = timed(false);
             L.box_double_us = timed(true);
+            const BoxPlan planned = {L.A.box_bs, L.A.box_q, L.A.box_ty, L.A.box_cz};
+            BoxPlan best = planned;
+            double t_best = 1e30;
+            std::vector<BoxPlan> others;  // (the finest level takes none)
+            if (!L.fine) others = box_plan_candidates(2, L.A.box_nx, L.A.box_ny, L.A.box_nz, 0);
+            for (const BoxPlan &c : others) {
+                if (same_plan(c, planned)) continue;
+                L.A.box_bs = c.threads;
+                L.A.box_q = c.q;
+                L.A.box_ty = c.ty;
+                L.A.box_cz = c.cz;
+                const double t = std::min(timed(true), timed(true));
+                if (t < t_best) {
+                    t_best = t;
+                    best = c;
+                }
+            }
+            if (t_best < 1e30) {  // (the planner's plan gets its second timing too)
+                L.A.box_bs = planned.threads;
+                L.A.box_q = planned.q;
+                L.A.box_ty = planned.ty;
+                L.A.box_cz = planned.cz;
+                L.box_double_us = std::min(L.box_double_us, timed(true));
+            }
+            if (!(t_best < 0.97 * L.box_double_us)) best = planned;
+            else L.box_double_us = t_best;
+            L.A.box_bs = best.threads;
+            L.A.box_q = best.q;
+            L.A.box_ty = best.ty;
+            L.A.box_cz = best.cz;
             L.A.box_on = L.box_double_us < 0.97 * L.box_single_us;
         }
         if (time1) {
@@ -731,6 +767,38 @@ void Engine::tune_box_kernels()
                     L.A.box1_ty = ty0;
                     L.A.box1_cz = cz0;
                 }
+            }
+            {  // the other candidates, smaller workgroups among them: at least 3 % faster than the plan so far, or that one stays
+                const BoxPlan current = {L.A.box1_bs, L.A.box1_q, L.A.box1_ty, L.A.box1_cz};
+                auto set1 = [&](const BoxPlan &c) {
+                    L.A.box1_bs = c.threads;
+                    L.A.box1_q = c.q;
+                    L.A.box1_ty = c.ty;
+                    L.A.box1_cz = c.cz;
+                };
+                BoxPlan best = current;
+                double t_best = 1e30;
+                DevCsr T = L.A;
+                const bool has_planner = box1_plan(T);
+                const BoxPlan planner = {1024, T.box1_q, T.box1_ty, T.box1_cz};  // (timed above)
+                std::vector<BoxPlan> others;  // (the finest level takes none)
+                if (!L.fine) others = box_plan_candidates(1, L.A.box_nx, L.A.box_ny, L.A.box_nz, part_cap_);
+                for (const BoxPlan &c : others) {
+                    if ((has_planner && same_plan(c, planner)) || same_plan(c, current)) continue;
+                    set1(c);
+                    const double t = std::min(timed1(true), timed1(true));
+                    if (t < t_best) {
+                        t_best = t;
+                        best = c;
+                    }
+                }
+                if (t_best < 1e30) {
+                    set1(current);
+                    L.box1_us = std::min(L.box1_us, timed1(true));
+                }
+                if (t_best < 0.97 * L.box1_us) L.box1_us = t_best;
+                else best = current;
+                set1(best);
             }
             L.A.box1_on = L.box1_us < 0.97 * L.box1_table_us;
         }
@@ -1424,6 +1492,7 @@ int Engine::setup(const sparsh_params &p)
     place_best_us = place_worst_us = place_first_us = 0.0;
     phase("coarsest-level factorisation + workspace");
     tune_box_kernels();
+    phase("box kernel plans");
     if (G == 1 && cfg_.place_search) tune_placement();
     phase("placement search");
     f32_ready_ = false;
@@ -1739,7 +1808,7 @@ double Engine::op_jacobi_dot(int l, const double *b, const double *x, double *y)
     return read_scalar(S_TMP);
 }
 
-int Engine::set_box_plan(int l, int kernel, int q, int ty, int cz)
+int Engine::set_box_plan(int l, int kernel, int threads, int q, int ty, int cz)
 {
     auto refuse = [&](const std::string &why) {
         error = why;
@@ -1752,13 +1821,15 @@ int Engine::set_box_plan(int l, int kernel, int q, int ty, int cz)
     if (kernel == 3 && !planner) return refuse("kernel 3 takes the planner's shared-CU plan: q, ty and cz must be 0");
     DevCsr T = A;  // (the planners write their plan into the operator: try it on a copy)
     if (planner) {
+        threads = 1024;
         if (!(kernel == 2 ? box2_plan(T) : box1_plan(T, kernel == 3))) return refuse("the planner has no plan for this grid");
         q = kernel == 2 ? T.box_q : T.box1_q;
         ty = kernel == 2 ? T.box_ty : T.box1_ty;
         cz = kernel == 2 ? T.box_cz : T.box1_cz;
     }
-    if (const char *why = box_plan_refusal(A, kernel == 2 ? 2 : 1, q, ty, cz)) return refuse(why);
+    if (const char *why = box_plan_refusal(A, kernel == 2 ? 2 : 1, threads, q, ty, cz)) return refuse(why);
     if (kernel == 2) {
+        A.box_bs = threads;
         A.box_q = q;
         A.box_ty = ty;
         A.box_cz = cz;
@@ -1768,6 +1839,7 @@ int Engine::set_box_plan(int l, int kernel, int q, int ty, int cz)
         T.box1_cz = cz;
         if (box1_workgroups(T) > part_cap_)
             return refuse("the plan launches " + std::to_string(box1_workgroups(T)) + " workgroups; the partial buffers hold " + std::to_string(part_cap_));
+        A.box1_bs = threads;
         A.box1_q = q;
         A.box1_ty = ty;
         A.box1_cz = cz;

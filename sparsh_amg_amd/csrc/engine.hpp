@@ -173,6 +173,7 @@ public:
     // all-gather at the partitioned -> replicated boundary.  -1 when the step does not exist.
     double bench_comm(int what, int level, int reps);
     hipStream_t stream() const { return st_; }
+    double *partials() const { return part0_; }  // one slot per workgroup of a reducing launch (part_cap_ of them)
     const DevLevel &level(int l) const { return lev_[l]; }
     int n0() const { return A0_.nrow; }
     int local_n0() const { return lev_.empty() ? A0_.nrow : lev_[0].n; }
@@ -242,10 +243,10 @@ public:
     // y = A_l x and x.y / y = J(x) and y.b, through the launches PCG and the V-cycle's last post-sweep use (fused dot, part0_)
     double op_spmv_dot(int l, const double *x, double *y);
     double op_jacobi_dot(int l, const double *b, const double *x, double *y);
-    // test hook: the launch plan of box-grid level l's double sweep (kernel 2) or plane-marching kernel (1); (0, 0, 0) = the planner's
-    // plan, kernel 3 = the marching kernel's shared-CU plan.  Refuses (SPARSH_EINVAL, reason in error) what the kernel cannot run or
+    // test hook: the launch plan (threads per workgroup, q, ty, cz) of box-grid level l's double sweep (kernel 2) or plane-marching
+    // kernel (1); q = ty = cz = 0: the planner's plan on 1024 threads, kernel 3 = the marching kernel's shared-CU plan.  Refuses (SPARSH_EINVAL, reason in error) what the kernel cannot run or
     // what writes more partials than part0_ / part1_ hold; does not switch the kernel on
-    int set_box_plan(int l, int kernel, int q, int ty, int cz);
+    int set_box_plan(int l, int kernel, int threads, int q, int ty, int cz);
     // fuse_zero: also write the coarse level's zero-guess sweep (aggregation P, no gather step); returns whether it did
     bool op_restrict(int l, const double *r, double *bc, bool fuse_zero = false);
     // level_paired(l) levels: b_{l+1} = R (b - A x) and x_{l+1} = omega b_{l+1} / d_{l+1} in one launch

@@ -1222,8 +1222,8 @@ __global__ __launch_bounds__(kTileBlock) void sdia_tile_kernel(int nrow, int xle
 // ------------------------------------------------------------------ double sweep on box grids
 // Two Jacobi sweeps in one pass over x, b and y (temporal blocking).  The single-sweep table kernel at 216^3 moves 24 B per
 // row and sweep at the rate HBM delivers (profiles/r03_pmc); the only way below that is to not write the first sweep's result.
-// A workgroup of 1024 threads owns TY grid lines of every plane of a chunk of CZ planes and marches through the planes:
-//   region in a plane = lines j0-2 .. j0+TY+1 (contiguous in memory), thread t owns the points p = t + 1024 q, q < Q;
+// A workgroup of BS threads owns TY grid lines of every plane of a chunk of CZ planes and marches through the planes:
+//   region in a plane = lines j0-2 .. j0+TY+1 (contiguous in memory), thread t owns the points p = t + BS q, q < Q;
 //   x0 of plane k sits in LDS (X0) for the in-plane neighbours, x0 of planes k-1 / k+1 at the own point in registers;
 //   step k: x1 = J(x0) on plane k, lines 1 .. TY+2 of the region (one ring more than the tile: recomputed, not exchanged --
 //           the same expression on the same operands gives the neighbour workgroup's bits);
@@ -1233,6 +1233,8 @@ __global__ __launch_bounds__(kTileBlock) void sdia_tile_kernel(int nrow, int xle
 // x = y = -0.0), which is exactly "skip the missing entry" of the table kernel, without a predicate.  Every row is computed with
 // the table kernel's products in the table kernel's order, so y is bitwise what two OP_JACOBI launches produce.
 // Reads per row and double sweep: x (TY+4)/TY * (CZ+3)/CZ, b (TY+2)/TY * (CZ+2)/CZ, one store: ~30 B instead of 48.
+// The workgroup is BS = 256, 512 or 1024 threads (a dimension of the launch plan, DevCsr::box_bs / box1_bs): a smaller one holds fewer
+// lines, but several of them share a CU at Q = 3 - 4 and fewer waves meet at each barrier.  The planners plan for kBoxBlock.
 constexpr int kBoxBlock = 1024;
 
 // a / b for a divisor known before the loop: the compiler's own fp64 division sequence -- v_div_scale of both operands, v_rcp_f64 and two
@@ -1280,9 +1282,9 @@ struct BoxArgs {
 
 // ZERO: the leg starts from a zero guess -- x0 is not read: the first (matrix-free) sweep x1 = omega b / d is evaluated where x0 would be
 // loaded, from the right-hand side the stages need anyway, so the launch performs the first THREE sweeps of the leg (y = J(J(omega b / d)))
-template <int Q, int TAG, bool ZERO>
-__global__ __launch_bounds__(kBoxBlock) void sdia_box2_kernel(BoxArgs g, const double *__restrict__ x, const double *__restrict__ b,
-                                                               double *__restrict__ y)
+template <int BS, int Q, int TAG, bool ZERO>
+__global__ __launch_bounds__(BS) void sdia_box2_kernel(BoxArgs g, const double *__restrict__ x, const double *__restrict__ b,
+                                                        double *__restrict__ y)
 {
     extern __shared__ double box_lds[];
     const int nx = g.nx, ny = g.ny, nz = g.nz, P = nx * ny, TY = g.TY;
@@ -1306,14 +1308,14 @@ __global__ __launch_bounds__(kBoxBlock) void sdia_box2_kernel(BoxArgs g, const d
     const int tid = threadIdx.x;
     const double c0 = g.c[0], c1 = g.c[1], c2 = g.c[2], c3 = g.c[3], c4 = g.c[4], c5 = g.c[5], c6 = g.c[6], om = g.omega;
     const DivConst dc = make_div_const(c3);
-    for (int i = tid; i < 2 * cells; i += kBoxBlock) box_lds[i] = 0.0;
+    for (int i = tid; i < 2 * cells; i += BS) box_lds[i] = 0.0;
     bool v0[Q], v1[Q], v2[Q];
     int sidx[Q];
     double xm[Q], xc[Q], xp[Q], bk[Q], bp[Q], x1m[Q], x1c[Q];
     double bq[Q];  // ZERO: b of plane k + 1 (it arrived as the source of xp)
 #pragma unroll
     for (int q = 0; q < Q; ++q) {
-        const int p = tid + kBoxBlock * q;
+        const int p = tid + BS * q;
         const int lr = p / nx;
         const int jr = j0 - 2 + lr;
         sidx[q] = p + lr + 1;
@@ -1325,7 +1327,7 @@ __global__ __launch_bounds__(kBoxBlock) void sdia_box2_kernel(BoxArgs g, const d
     const int ks = z0 - 1;  // first plane of the first sweep (-1: does not exist)
 #pragma unroll
     for (int q = 0; q < Q; ++q) {
-        const int p = tid + kBoxBlock * q;
+        const int p = tid + BS * q;
         if constexpr (ZERO) {
             if (v0[q]) {
                 if (ks >= 1) xm[q] = div_const(om * b[(long)(ks - 1) * P + base + p], dc);
@@ -1353,7 +1355,7 @@ __global__ __launch_bounds__(kBoxBlock) void sdia_box2_kernel(BoxArgs g, const d
         double xn[Q], bn[Q];  // operands of the next step: in flight across this one
 #pragma unroll
         for (int q = 0; q < Q; ++q) {
-            const int p = tid + kBoxBlock * q;
+            const int p = tid + BS * q;
             xn[q] = 0.0;
             bn[q] = 0.0;
             if (k + 1 <= z1) {
@@ -1391,7 +1393,7 @@ __global__ __launch_bounds__(kBoxBlock) void sdia_box2_kernel(BoxArgs g, const d
         if (k2 >= z0 && k2 < z1) {  // uniform
 #pragma unroll
             for (int q = 0; q < Q; ++q) {
-                const int p = tid + kBoxBlock * q;
+                const int p = tid + BS * q;
                 if (v2[q]) {
                     const int s = sidx[q];
                     double sum = 0.0;
@@ -1449,11 +1451,11 @@ struct Box1Args {
     double *partial;         // one per workgroup (the reducing epilogues)
 };
 
-template <int Q, int EPI, int TAG>
-__global__ __launch_bounds__(kBoxBlock) void sdia_box1_kernel(BoxArgs g, Box1Args a)
+template <int BS, int Q, int EPI, int TAG>
+__global__ __launch_bounds__(BS) void sdia_box1_kernel(BoxArgs g, Box1Args a)
 {
     extern __shared__ double box_lds[];
-    __shared__ double red[kBoxBlock / 64];
+    __shared__ double red[BS / 64];
     const int nx = g.nx, ny = g.ny, nz = g.nz, P = nx * ny, TY = g.TY;
     const int R0 = (TY + 2) * nx;
     const int pitch = nx + 1;
@@ -1475,13 +1477,13 @@ __global__ __launch_bounds__(kBoxBlock) void sdia_box1_kernel(BoxArgs g, Box1Arg
     constexpr bool kDivides = EPI == BOX_JACOBI_DOT || EPI == BOX_JACOBI_PROLONG || EPI == BOX_JACOBI;
     DivConst dc3 = {1.0, 1.0, 1.0};
     if constexpr (kDivides) dc3 = make_div_const(c3);
-    for (int i = tid; i < cells; i += kBoxBlock) X0[i] = 0.0;
+    for (int i = tid; i < cells; i += BS) X0[i] = 0.0;
     bool v0[Q], v1[Q];
     int sidx[Q];
     double xm[Q], xc[Q], xp[Q], bk[Q];
 #pragma unroll
     for (int q = 0; q < Q; ++q) {
-        const int p = tid + kBoxBlock * q;
+        const int p = tid + BS * q;
         const int lr = p / nx;
         const int jr = j0 - 1 + lr;
         sidx[q] = p + lr + 1;
@@ -1503,7 +1505,7 @@ __global__ __launch_bounds__(kBoxBlock) void sdia_box1_kernel(BoxArgs g, Box1Arg
         double xn[Q], bn[Q];
 #pragma unroll
         for (int q = 0; q < Q; ++q) {
-            const int p = tid + kBoxBlock * q;
+            const int p = tid + BS * q;
             xn[q] = 0.0;
             bn[q] = 0.0;
             if (k + 1 < z1) {
@@ -1519,7 +1521,7 @@ __global__ __launch_bounds__(kBoxBlock) void sdia_box1_kernel(BoxArgs g, Box1Arg
         __syncthreads();
 #pragma unroll
         for (int q = 0; q < Q; ++q) {
-            const int p = tid + kBoxBlock * q;
+            const int p = tid + BS * q;
             const int s = sidx[q];
             const long row = (long)k * P + base + p;
             double sum = 0.0;
@@ -1594,7 +1596,7 @@ __global__ __launch_bounds__(kBoxBlock) void sdia_box1_kernel(BoxArgs g, Box1Arg
         if (tid == 0) {
             double t = 0.0;
 #pragma unroll
-            for (int q = 0; q < kBoxBlock / 64; ++q) t += red[q];
+            for (int q = 0; q < BS / 64; ++q) t += red[q];
             a.partial[blockIdx.x] = t;
         }
     }
@@ -1974,18 +1976,107 @@ int box1_workgroups(const DevCsr &A)
     return ((A.box_ny + A.box1_ty - 1) / A.box1_ty) * ((A.box_nz + A.box1_cz - 1) / A.box1_cz);
 }
 
-const char *box_plan_refusal(const DevCsr &A, int kernel, int Q, int TY, int CZ)
+const char *box_plan_refusal(const DevCsr &A, int kernel, int threads, int Q, int TY, int CZ)
 {
     const int nx = A.box_nx, ny = A.box_ny, nz = A.box_nz;
     if (nx <= 0) return "the level is not a box grid";
     if (kernel != 1 && kernel != 2) return "kernel must be 2 (double sweep) or 1 (plane-marching kernel)";
+    if (threads != 256 && threads != 512 && threads != 1024) return "threads per workgroup must be 256, 512 or 1024";
     if (Q < 2 || Q > 4) return "points per thread must be 2, 3 or 4";
     if (TY < 1 || TY > ny) return "lines per tile must lie in 1 .. ny";
     if (CZ < 1 || CZ > nz) return "planes per chunk must lie in 1 .. nz";
     const int halo = kernel == 2 ? 4 : 2;  // region = TY + 4 (double sweep) / TY + 2 lines, one point per thread and q
-    if ((long)(TY + halo) * nx > (long)Q * kBoxBlock) return "the tile's region has more points than the workgroup's threads hold";
+    if ((long)(TY + halo) * nx > (long)Q * threads) return "the tile's region has more points than the workgroup's threads hold";
     if ((kernel == 2 ? box2_lds_bytes(nx, TY) : box1_lds_bytes(nx, TY)) > 65536) return "the tile's region does not fit the 64 KiB of LDS";
     return nullptr;
+}
+
+// Pruning model of box_plan_candidates (it only decides which plans are worth timing; the timing decides): r workgroups share a CU --
+// bounded by 2048 threads, by the registers (waves per SIMD at Q = 2 / 3 / 4: 8 / 5 / 4 for the double sweep, 8 / 7 / 5 for the marching
+// kernel) and by 160 KiB of LDS --
+// and a step of theirs costs a fixed part (load round trip and two barriers, overlapped among them: ~1500 point updates, from the
+// 2.0 / 3.5 us steps of 2048 / 4096 points per CU in profiles/r03_levels_216_box_kernels.txt) plus one unit per point.
+static long box_candidate_cost(int kernel, int nx, int ny, int nz, const BoxPlan &p)
+{
+    const long lds = (long)(kernel == 2 ? box2_lds_bytes(nx, p.ty) : box1_lds_bytes(nx, p.ty));
+    const int waves_simd = p.q == 2 ? 8 : (kernel == 2 ? (p.q == 3 ? 5 : 4) : (p.q == 3 ? 7 : 5));
+    long r = std::min<long>(2048 / p.threads, (long)waves_simd * 256 / p.threads);
+    r = std::max<long>(1, std::min<long>(r, 163840 / lds));
+    const long wgs = (long)((ny + p.ty - 1) / p.ty) * ((nz + p.cz - 1) / p.cz);
+    const long rounds = (wgs + 256 * r - 1) / (256 * r);
+    const long resident = std::min<long>(r, (wgs + 255) / 256);
+    return rounds * (p.cz + (kernel == 2 ? 2 : 1)) * (1536 + resident * p.q * p.threads);
+}
+
+std::vector<BoxPlan> box_plan_candidates(int kernel, int nx, int ny, int nz, int part_cap)
+{
+    std::vector<BoxPlan> out;
+    if ((kernel != 1 && kernel != 2) || nx < 2 || ny < 1 || nz < 1) return out;
+    DevCsr T;
+    T.box_nx = nx;
+    T.box_ny = ny;
+    T.box_nz = nz;
+    const int halo = kernel == 2 ? 4 : 2;
+    auto add = [&](int threads, int q, int ty, int cz) {
+        if (box_plan_refusal(T, kernel, threads, q, ty, cz)) return;
+        if (kernel == 1 && part_cap > 0 && (long)((ny + ty - 1) / ty) * ((nz + cz - 1) / cz) > part_cap) return;
+        for (const BoxPlan &o : out)
+            if (o.threads == threads && o.q == q && o.ty == ty && o.cz == cz) return;
+        out.push_back({threads, q, ty, cz});
+    };
+    if (kernel == 2 ? box2_plan(T) : box1_plan(T)) {
+        if (kernel == 2) add(kBoxBlock, T.box_q, T.box_ty, T.box_cz);
+        else add(kBoxBlock, T.box1_q, T.box1_ty, T.box1_cz);
+    }
+    if (kernel == 1 && box1_plan(T, true)) add(kBoxBlock, T.box1_q, T.box1_ty, T.box1_cz);  // the shared-CU plan, where it is another one
+    const size_t first = out.size();
+    for (int threads : {1024, 512, 256}) {
+        for (int Q = 2; Q <= 4; ++Q) {
+            int top = std::min(ny, Q * threads / nx - halo);
+            while (top >= 1 && (kernel == 2 ? box2_lds_bytes(nx, top) : box1_lds_bytes(nx, top)) > 65536) --top;
+            if (top < 1) continue;
+            for (int TY : {top, std::max(1, top / 2)}) {
+                const int ytiles = (ny + TY - 1) / TY;
+                for (int target : {256, 512, 1024}) {
+                    const int chunks = std::max(1, std::min(nz, (target + ytiles / 2) / ytiles));
+                    add(threads, Q, TY, (nz + chunks - 1) / chunks);
+                }
+                add(threads, Q, TY, nz);
+            }
+        }
+    }
+    if ((int)out.size() > kBoxCandidates) {
+        // keep the planners' plans, the lowest modelled cost of every thread count, then the lowest costs overall (first one on
+        // ties); the list keeps its order
+        const size_t n = out.size();
+        std::vector<long> cost(n, 0);
+        std::vector<char> keep(n, 0);
+        for (size_t i = 0; i < n; ++i) cost[i] = i < first ? 0 : box_candidate_cost(kernel, nx, ny, nz, out[i]);
+        std::vector<size_t> order;
+        for (size_t i = first; i < n; ++i) order.push_back(i);
+        std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) { return cost[x] < cost[y]; });
+        size_t nkeep = first;
+        for (size_t i = 0; i < first; ++i) keep[i] = 1;
+        for (int threads : {1024, 512, 256})
+            for (size_t i : order)
+                if (out[i].threads == threads) {
+                    keep[i] = 1;
+                    ++nkeep;
+                    break;
+                }
+        for (size_t i : order) {
+            if ((int)nkeep >= kBoxCandidates) break;
+            if (!keep[i]) {
+                keep[i] = 1;
+                ++nkeep;
+            }
+        }
+        std::vector<BoxPlan> kept;
+        for (size_t i = 0; i < n; ++i)
+            if (keep[i]) kept.push_back(out[i]);
+        out.swap(kept);
+    }
+    return out;
 }
 
 bool box1_applies(const DevCsr &A, const KernelConfig &c)
@@ -2016,18 +2107,24 @@ int launch_box1(const DevCsr &A, int epi, const CsrArgs &a, bool finest, hipStre
     b.partial = a.partial ? a.partial + a.partial_off : nullptr;
     const int chunks = (g.nz + g.CZ - 1) / g.CZ;
     const int nwg = g.ytiles * chunks;
-    const dim3 grid(nwg), block(kBoxBlock);
+    const dim3 grid(nwg), block(A.box1_bs);
     const size_t lds = box1_lds_bytes(g.nx, g.TY);
-#define SPARSH_LAUNCH_BOX1(Q_, E_)                                                                  \
-    do {                                                                                            \
-        if (finest) hipLaunchKernelGGL((sdia_box1_kernel<Q_, E_, 1>), grid, block, lds, st, g, b);  \
-        else hipLaunchKernelGGL((sdia_box1_kernel<Q_, E_, 0>), grid, block, lds, st, g, b);         \
+#define SPARSH_LAUNCH_BOX1(BS_, Q_, E_)                                                                  \
+    do {                                                                                                 \
+        if (finest) hipLaunchKernelGGL((sdia_box1_kernel<BS_, Q_, E_, 1>), grid, block, lds, st, g, b);  \
+        else hipLaunchKernelGGL((sdia_box1_kernel<BS_, Q_, E_, 0>), grid, block, lds, st, g, b);         \
     } while (0)
-#define SPARSH_LAUNCH_BOX1_Q(E_)                      \
-    do {                                              \
-        if (A.box1_q == 4) SPARSH_LAUNCH_BOX1(4, E_); \
-        else if (A.box1_q == 3) SPARSH_LAUNCH_BOX1(3, E_); \
-        else SPARSH_LAUNCH_BOX1(2, E_);               \
+#define SPARSH_LAUNCH_BOX1_BS(Q_, E_)                                \
+    do {                                                             \
+        if (A.box1_bs == 256) SPARSH_LAUNCH_BOX1(256, Q_, E_);       \
+        else if (A.box1_bs == 512) SPARSH_LAUNCH_BOX1(512, Q_, E_);  \
+        else SPARSH_LAUNCH_BOX1(1024, Q_, E_);                       \
+    } while (0)
+#define SPARSH_LAUNCH_BOX1_Q(E_)                              \
+    do {                                                      \
+        if (A.box1_q == 4) SPARSH_LAUNCH_BOX1_BS(4, E_);      \
+        else if (A.box1_q == 3) SPARSH_LAUNCH_BOX1_BS(3, E_); \
+        else SPARSH_LAUNCH_BOX1_BS(2, E_);                    \
     } while (0)
     switch (epi) {
     case BOX_SPMV_DOT: SPARSH_LAUNCH_BOX1_Q(BOX_SPMV_DOT); break;
@@ -2037,6 +2134,7 @@ int launch_box1(const DevCsr &A, int epi, const CsrArgs &a, bool finest, hipStre
     default: SPARSH_LAUNCH_BOX1_Q(BOX_JACOBI_PROLONG); break;
     }
 #undef SPARSH_LAUNCH_BOX1_Q
+#undef SPARSH_LAUNCH_BOX1_BS
 #undef SPARSH_LAUNCH_BOX1
     return nwg;
 }
@@ -2058,21 +2156,28 @@ void launch_box2(const DevCsr &A, const double *x, const double *b, double *y, d
     for (int u = 0; u < 7; ++u) g.c[u] = A.sd_tab.cval[u];
     g.omega = omega;
     const int chunks = (g.nz + g.CZ - 1) / g.CZ;
-    const dim3 grid(g.ytiles * chunks), block(kBoxBlock);
+    const dim3 grid(g.ytiles * chunks), block(A.box_bs);
     const size_t lds = box2_lds_bytes(g.nx, g.TY);
-#define SPARSH_LAUNCH_BOX(Q_)                                                                                       \
-    do {                                                                                                            \
-        if (from_zero) {                                                                                            \
-            if (finest) hipLaunchKernelGGL((sdia_box2_kernel<Q_, 1, true>), grid, block, lds, st, g, x, b, y);      \
-            else hipLaunchKernelGGL((sdia_box2_kernel<Q_, 0, true>), grid, block, lds, st, g, x, b, y);             \
-        } else {                                                                                                    \
-            if (finest) hipLaunchKernelGGL((sdia_box2_kernel<Q_, 1, false>), grid, block, lds, st, g, x, b, y);     \
-            else hipLaunchKernelGGL((sdia_box2_kernel<Q_, 0, false>), grid, block, lds, st, g, x, b, y);            \
-        }                                                                                                           \
+#define SPARSH_LAUNCH_BOX(BS_, Q_)                                                                                       \
+    do {                                                                                                                 \
+        if (from_zero) {                                                                                                 \
+            if (finest) hipLaunchKernelGGL((sdia_box2_kernel<BS_, Q_, 1, true>), grid, block, lds, st, g, x, b, y);      \
+            else hipLaunchKernelGGL((sdia_box2_kernel<BS_, Q_, 0, true>), grid, block, lds, st, g, x, b, y);             \
+        } else {                                                                                                         \
+            if (finest) hipLaunchKernelGGL((sdia_box2_kernel<BS_, Q_, 1, false>), grid, block, lds, st, g, x, b, y);     \
+            else hipLaunchKernelGGL((sdia_box2_kernel<BS_, Q_, 0, false>), grid, block, lds, st, g, x, b, y);            \
+        }                                                                                                                \
     } while (0)
-    if (A.box_q == 4) SPARSH_LAUNCH_BOX(4);
-    else if (A.box_q == 3) SPARSH_LAUNCH_BOX(3);
-    else SPARSH_LAUNCH_BOX(2);
+#define SPARSH_LAUNCH_BOX_BS(Q_)                              \
+    do {                                                      \
+        if (A.box_bs == 256) SPARSH_LAUNCH_BOX(256, Q_);      \
+        else if (A.box_bs == 512) SPARSH_LAUNCH_BOX(512, Q_); \
+        else SPARSH_LAUNCH_BOX(1024, Q_);                     \
+    } while (0)
+    if (A.box_q == 4) SPARSH_LAUNCH_BOX_BS(4);
+    else if (A.box_q == 3) SPARSH_LAUNCH_BOX_BS(3);
+    else SPARSH_LAUNCH_BOX_BS(2);
+#undef SPARSH_LAUNCH_BOX_BS
 #undef SPARSH_LAUNCH_BOX
 }
 
