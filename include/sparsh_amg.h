@@ -229,8 +229,8 @@ int sparsh_set_zero_start(sparsh_handle h, int enable);
 int sparsh_set_deferred_x(sparsh_handle h, int enable);
 int sparsh_level_marching_ops(sparsh_handle h, int level, int *on, int *plan, double *table_us, double *marching_us);
 /* Test hook: the launch plan {points per thread q, lines per tile ty, planes per chunk cz} of a box-grid level's double sweep
- * (kernel 2) or plane-marching kernel (kernel 1) instead of the planner's; (0, 0, 0) restores the planner's plan (box2_plan /
- * box1_plan), kernel 3 with (0, 0, 0) takes the marching kernel's shared-CU plan without timing it.  SPARSH_EINVAL for a level that
+ * (kernel 2) or plane-marching kernel (kernel 1) instead of the planner's; (0, 0, 0) restores the planner's plan (box_planner,
+ * csrc/box_plan.cpp), kernel 3 with (0, 0, 0) takes the marching kernel's shared-CU plan without timing it.  SPARSH_EINVAL for a level that
  * is not a box grid and for a plan the kernel cannot run: q outside {2, 3, 4}, ty outside 1 .. ny, cz outside 1 .. nz, a tile region
  * ((ty + 4) nx points for kernel 2, (ty + 2) nx for kernel 1) larger than q 1024 threads cover or than 64 KiB of LDS, a marching
  * launch with more workgroups than the reduction buffers hold.  Does not switch a kernel on (sparsh_set_double_sweep /

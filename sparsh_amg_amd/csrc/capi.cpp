@@ -442,9 +442,9 @@ int sparsh_level_double_sweep(sparsh_handle h, int level, int *on, int *dims, in
         dims[2] = L.A.box_nz;
     }
     if (plan) {
-        plan[0] = L.A.box_q;
-        plan[1] = L.A.box_ty;
-        plan[2] = L.A.box_cz;
+        plan[0] = L.A.box2.q;
+        plan[1] = L.A.box2.ty;
+        plan[2] = L.A.box2.cz;
     }
     if (single_us) *single_us = L.box_single_us;
     if (double_us) *double_us = L.box_double_us;
@@ -483,9 +483,9 @@ int sparsh_level_marching_ops(sparsh_handle h, int level, int *on, int *plan, do
     const DevLevel &L = h->eng->level(level);
     if (on) *on = (!h->eng->distributed() || L.replicated) && box1_applies(L.A, h->eng->kernel_cfg()) ? 1 : 0;
     if (plan) {
-        plan[0] = L.A.box1_q;
-        plan[1] = L.A.box1_ty;
-        plan[2] = L.A.box1_cz;
+        plan[0] = L.A.box1.q;
+        plan[1] = L.A.box1.ty;
+        plan[2] = L.A.box1.cz;
     }
     if (table_us) *table_us = L.box1_table_us;
     if (marching_us) *marching_us = L.box1_us;
@@ -510,8 +510,8 @@ int sparsh_level_box_threads(sparsh_handle h, int level, int *double_threads, in
     REQUIRE_READY(h);
     REQUIRE_LEVEL(h, level);
     const DevLevel &L = h->eng->level(level);
-    if (double_threads) *double_threads = L.A.box_q > 0 ? L.A.box_bs : 0;
-    if (marching_threads) *marching_threads = L.A.box1_q > 0 ? L.A.box1_bs : 0;
+    if (double_threads) *double_threads = L.A.box2.q > 0 ? L.A.box2.threads : 0;
+    if (marching_threads) *marching_threads = L.A.box1.q > 0 ? L.A.box1.threads : 0;
     return SPARSH_OK;
 }
 

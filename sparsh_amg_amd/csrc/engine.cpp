@@ -384,8 +384,8 @@ bool upload_sdia(Engine &E, const HostCsr &A, DevCsr &D)
                     D.box_nx = nx;
                     D.box_ny = ny;
                     D.box_nz = nz;
-                    box2_plan(D);
-                    box1_plan(D);
+                    D.box2 = box_planner(2, nx, ny, nz);
+                    D.box1 = box_planner(1, nx, ny, nz);
                 }
             }
         }
@@ -486,7 +486,7 @@ bool upload_csr(Engine &E, const HostCsr &A, DevCsr &D, bool with_sell, const st
 }
 
 // partials of a reducing launch on D: one per row block / four wave blocks / four slices, one per workgroup of the plane-marching kernel
-int partial_count(const DevCsr &D) { return std::max(std::max(D.nblk, box1_workgroups(D)), std::max((D.nwblk + 3) / 4, (D.nslice + 3) / 4)); }
+int partial_count(const DevCsr &D) { return std::max(std::max(D.nblk, D.box1.workgroups(D.box_ny, D.box_nz)), std::max((D.nwblk + 3) / 4, (D.nslice + 3) / 4)); }
 
 }  // namespace
 
@@ -654,17 +654,16 @@ int Engine::setup_host_shared(const sparsh_params &p)
 // residual history must not depend on which of a dozen plans won a timing.  (Coarser levels carry no reducing epilogue.)
 void Engine::tune_box_kernels()
 {
-    auto same_plan = [](const BoxPlan &a, const BoxPlan &b) { return a.threads == b.threads && a.q == b.q && a.ty == b.ty && a.cz == b.cz; };
     for (size_t l = 0; l + 1 < lev_.size(); ++l) {
         DevLevel &L = lev_[l];
         L.A.box_on = L.A.box1_on = false;
         L.box_single_us = L.box_double_us = L.box1_table_us = L.box1_us = 0.0;
         // (several GPUs: the replicated levels are whole levels on every rank and take the same path; ranks may decide differently,
         // the results are the same bits either way)
-        if (L.A.box_q <= 0 || (dist_ && !L.replicated) || L.deep || csr_family(L.A, cfg_) != FAM_SDIA_TAB) continue;
+        if (L.A.box2.q <= 0 || (dist_ && !L.replicated) || L.deep || csr_family(L.A, cfg_) != FAM_SDIA_TAB) continue;
         if (cfg_.box2 >= 2) L.A.box_on = true;
-        if (cfg_.box1 >= 2) L.A.box1_on = L.A.box1_q > 0;
-        const bool time2 = cfg_.box2 == 1, time1 = cfg_.box1 == 1 && L.A.box1_q > 0;
+        if (cfg_.box1 >= 2) L.A.box1_on = L.A.box1.q > 0;
+        const bool time2 = cfg_.box2 == 1, time1 = cfg_.box1 == 1 && L.A.box1.q > 0;
         if (!(time1 || time2)) continue;
         if (L.n < 60000) continue;
         hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -694,39 +693,35 @@ void Engine::tune_box_kernels()
             (void)hipEventElapsedTime(&ms, e0, e1);
             return (double)ms * 1e3 / 4.0;  // per pair of sweeps
         };
-        if (time2) {
-            L.box_single_us = timed(false);
-            L.box_double_us = timed(true);
-            const BoxPlan planned = {L.A.box_bs, L.A.box_q, L.A.box_ty, L.A.box_cz};
-            BoxPlan best = planned;
+        // candidates against the incumbent `plan` (timed once already: us): every candidate not in `skip`, the smaller of two timings
+        // each; then the incumbent once more if anything was timed; the best candidate replaces it only where at least 3 % faster
+        auto try_candidates = [&](BoxPlan &plan, double &us, const std::vector<BoxPlan> &cands, const std::vector<BoxPlan> &skip, auto &&time) {
+            const BoxPlan incumbent = plan;
+            BoxPlan best = incumbent;
             double t_best = 1e30;
-            std::vector<BoxPlan> others;  // (the finest level takes none)
-            if (!L.fine) others = box_plan_candidates(2, L.A.box_nx, L.A.box_ny, L.A.box_nz, 0);
-            for (const BoxPlan &c : others) {
-                if (same_plan(c, planned)) continue;
-                L.A.box_bs = c.threads;
-                L.A.box_q = c.q;
-                L.A.box_ty = c.ty;
-                L.A.box_cz = c.cz;
-                const double t = std::min(timed(true), timed(true));
+            for (const BoxPlan &c : cands) {
+                if (std::find(skip.begin(), skip.end(), c) != skip.end()) continue;
+                plan = c;
+                const double t = std::min(time(), time());
                 if (t < t_best) {
                     t_best = t;
                     best = c;
                 }
             }
-            if (t_best < 1e30) {  // (the planner's plan gets its second timing too)
-                L.A.box_bs = planned.threads;
-                L.A.box_q = planned.q;
-                L.A.box_ty = planned.ty;
-                L.A.box_cz = planned.cz;
-                L.box_double_us = std::min(L.box_double_us, timed(true));
+            plan = incumbent;
+            if (t_best < 1e30) us = std::min(us, time());
+            if (t_best < 0.97 * us) {
+                us = t_best;
+                plan = best;
             }
-            if (!(t_best < 0.97 * L.box_double_us)) best = planned;
-            else L.box_double_us = t_best;
-            L.A.box_bs = best.threads;
-            L.A.box_q = best.q;
-            L.A.box_ty = best.ty;
-            L.A.box_cz = best.cz;
+        };
+        const int nx = L.A.box_nx, ny = L.A.box_ny, nz = L.A.box_nz;
+        if (time2) {
+            L.box_single_us = timed(false);
+            L.box_double_us = timed(true);
+            std::vector<BoxPlan> others;  // (the finest level takes none)
+            if (!L.fine) others = box_plan_candidates(2, nx, ny, nz, 0);
+            try_candidates(L.A.box2, L.box_double_us, others, {L.A.box2}, [&] { return timed(true); });
             L.A.box_on = L.box_double_us < 0.97 * L.box_single_us;
         }
         if (time1) {
@@ -750,56 +745,19 @@ void Engine::tune_box_kernels()
             };
             L.box1_table_us = timed1(false);
             L.box1_us = timed1(true);
-            {  // the plan that lets two workgroups share a CU, if it is another one: keep the faster
-                // (more workgroups than the partial buffers hold: not a candidate)
-                const int q0 = L.A.box1_q, ty0 = L.A.box1_ty, cz0 = L.A.box1_cz;
-                if (box1_plan(L.A, true) && (L.A.box1_q != q0 || L.A.box1_ty != ty0 || L.A.box1_cz != cz0) && box1_workgroups(L.A) <= part_cap_) {
-                    const double t_alt = timed1(true);
-                    if (t_alt < L.box1_us) {
-                        L.box1_us = t_alt;
-                    } else {
-                        L.A.box1_q = q0;
-                        L.A.box1_ty = ty0;
-                        L.A.box1_cz = cz0;
-                    }
-                } else {
-                    L.A.box1_q = q0;
-                    L.A.box1_ty = ty0;
-                    L.A.box1_cz = cz0;
-                }
+            // the plan that lets two workgroups share a CU, if it is another one: keep the faster
+            // (more workgroups than the partial buffers hold: not a candidate)
+            const BoxPlan planner = L.A.box1, shared = box_planner(1, nx, ny, nz, true);
+            if (shared.q > 0 && shared != planner && shared.workgroups(ny, nz) <= part_cap_) {
+                L.A.box1 = shared;
+                const double t_alt = timed1(true);
+                if (t_alt < L.box1_us) L.box1_us = t_alt;
+                else L.A.box1 = planner;
             }
-            {  // the other candidates, smaller workgroups among them: at least 3 % faster than the plan so far, or that one stays
-                const BoxPlan current = {L.A.box1_bs, L.A.box1_q, L.A.box1_ty, L.A.box1_cz};
-                auto set1 = [&](const BoxPlan &c) {
-                    L.A.box1_bs = c.threads;
-                    L.A.box1_q = c.q;
-                    L.A.box1_ty = c.ty;
-                    L.A.box1_cz = c.cz;
-                };
-                BoxPlan best = current;
-                double t_best = 1e30;
-                DevCsr T = L.A;
-                const bool has_planner = box1_plan(T);
-                const BoxPlan planner = {1024, T.box1_q, T.box1_ty, T.box1_cz};  // (timed above)
-                std::vector<BoxPlan> others;  // (the finest level takes none)
-                if (!L.fine) others = box_plan_candidates(1, L.A.box_nx, L.A.box_ny, L.A.box_nz, part_cap_);
-                for (const BoxPlan &c : others) {
-                    if ((has_planner && same_plan(c, planner)) || same_plan(c, current)) continue;
-                    set1(c);
-                    const double t = std::min(timed1(true), timed1(true));
-                    if (t < t_best) {
-                        t_best = t;
-                        best = c;
-                    }
-                }
-                if (t_best < 1e30) {
-                    set1(current);
-                    L.box1_us = std::min(L.box1_us, timed1(true));
-                }
-                if (t_best < 0.97 * L.box1_us) L.box1_us = t_best;
-                else best = current;
-                set1(best);
-            }
+            // the other candidates, smaller workgroups among them: at least 3 % faster than the plan so far, or that one stays
+            std::vector<BoxPlan> others;  // (the finest level takes none)
+            if (!L.fine) others = box_plan_candidates(1, nx, ny, nz, part_cap_);
+            try_candidates(L.A.box1, L.box1_us, others, {planner, L.A.box1}, [&] { return timed1(true); });
             L.A.box1_on = L.box1_us < 0.97 * L.box1_table_us;
         }
         (void)hipMemsetAsync(L.x, 0, (size_t)L.n * 8, st_);
@@ -1819,30 +1777,18 @@ int Engine::set_box_plan(int l, int kernel, int threads, int q, int ty, int cz)
     if (kernel < 1 || kernel > 3) return refuse("kernel must be 2 (double sweep), 1 (plane-marching kernel) or 3 (its shared-CU plan)");
     const bool planner = q == 0 && ty == 0 && cz == 0;
     if (kernel == 3 && !planner) return refuse("kernel 3 takes the planner's shared-CU plan: q, ty and cz must be 0");
-    DevCsr T = A;  // (the planners write their plan into the operator: try it on a copy)
+    BoxPlan plan = {threads, q, ty, cz};
     if (planner) {
-        threads = 1024;
-        if (!(kernel == 2 ? box2_plan(T) : box1_plan(T, kernel == 3))) return refuse("the planner has no plan for this grid");
-        q = kernel == 2 ? T.box_q : T.box1_q;
-        ty = kernel == 2 ? T.box_ty : T.box1_ty;
-        cz = kernel == 2 ? T.box_cz : T.box1_cz;
+        plan = box_planner(kernel == 2 ? 2 : 1, A.box_nx, A.box_ny, A.box_nz, kernel == 3);
+        if (plan.q <= 0) return refuse("the planner has no plan for this grid");
     }
-    if (const char *why = box_plan_refusal(A, kernel == 2 ? 2 : 1, threads, q, ty, cz)) return refuse(why);
+    if (const char *why = box_plan_refusal(kernel == 2 ? 2 : 1, A.box_nx, A.box_ny, A.box_nz, plan)) return refuse(why);
     if (kernel == 2) {
-        A.box_bs = threads;
-        A.box_q = q;
-        A.box_ty = ty;
-        A.box_cz = cz;
+        A.box2 = plan;
     } else {
-        T.box1_q = q;
-        T.box1_ty = ty;
-        T.box1_cz = cz;
-        if (box1_workgroups(T) > part_cap_)
-            return refuse("the plan launches " + std::to_string(box1_workgroups(T)) + " workgroups; the partial buffers hold " + std::to_string(part_cap_));
-        A.box1_bs = threads;
-        A.box1_q = q;
-        A.box1_ty = ty;
-        A.box1_cz = cz;
+        const int wgs = plan.workgroups(A.box_ny, A.box_nz);
+        if (wgs > part_cap_) return refuse("the plan launches " + std::to_string(wgs) + " workgroups; the partial buffers hold " + std::to_string(part_cap_));
+        A.box1 = plan;
     }
     config_changed();
     return SPARSH_OK;

@@ -25,6 +25,7 @@
 #include "kernels.hpp"
 
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 namespace sparsh {
@@ -1233,9 +1234,8 @@ __global__ __launch_bounds__(kTileBlock) void sdia_tile_kernel(int nrow, int xle
 // x = y = -0.0), which is exactly "skip the missing entry" of the table kernel, without a predicate.  Every row is computed with
 // the table kernel's products in the table kernel's order, so y is bitwise what two OP_JACOBI launches produce.
 // Reads per row and double sweep: x (TY+4)/TY * (CZ+3)/CZ, b (TY+2)/TY * (CZ+2)/CZ, one store: ~30 B instead of 48.
-// The workgroup is BS = 256, 512 or 1024 threads (a dimension of the launch plan, DevCsr::box_bs / box1_bs): a smaller one holds fewer
-// lines, but several of them share a CU at Q = 3 - 4 and fewer waves meet at each barrier.  The planners plan for kBoxBlock.
-constexpr int kBoxBlock = 1024;
+// The workgroup is BS = 256, 512 or 1024 threads (a dimension of the launch plan, BoxPlan::threads): a smaller one holds fewer
+// lines, but several of them share a CU at Q = 3 - 4 and fewer waves meet at each barrier.  The planner (box_plan.cpp) plans for kBoxBlock.
 
 // a / b for a divisor known before the loop: the compiler's own fp64 division sequence -- v_div_scale of both operands, v_rcp_f64 and two
 // Newton steps on the scaled divisor, q0 = a_s r, rem = fma(-b_s, q0, a_s), v_div_fmas, v_div_fixup -- with the part that depends on b
@@ -1900,201 +1900,46 @@ int launch_csr_tagged(const DevCsr &A, const CsrArgs &a, bool nt, int remap, hip
 }  // namespace
 
 namespace {
-size_t box2_lds_bytes(int nx, int TY) { return (size_t)2 * ((size_t)(TY + 4) * (nx + 1) + 1) * sizeof(double); }
-size_t box1_lds_bytes(int nx, int TY) { return ((size_t)(TY + 2) * (nx + 1) + 1) * sizeof(double); }
-}  // namespace
 
-// Plan of the double sweep: Q points per thread, TY lines per tile, CZ planes per chunk.  Cost model (checked against
-// tools/micro/box2_proto on MI355X: 216^3 Q4/TY14/CZ14 57 us, Q3/TY10/CZ14 94 us, 108x216x216 Q4/TY33/CZ6 34 us, Q2/TY14/CZ14 38 us):
-// a workgroup's time ~ (CZ + 2) steps x Q points, the launch takes ceil(workgroups / 256 CUs) rounds of it.  The Q = 2 instance needs
-// 62 VGPRs and 31 KB of LDS, so two of its workgroups share a CU: 512 slots, each running at ~1/1.6 of the speed it has alone
-// (108 x 216 x 216: Q2/TY14/CZ7 = 496 workgroups 32.9 us against 35.8 for CZ14 = 256 and 35.4 for Q3/TY24/CZ8 = 243).
-bool box2_plan(DevCsr &A)
-{
-    A.box_q = A.box_ty = A.box_cz = 0;
-    const int nx = A.box_nx, ny = A.box_ny, nz = A.box_nz;
-    if (nx < 2 || ny < 1 || nz < 1) return false;
-    long best = -1;
-    for (int Q = 2; Q <= 4; ++Q) {
-        int TY = std::min(ny, Q * kBoxBlock / nx - 4);
-        while (TY >= 1 && box2_lds_bytes(nx, TY) > 65536) --TY;
-        if (TY < 1) continue;
-        const int ytiles = (ny + TY - 1) / TY;
-        for (int zch = 1; zch <= nz; ++zch) {
-            const int CZ = (nz + zch - 1) / zch;
-            const int chunks = (nz + CZ - 1) / CZ;
-            const long wgs = (long)ytiles * chunks;
-            long cost;  // in tenths of a step of one point
-            if (Q == 2 && wgs > 256) cost = ((wgs + 511) / 512) * (CZ + 2) * Q * 16;
-            else cost = ((wgs + 255) / 256) * (CZ + 2) * Q * 10;
-            if (best < 0 || cost < best) {
-                best = cost;
-                A.box_q = Q;
-                A.box_ty = TY;
-                A.box_cz = CZ;
-            }
-        }
-    }
-    return A.box_q > 0;
-}
-
-// plan of the single-stage kernel: region = TY + 2 lines, one LDS plane, nothing recomputed; a workgroup's time ~ (CZ + 1) steps x Q points.
-// shared_cu: count 512 slots for the instances of <= 3 points per thread (<= 64 VGPRs, <= 32 KB of LDS: two workgroups per CU, each at
-// ~1/1.6 speed) -- the alternative plan the setup times against the one-workgroup-per-CU plan (Engine::tune_box_kernels)
-bool box1_plan(DevCsr &A, bool shared_cu)
-{
-    A.box1_q = A.box1_ty = A.box1_cz = 0;
-    const int nx = A.box_nx, ny = A.box_ny, nz = A.box_nz;
-    if (nx < 2 || ny < 1 || nz < 1) return false;
-    long best = -1;
-    for (int Q = 2; Q <= 4; ++Q) {
-        int TY = std::min(ny, Q * kBoxBlock / nx - 2);
-        while (TY >= 1 && box1_lds_bytes(nx, TY) > 65536) --TY;
-        if (TY < 1) continue;
-        const int ytiles = (ny + TY - 1) / TY;
-        for (int zch = 1; zch <= nz; ++zch) {
-            const int CZ = (nz + zch - 1) / zch;
-            const int chunks = (nz + CZ - 1) / CZ;
-            const long wgs = (long)ytiles * chunks;
-            long cost;
-            if (shared_cu && Q <= 3 && wgs > 256) cost = ((wgs + 511) / 512) * (CZ + 1) * Q * 16;
-            else cost = ((wgs + 255) / 256) * (CZ + 1) * Q * 10;
-            if (best < 0 || cost < best) {
-                best = cost;
-                A.box1_q = Q;
-                A.box1_ty = TY;
-                A.box1_cz = CZ;
-            }
-        }
-    }
-    return A.box1_q > 0;
-}
-
-int box1_workgroups(const DevCsr &A)
-{
-    if (A.box1_q <= 0 || A.box1_ty <= 0 || A.box1_cz <= 0) return 0;
-    return ((A.box_ny + A.box1_ty - 1) / A.box1_ty) * ((A.box_nz + A.box1_cz - 1) / A.box1_cz);
-}
-
-const char *box_plan_refusal(const DevCsr &A, int kernel, int threads, int Q, int TY, int CZ)
-{
-    const int nx = A.box_nx, ny = A.box_ny, nz = A.box_nz;
-    if (nx <= 0) return "the level is not a box grid";
-    if (kernel != 1 && kernel != 2) return "kernel must be 2 (double sweep) or 1 (plane-marching kernel)";
-    if (threads != 256 && threads != 512 && threads != 1024) return "threads per workgroup must be 256, 512 or 1024";
-    if (Q < 2 || Q > 4) return "points per thread must be 2, 3 or 4";
-    if (TY < 1 || TY > ny) return "lines per tile must lie in 1 .. ny";
-    if (CZ < 1 || CZ > nz) return "planes per chunk must lie in 1 .. nz";
-    const int halo = kernel == 2 ? 4 : 2;  // region = TY + 4 (double sweep) / TY + 2 lines, one point per thread and q
-    if ((long)(TY + halo) * nx > (long)Q * threads) return "the tile's region has more points than the workgroup's threads hold";
-    if ((kernel == 2 ? box2_lds_bytes(nx, TY) : box1_lds_bytes(nx, TY)) > 65536) return "the tile's region does not fit the 64 KiB of LDS";
-    return nullptr;
-}
-
-// Pruning model of box_plan_candidates (it only decides which plans are worth timing; the timing decides): r workgroups share a CU --
-// bounded by 2048 threads, by the registers (waves per SIMD at Q = 2 / 3 / 4: 8 / 5 / 4 for the double sweep, 8 / 7 / 5 for the marching
-// kernel) and by 160 KiB of LDS --
-// and a step of theirs costs a fixed part (load round trip and two barriers, overlapped among them: ~1500 point updates, from the
-// 2.0 / 3.5 us steps of 2048 / 4096 points per CU in profiles/r03_levels_216_box_kernels.txt) plus one unit per point.
-static long box_candidate_cost(int kernel, int nx, int ny, int nz, const BoxPlan &p)
-{
-    const long lds = (long)(kernel == 2 ? box2_lds_bytes(nx, p.ty) : box1_lds_bytes(nx, p.ty));
-    const int waves_simd = p.q == 2 ? 8 : (kernel == 2 ? (p.q == 3 ? 5 : 4) : (p.q == 3 ? 7 : 5));
-    long r = std::min<long>(2048 / p.threads, (long)waves_simd * 256 / p.threads);
-    r = std::max<long>(1, std::min<long>(r, 163840 / lds));
-    const long wgs = (long)((ny + p.ty - 1) / p.ty) * ((nz + p.cz - 1) / p.cz);
-    const long rounds = (wgs + 256 * r - 1) / (256 * r);
-    const long resident = std::min<long>(r, (wgs + 255) / 256);
-    return rounds * (p.cz + (kernel == 2 ? 2 : 1)) * (1536 + resident * p.q * p.threads);
-}
-
-std::vector<BoxPlan> box_plan_candidates(int kernel, int nx, int ny, int nz, int part_cap)
-{
-    std::vector<BoxPlan> out;
-    if ((kernel != 1 && kernel != 2) || nx < 2 || ny < 1 || nz < 1) return out;
-    DevCsr T;
-    T.box_nx = nx;
-    T.box_ny = ny;
-    T.box_nz = nz;
-    const int halo = kernel == 2 ? 4 : 2;
-    auto add = [&](int threads, int q, int ty, int cz) {
-        if (box_plan_refusal(T, kernel, threads, q, ty, cz)) return;
-        if (kernel == 1 && part_cap > 0 && (long)((ny + ty - 1) / ty) * ((nz + cz - 1) / cz) > part_cap) return;
-        for (const BoxPlan &o : out)
-            if (o.threads == threads && o.q == q && o.ty == ty && o.cz == cz) return;
-        out.push_back({threads, q, ty, cz});
-    };
-    if (kernel == 2 ? box2_plan(T) : box1_plan(T)) {
-        if (kernel == 2) add(kBoxBlock, T.box_q, T.box_ty, T.box_cz);
-        else add(kBoxBlock, T.box1_q, T.box1_ty, T.box1_cz);
-    }
-    if (kernel == 1 && box1_plan(T, true)) add(kBoxBlock, T.box1_q, T.box1_ty, T.box1_cz);  // the shared-CU plan, where it is another one
-    const size_t first = out.size();
-    for (int threads : {1024, 512, 256}) {
-        for (int Q = 2; Q <= 4; ++Q) {
-            int top = std::min(ny, Q * threads / nx - halo);
-            while (top >= 1 && (kernel == 2 ? box2_lds_bytes(nx, top) : box1_lds_bytes(nx, top)) > 65536) --top;
-            if (top < 1) continue;
-            for (int TY : {top, std::max(1, top / 2)}) {
-                const int ytiles = (ny + TY - 1) / TY;
-                for (int target : {256, 512, 1024}) {
-                    const int chunks = std::max(1, std::min(nz, (target + ytiles / 2) / ytiles));
-                    add(threads, Q, TY, (nz + chunks - 1) / chunks);
-                }
-                add(threads, Q, TY, nz);
-            }
-        }
-    }
-    if ((int)out.size() > kBoxCandidates) {
-        // keep the planners' plans, the lowest modelled cost of every thread count, then the lowest costs overall (first one on
-        // ties); the list keeps its order
-        const size_t n = out.size();
-        std::vector<long> cost(n, 0);
-        std::vector<char> keep(n, 0);
-        for (size_t i = 0; i < n; ++i) cost[i] = i < first ? 0 : box_candidate_cost(kernel, nx, ny, nz, out[i]);
-        std::vector<size_t> order;
-        for (size_t i = first; i < n; ++i) order.push_back(i);
-        std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) { return cost[x] < cost[y]; });
-        size_t nkeep = first;
-        for (size_t i = 0; i < first; ++i) keep[i] = 1;
-        for (int threads : {1024, 512, 256})
-            for (size_t i : order)
-                if (out[i].threads == threads) {
-                    keep[i] = 1;
-                    ++nkeep;
-                    break;
-                }
-        for (size_t i : order) {
-            if ((int)nkeep >= kBoxCandidates) break;
-            if (!keep[i]) {
-                keep[i] = 1;
-                ++nkeep;
-            }
-        }
-        std::vector<BoxPlan> kept;
-        for (size_t i = 0; i < n; ++i)
-            if (keep[i]) kept.push_back(out[i]);
-        out.swap(kept);
-    }
-    return out;
-}
-
-bool box1_applies(const DevCsr &A, const KernelConfig &c)
-{
-    return c.box1 != 0 && A.box1_on && A.box1_q > 0 && csr_family(A, c) == FAM_SDIA_TAB;
-}
-
-int launch_box1(const DevCsr &A, int epi, const CsrArgs &a, bool finest, hipStream_t st)
+// grid, stencil constants, omega and the plan's tiling (no plan: the launches that do not tile)
+BoxArgs box_args(const DevCsr &A, double omega, const BoxPlan &p = {})
 {
     BoxArgs g;
     g.nx = A.box_nx;
     g.ny = A.box_ny;
     g.nz = A.box_nz;
-    g.TY = A.box1_ty;
-    g.CZ = A.box1_cz;
-    g.ytiles = (g.ny + g.TY - 1) / g.TY;
+    g.TY = p.ty;
+    g.CZ = p.cz;
+    g.ytiles = p.ty > 0 ? (g.ny + p.ty - 1) / p.ty : 0;
     for (int u = 0; u < 7; ++u) g.c[u] = A.sd_tab.cval[u];
-    g.omega = a.omega;
+    g.omega = omega;
+    return g;
+}
+
+// f(BS, Q) with the plan's threads (256, 512, else 1024) and points per thread (4, 3, else 2) as compile-time constants
+template <class F>
+void box_dispatch(const BoxPlan &p, F &&f)
+{
+    auto with_q = [&](auto bs) {
+        if (p.q == 4) f(bs, std::integral_constant<int, 4>{});
+        else if (p.q == 3) f(bs, std::integral_constant<int, 3>{});
+        else f(bs, std::integral_constant<int, 2>{});
+    };
+    if (p.threads == 256) with_q(std::integral_constant<int, 256>{});
+    else if (p.threads == 512) with_q(std::integral_constant<int, 512>{});
+    else with_q(std::integral_constant<int, 1024>{});
+}
+
+}  // namespace
+
+bool box1_applies(const DevCsr &A, const KernelConfig &c)
+{
+    return c.box1 != 0 && A.box1_on && A.box1.q > 0 && csr_family(A, c) == FAM_SDIA_TAB;
+}
+
+int launch_box1(const DevCsr &A, int epi, const CsrArgs &a, bool finest, hipStream_t st)
+{
+    const BoxArgs g = box_args(A, a.omega, A.box1);
     Box1Args b;
     b.x = a.x;
     b.b = a.b;
@@ -2105,92 +1950,52 @@ int launch_box1(const DevCsr &A, int epi, const CsrArgs &a, bool finest, hipStre
     b.members = a.members;
     b.nfine = a.nfine;
     b.partial = a.partial ? a.partial + a.partial_off : nullptr;
-    const int chunks = (g.nz + g.CZ - 1) / g.CZ;
-    const int nwg = g.ytiles * chunks;
-    const dim3 grid(nwg), block(A.box1_bs);
-    const size_t lds = box1_lds_bytes(g.nx, g.TY);
-#define SPARSH_LAUNCH_BOX1(BS_, Q_, E_)                                                                  \
-    do {                                                                                                 \
-        if (finest) hipLaunchKernelGGL((sdia_box1_kernel<BS_, Q_, E_, 1>), grid, block, lds, st, g, b);  \
-        else hipLaunchKernelGGL((sdia_box1_kernel<BS_, Q_, E_, 0>), grid, block, lds, st, g, b);         \
-    } while (0)
-#define SPARSH_LAUNCH_BOX1_BS(Q_, E_)                                \
-    do {                                                             \
-        if (A.box1_bs == 256) SPARSH_LAUNCH_BOX1(256, Q_, E_);       \
-        else if (A.box1_bs == 512) SPARSH_LAUNCH_BOX1(512, Q_, E_);  \
-        else SPARSH_LAUNCH_BOX1(1024, Q_, E_);                       \
-    } while (0)
-#define SPARSH_LAUNCH_BOX1_Q(E_)                              \
-    do {                                                      \
-        if (A.box1_q == 4) SPARSH_LAUNCH_BOX1_BS(4, E_);      \
-        else if (A.box1_q == 3) SPARSH_LAUNCH_BOX1_BS(3, E_); \
-        else SPARSH_LAUNCH_BOX1_BS(2, E_);                    \
-    } while (0)
+    const int nwg = A.box1.workgroups(g.ny, g.nz);
+    const dim3 grid(nwg), block(A.box1.threads);
+    const size_t lds = box_lds_bytes(1, g.nx, g.TY);
+    auto launch = [&](auto e) {
+        box_dispatch(A.box1, [&](auto bs, auto q) {
+            constexpr int BS = decltype(bs)::value, Q = decltype(q)::value, E = decltype(e)::value;
+            if (finest) hipLaunchKernelGGL((sdia_box1_kernel<BS, Q, E, 1>), grid, block, lds, st, g, b);
+            else hipLaunchKernelGGL((sdia_box1_kernel<BS, Q, E, 0>), grid, block, lds, st, g, b);
+        });
+    };
     switch (epi) {
-    case BOX_SPMV_DOT: SPARSH_LAUNCH_BOX1_Q(BOX_SPMV_DOT); break;
-    case BOX_JACOBI_DOT: SPARSH_LAUNCH_BOX1_Q(BOX_JACOBI_DOT); break;
-    case BOX_RESID_PAIRX: SPARSH_LAUNCH_BOX1_Q(BOX_RESID_PAIRX); break;
-    case BOX_JACOBI: SPARSH_LAUNCH_BOX1_Q(BOX_JACOBI); break;
-    default: SPARSH_LAUNCH_BOX1_Q(BOX_JACOBI_PROLONG); break;
+    case BOX_SPMV_DOT: launch(std::integral_constant<int, BOX_SPMV_DOT>{}); break;
+    case BOX_JACOBI_DOT: launch(std::integral_constant<int, BOX_JACOBI_DOT>{}); break;
+    case BOX_RESID_PAIRX: launch(std::integral_constant<int, BOX_RESID_PAIRX>{}); break;
+    case BOX_JACOBI: launch(std::integral_constant<int, BOX_JACOBI>{}); break;
+    default: launch(std::integral_constant<int, BOX_JACOBI_PROLONG>{}); break;
     }
-#undef SPARSH_LAUNCH_BOX1_Q
-#undef SPARSH_LAUNCH_BOX1_BS
-#undef SPARSH_LAUNCH_BOX1
     return nwg;
 }
 
 bool box2_applies(const DevCsr &A, const KernelConfig &c)
 {
-    return c.box2 != 0 && A.box_on && A.box_q > 0 && csr_family(A, c) == FAM_SDIA_TAB;
+    return c.box2 != 0 && A.box_on && A.box2.q > 0 && csr_family(A, c) == FAM_SDIA_TAB;
 }
 
 void launch_box2(const DevCsr &A, const double *x, const double *b, double *y, double omega, bool finest, hipStream_t st, bool from_zero)
 {
-    BoxArgs g;
-    g.nx = A.box_nx;
-    g.ny = A.box_ny;
-    g.nz = A.box_nz;
-    g.TY = A.box_ty;
-    g.CZ = A.box_cz;
-    g.ytiles = (g.ny + g.TY - 1) / g.TY;
-    for (int u = 0; u < 7; ++u) g.c[u] = A.sd_tab.cval[u];
-    g.omega = omega;
-    const int chunks = (g.nz + g.CZ - 1) / g.CZ;
-    const dim3 grid(g.ytiles * chunks), block(A.box_bs);
-    const size_t lds = box2_lds_bytes(g.nx, g.TY);
-#define SPARSH_LAUNCH_BOX(BS_, Q_)                                                                                       \
-    do {                                                                                                                 \
-        if (from_zero) {                                                                                                 \
-            if (finest) hipLaunchKernelGGL((sdia_box2_kernel<BS_, Q_, 1, true>), grid, block, lds, st, g, x, b, y);      \
-            else hipLaunchKernelGGL((sdia_box2_kernel<BS_, Q_, 0, true>), grid, block, lds, st, g, x, b, y);             \
-        } else {                                                                                                         \
-            if (finest) hipLaunchKernelGGL((sdia_box2_kernel<BS_, Q_, 1, false>), grid, block, lds, st, g, x, b, y);     \
-            else hipLaunchKernelGGL((sdia_box2_kernel<BS_, Q_, 0, false>), grid, block, lds, st, g, x, b, y);            \
-        }                                                                                                                \
-    } while (0)
-#define SPARSH_LAUNCH_BOX_BS(Q_)                              \
-    do {                                                      \
-        if (A.box_bs == 256) SPARSH_LAUNCH_BOX(256, Q_);      \
-        else if (A.box_bs == 512) SPARSH_LAUNCH_BOX(512, Q_); \
-        else SPARSH_LAUNCH_BOX(1024, Q_);                     \
-    } while (0)
-    if (A.box_q == 4) SPARSH_LAUNCH_BOX_BS(4);
-    else if (A.box_q == 3) SPARSH_LAUNCH_BOX_BS(3);
-    else SPARSH_LAUNCH_BOX_BS(2);
-#undef SPARSH_LAUNCH_BOX_BS
-#undef SPARSH_LAUNCH_BOX
+    const BoxArgs g = box_args(A, omega, A.box2);
+    const dim3 grid(A.box2.workgroups(g.ny, g.nz)), block(A.box2.threads);
+    const size_t lds = box_lds_bytes(2, g.nx, g.TY);
+    box_dispatch(A.box2, [&](auto bs, auto q) {
+        constexpr int BS = decltype(bs)::value, Q = decltype(q)::value;
+        if (from_zero) {
+            if (finest) hipLaunchKernelGGL((sdia_box2_kernel<BS, Q, 1, true>), grid, block, lds, st, g, x, b, y);
+            else hipLaunchKernelGGL((sdia_box2_kernel<BS, Q, 0, true>), grid, block, lds, st, g, x, b, y);
+        } else {
+            if (finest) hipLaunchKernelGGL((sdia_box2_kernel<BS, Q, 1, false>), grid, block, lds, st, g, x, b, y);
+            else hipLaunchKernelGGL((sdia_box2_kernel<BS, Q, 0, false>), grid, block, lds, st, g, x, b, y);
+        }
+    });
 }
 
 void launch_box_resid_pair(const DevCsr &A, int axis, const double *x, const double *b, const double *dc, double dconst, double omega,
                            double *bc, double *xc, hipStream_t st)
 {
-    BoxArgs g;
-    g.nx = A.box_nx;
-    g.ny = A.box_ny;
-    g.nz = A.box_nz;
-    g.TY = g.CZ = g.ytiles = 0;
-    for (int u = 0; u < 7; ++u) g.c[u] = A.sd_tab.cval[u];
-    g.omega = omega;
+    const BoxArgs g = box_args(A, omega);
     const int nc = A.nrow / 2;
     if (nc <= 0) return;
     const dim3 grid((nc + kBlock - 1) / kBlock), block(kBlock);

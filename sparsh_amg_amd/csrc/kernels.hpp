@@ -7,6 +7,8 @@
 
 #include <vector>
 
+#include "box_plan.hpp"
+
 namespace sparsh {
 
 // level-wide stencil of the sliced-diagonal layout (see DevCsr::sd_tab)
@@ -75,15 +77,13 @@ struct DevCsr {
     bool has_sdia() const { return sd_ptr != nullptr; }
     // box grid: the table is the 7-point stencil (-plane, -line, -1, 0, +1, +line, +plane) of an nx x ny x nz grid in lexicographic
     // order, every slice conforms and a row lacks exactly the neighbours that would lie outside the box.  Such a level can run
-    // two Jacobi sweeps in one pass over its vectors (sdia_box2_kernel); box_q/ty/cz = the launch plan (box2_plan), box_on =
-    // the setup's verdict that the double sweep beats two single ones on this level (timed there, or forced)
+    // two Jacobi sweeps in one pass over its vectors (sdia_box2_kernel); box2 = the launch plan (box_planner, or a timed or forced
+    // one; q == 0: none), box_on = the setup's verdict that the double sweep beats two single ones on this level (timed there, or forced)
     int box_nx = 0, box_ny = 0, box_nz = 0;
-    int box_q = 0, box_ty = 0, box_cz = 0;
-    int box_bs = 1024;  // threads per workgroup of the plan: 256, 512 or 1024 (the planners' plans are made for 1024)
+    BoxPlan box2;
     bool box_on = false;
     // the same for the single-stage kernel of the launches that carry an epilogue (sdia_box1_kernel): plan and the setup's verdict
-    int box1_q = 0, box1_ty = 0, box1_cz = 0;
-    int box1_bs = 1024;
+    BoxPlan box1;
     bool box1_on = false;
     // rank-local blocks: slices whose rows touch no halo column (interior) / some (boundary)
     int *int_list = nullptr, *bnd_list = nullptr;
@@ -197,8 +197,7 @@ int build_col16(const int *rowptr, const int *col, const int *rec, int nblk, uns
 int launch_csr(const DevCsr &A, CsrOp op, const CsrArgs &a, bool finest, hipStream_t st, const KernelConfig &cfg);
 CsrFamily csr_family(const DevCsr &A, const KernelConfig &cfg);
 // Double Jacobi sweep y = J(J(x)) on a box-grid level (DevCsr::box_nx > 0), bitwise what two OP_JACOBI launches give.
-// box2_plan fills box_q/ty/cz (false: no plan -- lines too long for the LDS region); box2_applies = the level runs it under cfg
-bool box2_plan(DevCsr &A);
+// box2_applies = the level has a plan (DevCsr::box2) and runs it under cfg
 bool box2_applies(const DevCsr &A, const KernelConfig &cfg);
 // from_zero: the leg starts from x = 0: x is not read, y = J(J(omega b / d)) = the first three sweeps of the leg
 void launch_box2(const DevCsr &A, const double *x, const double *b, double *y, double omega, bool finest, hipStream_t st, bool from_zero = false);
@@ -211,23 +210,7 @@ void launch_box_resid_pair(const DevCsr &A, int axis, const double *x, const dou
 // y.b, 2 residual + pair restriction (aggregates = row pairs; y = coarse rhs, y2 = coarse zero-guess sweep, d / dconst = coarse diagonal),
 // 3 Jacobi sweep added to the finer iterate y2 (members / nfine as OP_JACOBI_PROLONG), 4 plain Jacobi sweep into y (the odd sweep of a leg
 // that runs double sweeps).  Returns the number of partial sums written.
-bool box1_plan(DevCsr &A, bool shared_cu = false);
 bool box1_applies(const DevCsr &A, const KernelConfig &cfg);
-// workgroups of a sdia_box1_kernel launch under the level's plan = the partial sums its reducing epilogues write (0: no plan)
-int box1_workgroups(const DevCsr &A);
-// why sdia_box2_kernel (kernel 2) / sdia_box1_kernel (kernel 1) cannot run the plan (threads per workgroup, Q, TY, CZ) on box-grid level
-// A: a message, or nullptr where it can (256, 512 or 1024 threads, one point per thread and q of the tile's region, 64 KiB of LDS)
-const char *box_plan_refusal(const DevCsr &A, int kernel, int threads, int Q, int TY, int CZ);
-// The plans the setup times on an nx x ny x nz box for kernel 2 / 1 (Engine::tune_box_kernels), in a fixed order: the planner's own
-// (1024 threads) first, then per thread count and Q the largest TY and half of it, each with the CZ that bring the workgroup count
-// near 1x, 2x and 4x the 256 CUs and with CZ = nz; duplicates and plans box_plan_refusal rejects dropped, at most kBoxCandidates kept
-// (the planners' own, the lowest modelled cost of each thread count, then the lowest costs overall).  Marching kernel: its shared-CU
-// plan comes second, and no plan launches more than part_cap workgroups (part_cap <= 0: no bound).
-struct BoxPlan {
-    int threads, q, ty, cz;
-};
-constexpr int kBoxCandidates = 12;
-std::vector<BoxPlan> box_plan_candidates(int kernel, int nx, int ny, int nz, int part_cap);
 int launch_box1(const DevCsr &A, int epi, const CsrArgs &a, bool finest, hipStream_t st);
 // OP_RESID_PAIR over the whole of A (a.y = coarse rhs, a.y2 = coarse iterate, a.d = coarse diagonal); applies to operators
 // that run the table kernel under cfg -- resid_pair_applies says whether launch_resid_pair may be called

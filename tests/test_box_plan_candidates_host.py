@@ -41,7 +41,7 @@ def _refused(kernel, box, plan):
 
 
 def _planner(kernel, nx, ny, nz):
-    """box2_plan / box1_plan restated (1024 threads): the plan with the lowest modelled cost, the first one on ties."""
+    """box_planner restated (1024 threads): the plan with the lowest modelled cost, the first one on ties."""
     best, plan = None, None
     for q in (2, 3, 4):
         ty = min(ny, q * 1024 // nx - _halo(kernel))

@@ -50,7 +50,7 @@ def _max_ty(kernel, q, nx, ny):
 
 
 def _planner(kernel, nx, ny, nz, shared_cu=False):
-    """box2_plan / box1_plan restated: the plan with the lowest modelled cost (first one on ties)."""
+    """box_planner restated: the plan with the lowest modelled cost (first one on ties)."""
     best, plan = None, None
     for q in (2, 3, 4):
         ty = _max_ty(kernel, q, nx, ny)
