@@ -1237,40 +1237,50 @@ __global__ __launch_bounds__(kTileBlock) void sdia_tile_kernel(int nrow, int xle
 // The workgroup is BS = 256, 512 or 1024 threads (a dimension of the launch plan, BoxPlan::threads): a smaller one holds fewer
 // lines, but several of them share a CU at Q = 3 - 4 and fewer waves meet at each barrier.  The planner (box_plan.cpp) plans for kBoxBlock.
 
-// a / b for a divisor known before the loop: the compiler's own fp64 division sequence -- v_div_scale of both operands, v_rcp_f64 and two
-// Newton steps on the scaled divisor, q0 = a_s r, rem = fma(-b_s, q0, a_s), v_div_fmas, v_div_fixup -- with the part that depends on b
-// alone, the refined reciprocal of the scaled divisor, computed once per thread instead of once per row and sweep (5 of the 12
-// instructions, among them the quarter-rate v_rcp_f64).  Where v_div_scale would scale b differently for this a (denormal or zero
-// operands, exponents ~2^1000 apart: not residual-sized numbers) the whole wave takes the plain division.  Same instructions on the
-// same operands, hence bitwise the plain division's result (tools/micro/divtest: 1.7e8 random quotients incl. denormals, infinities
-// and NaNs against the compiler's division and against the host's, no difference).
+// a / b for a divisor known before the loop.  The compiler's own fp64 division is v_div_scale of both operands, v_rcp_f64 and two Newton
+// steps on the scaled divisor, q0 = a_s r, rem = fma(-b_s, q0, a_s), v_div_fmas, v_div_fixup.  For operands whose exponents lie in a
+// moderate window (kDivWindow binades either side of 1.0) v_div_scale hands both operands back unchanged with its flag clear, v_div_fmas
+// with a clear flag is a plain FMA and v_div_fixup returns the quotient it is given: the sequence then *is* the three instructions
+// below on the refined reciprocal r0, which depends on b alone and is computed once per thread.  Whether a numerator is in the window
+// is an unsigned range test on its high dword.  If the divisor is outside the window, or any active lane's numerator is (zeros,
+// denormals, infinities, NaNs, |a| below 2^-256 or from 2^257 up: not residual-sized numbers), the whole wave takes the plain
+// division.  The plain division's instructions on its operands, less four that change nothing: bitwise its result (tools/micro/divtest,
+// profiles/div_window_validation.txt: 34 divisors x 2.5e7 numerators against the compiler's division and the host's, window edges
+// included, no difference; tests/test_gpu_div_window.py holds the kernels themselves to the oracle's bits across the edges).
+constexpr int kDivWindow = 256;
+constexpr unsigned kDivWindowWidth = (unsigned)(2 * kDivWindow + 1) << 20;
 struct DivConst {
-    double b, bs0, r0;
+    double b, r0;
+    unsigned fast;  // the flag "b is inside the window and v_div_scale leaves it alone", kept as the width of the numerators' window:
+                    // kDivWindowWidth if set, 0 (no numerator is inside) if clear -- one compare tests the numerator and the flag
 };
+// where v's biased exponent E lies relative to the window |E - 1023| <= kDivWindow: below kDivWindowWidth inside it, from there up outside
+// (the high dword without its sign, exponent field in bits 20 - 30, minus the window's lower edge: one unsigned range test)
+__device__ __forceinline__ unsigned div_window_pos(double v)
+{
+    return ((unsigned)__double2hiint(v) & 0x7fffffffu) - ((unsigned)(1023 - kDivWindow) << 20);
+}
 __device__ __forceinline__ DivConst make_div_const(double b)
 {
     DivConst c;
     c.b = b;
     bool f;
-    c.bs0 = __builtin_amdgcn_div_scale(1.0, b, false, &f);
-    double r = __builtin_amdgcn_rcp(c.bs0);
-    double e = __builtin_fma(-c.bs0, r, 1.0);
+    const double bs0 = __builtin_amdgcn_div_scale(1.0, b, false, &f);
+    double r = __builtin_amdgcn_rcp(bs0);
+    double e = __builtin_fma(-bs0, r, 1.0);
     r = __builtin_fma(r, e, r);
-    e = __builtin_fma(-c.bs0, r, 1.0);
+    e = __builtin_fma(-bs0, r, 1.0);
     r = __builtin_fma(r, e, r);
     c.r0 = r;
+    c.fast = div_window_pos(b) < kDivWindowWidth && bs0 == b ? kDivWindowWidth : 0u;
     return c;
 }
 __device__ __forceinline__ double div_const(double a, const DivConst &c)
 {
-    bool fd, fn;
-    const double bs = __builtin_amdgcn_div_scale(a, c.b, false, &fd);
-    const double as = __builtin_amdgcn_div_scale(a, c.b, true, &fn);
-    if (__builtin_amdgcn_ballot_w64(bs != c.bs0) != 0ull) return a / c.b;  // wave-uniform
-    const double q0 = as * c.r0;
-    const double rem = __builtin_fma(-bs, q0, as);
-    const double q = __builtin_amdgcn_div_fmas(rem, c.r0, q0, fn);
-    return __builtin_amdgcn_div_fixup(q, c.b, a);
+    if (__builtin_expect(__builtin_amdgcn_ballot_w64(div_window_pos(a) >= c.fast) != 0ull, 0)) return a / c.b;  // wave-uniform
+    const double q0 = a * c.r0;
+    const double rem = __builtin_fma(-c.b, q0, a);
+    return __builtin_fma(rem, c.r0, q0);
 }
 
 struct BoxArgs {
@@ -1475,7 +1485,7 @@ __global__ __launch_bounds__(BS) void sdia_box1_kernel(BoxArgs g, Box1Args a)
     const double c0 = g.c[0], c1 = g.c[1], c2 = g.c[2], c3 = g.c[3], c4 = g.c[4], c5 = g.c[5], c6 = g.c[6], om = g.omega;
     constexpr bool kNeedsB = EPI != BOX_SPMV_DOT;
     constexpr bool kDivides = EPI == BOX_JACOBI_DOT || EPI == BOX_JACOBI_PROLONG || EPI == BOX_JACOBI;
-    DivConst dc3 = {1.0, 1.0, 1.0};
+    DivConst dc3 = {1.0, 1.0, 0u};
     if constexpr (kDivides) dc3 = make_div_const(c3);
     for (int i = tid; i < cells; i += BS) X0[i] = 0.0;
     bool v0[Q], v1[Q];

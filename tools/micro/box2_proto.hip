@@ -50,39 +50,42 @@ __global__ __launch_bounds__(256) void sweep1_kernel(Box g, const double *__rest
 
 constexpr int kT = 1024;  // threads per workgroup
 
-// a / b for a divisor known before the loop: the compiler's own fp64 division sequence (v_div_scale x2, v_rcp + two Newton steps on the
-// scaled divisor, q0 = a_s r, rem = fma(-b_s, q0, a_s), v_div_fmas, v_div_fixup) with the part that depends on b alone -- the refined
-// reciprocal of the scaled divisor -- computed once.  Where v_div_scale would scale b differently for this a (denormals, exponents
-// ~2^1000 apart: never for residual-sized numbers) the whole wave takes the plain division.  Same instructions on the same operands:
-// bitwise the plain division's result.
+// a / b for a divisor known before the loop (the copy of csrc/kernels.hip's): for a divisor and numerators whose exponents lie within
+// kDivWindow binades of 1.0 the compiler's own fp64 division sequence leaves both operands unscaled, its v_div_fmas is a plain FMA and its
+// v_div_fixup returns the quotient it is given, so the three instructions below on the reciprocal refined once per thread are bitwise the
+// plain division's result; if any active lane's numerator is outside the window the whole wave takes the plain division.
+constexpr int kDivWindow = 256;
+constexpr unsigned kDivWindowWidth = (unsigned)(2 * kDivWindow + 1) << 20;
 struct DivConst {
-    double b, bs0, r0;
+    double b, r0;
+    unsigned fast;  // kDivWindowWidth if b is inside the window and v_div_scale leaves it alone, else 0 (no numerator is inside)
 };
+__device__ __forceinline__ unsigned div_window_pos(double v)
+{
+    return ((unsigned)__double2hiint(v) & 0x7fffffffu) - ((unsigned)(1023 - kDivWindow) << 20);
+}
 __device__ __forceinline__ DivConst make_div_const(double b)
 {
     DivConst c;
     c.b = b;
     bool f;
-    c.bs0 = __builtin_amdgcn_div_scale(1.0, b, false, &f);
-    double r = __builtin_amdgcn_rcp(c.bs0);
-    double e = __builtin_fma(-c.bs0, r, 1.0);
+    const double bs0 = __builtin_amdgcn_div_scale(1.0, b, false, &f);
+    double r = __builtin_amdgcn_rcp(bs0);
+    double e = __builtin_fma(-bs0, r, 1.0);
     r = __builtin_fma(r, e, r);
-    e = __builtin_fma(-c.bs0, r, 1.0);
+    e = __builtin_fma(-bs0, r, 1.0);
     r = __builtin_fma(r, e, r);
     c.r0 = r;
+    c.fast = div_window_pos(b) < kDivWindowWidth && bs0 == b ? kDivWindowWidth : 0u;
     return c;
 }
 __device__ __forceinline__ double div_const(double a, const DivConst &c)
 {
 #ifdef FASTDIV
-    bool fd, fn;
-    const double bs = __builtin_amdgcn_div_scale(a, c.b, false, &fd);
-    const double as = __builtin_amdgcn_div_scale(a, c.b, true, &fn);
-    if (__builtin_amdgcn_ballot_w64(bs != c.bs0) != 0ull) return a / c.b;
-    const double q0 = as * c.r0;
-    const double rem = __builtin_fma(-bs, q0, as);
-    const double q = __builtin_amdgcn_div_fmas(rem, c.r0, q0, fn);
-    return __builtin_amdgcn_div_fixup(q, c.b, a);
+    if (__builtin_expect(__builtin_amdgcn_ballot_w64(div_window_pos(a) >= c.fast) != 0ull, 0)) return a / c.b;  // wave-uniform
+    const double q0 = a * c.r0;
+    const double rem = __builtin_fma(-c.b, q0, a);
+    return __builtin_fma(rem, c.r0, q0);
 #else
     return a / c.b;
 #endif
