@@ -42,6 +42,8 @@ extern "C" {
 /* Smoother of the V-cycle (sparsh_set_smoother). */
 #define SPARSH_SMOOTH_JACOBI 0  /* weighted Jacobi, parallel::jacobi_smoother (default) */
 #define SPARSH_SMOOTH_SOR 1     /* multicolour SOR, parallel::sor_smoother (src/AMG_smoothers.cpp:78-102) */
+#define SPARSH_SMOOTH_CHEBYSHEV 3 /* Chebyshev polynomial in D^-1 A (see "Chebyshev polynomial smoother" below); 2 is no smoother and
+                                   * stays SPARSH_EINVAL, as sparsh_set_smoother has always reported it */
 #define SPARSH_SOR_FORWARD 0    /* post-smoothing takes the colours 1..C, as AMG_solve_SOR (src/AMG_phases.cpp:234-306) */
 #define SPARSH_SOR_SYMMETRIC 1  /* post-smoothing takes the colours C..1: a symmetric preconditioner (required by SPARSH_PCG) */
 
@@ -428,7 +430,9 @@ int sparsh_op_axpby(sparsh_handle h, int n, double a, const double *x, double bc
  * launch_axpby per basis vector and pass, which is what the fused kernels replace (13 and 14 want SPARSH_BASIS_FP64 on the handle,
  * SPARSH_ESTATE otherwise), 15 the fused step of 13 on a float basis: the same fill pattern rounded to float (`level` must be 0; wants
  * SPARSH_BASIS_FP32 on the handle, SPARSH_ESTATE otherwise), 16 the last post-sweep with its dot through the plane-marching kernel on
- * the level's resident buffers (SPARSH_ESTATE where the level does not run it). */
+ * the level's resident buffers (SPARSH_ESTATE where the level does not run it), 17 one Chebyshev step (the k >= 1 form: both
+ * coefficients and the previous correction in use) ping-ponging on the level's resident x / x2 buffers with its d vector and r as
+ * the right-hand side: the counterpart of 10 (single-GPU handles). */
 int sparsh_bench_op(sparsh_handle h, int op, int level, int reps, double *avg_seconds);
 
 /* ---- restarted GMRES (SPARSH_GMRES, SPARSH_PGMRES) ----
@@ -467,7 +471,7 @@ int sparsh_set_gmres_basis(sparsh_handle h, int precision);
 int sparsh_gmres_basis(sparsh_handle h, int *precision);
 
 /* ---- multicolour SOR smoother ----
- * sparsh_set_smoother: kind SPARSH_SMOOTH_JACOBI (default) or SPARSH_SMOOTH_SOR; sweeps per leg (0: the default -- 6 for SOR,
+ * sparsh_set_smoother: kind SPARSH_SMOOTH_JACOBI (default), SPARSH_SMOOTH_SOR or SPARSH_SMOOTH_CHEBYSHEV (below); sweeps per leg (0: the default -- 6 for SOR,
  * the count AMG_solve_SOR hard-codes, params.sweeps for Jacobi); order SPARSH_SOR_FORWARD / SPARSH_SOR_SYMMETRIC (SOR only).
  * May be called before or after sparsh_setup, also between sparsh_krylov_init_dev and sparsh_krylov_step_dev (the steps then
  * use the new smoother); selecting Jacobi again restores the Jacobi cycle exactly.  SOR is refused (SPARSH_EINVAL) on
@@ -494,6 +498,35 @@ int sparsh_set_sor_path(sparsh_handle h, int mode);
  * copy.  The smoothed levels (all but the coarsest, which is solved directly) get theirs at sparsh_setup when SOR was selected
  * before it, else at the first SOR solve; any level at its first sparsh_op_sor.  SPARSH_ESTATE when it is not built. */
 int sparsh_level_sor_layout(sparsh_handle h, int level, int *ncolors, int *single_launch, long *bytes);
+
+/* ---- Chebyshev polynomial smoother ----
+ * sparsh_set_smoother(h, SPARSH_SMOOTH_CHEBYSHEV, degree, 0): a smoothing leg is a Chebyshev polynomial of that degree in D^-1 A
+ * (1..16; 0: the default of 4; order must be 0; anything else SPARSH_EINVAL).  One step costs one pass over A, like a Jacobi
+ * sweep, plus one vector d per smoothed level (read and written: 16 B per row).  The leg is symmetric, so SPARSH_PCG takes it as
+ * it is; SPARSH_AMG, SPARSH_PBICG, SPARSH_PGMRES, sparsh_op_precond and the stepwise Krylov calls accept it too.  Refused
+ * (SPARSH_EINVAL) on partitioned (multi-GPU) handles and with params.precond_fp32, like SOR.  The V-cycle keeps the Jacobi hierarchy
+ * and order of operations; selecting Jacobi again restores the Jacobi cycle exactly.
+ * Bounds, per smoothed level (every level but the coarsest), on the host: gershgorin = max_i sum_j |a_ij| / |a_ii|; lanczos = the
+ * largest Ritz value of D^-1/2 A D^-1/2 after min(steps, n) steps of plain Lanczos from a fixed start vector (independent of the
+ * thread count); lmax = min(1.1 * lanczos, gershgorin); lmin = lmax / ratio.  Where some a_ii is not positive and finite, lanczos = 0
+ * and lmax = gershgorin.  Computed at sparsh_setup / sparsh_setup_host when Chebyshev was selected before it, otherwise at first use.
+ * The polynomial assumes a real positive spectrum in [lmin, lmax]: an unsymmetric A is accepted (SPARSH_PGMRES, SPARSH_PBICG), and
+ * whether its spectrum is close enough to such an interval is the caller's risk.
+ * Step k of a leg (coefficients in double on the host: theta = (lmax + lmin)/2, delta = (lmax - lmin)/2, sigma = theta/delta,
+ * rho_0 = 1/sigma, c1_0 = 0, c2_0 = 1/theta; rho_k = 1/(2 sigma - rho_{k-1}), c1_k = rho_k rho_{k-1}, c2_k = 2 rho_k/delta):
+ *   h = b_i - s_i ; d_i = c1_k d_i + (c2_k h)/a_ii ; x_i = x_i + d_i      (s_i = sum_j a_ij x_j in stored order, d = 0 before step 0)
+ * sparsh_set_chebyshev: ratio > 1 (0: the default of 30) and Lanczos steps 1..64 (0: the default of 10); callable before or after
+ * the setup; a changed step count drops the computed bounds.
+ * sparsh_set_chebyshev_lmax: the caller's own upper bound for a level (> 0 and finite; 0 restores the estimate); after
+ * sparsh_setup_host, and dropped by the next setup.
+ * sparsh_level_chebyshev: the bounds of a level (after sparsh_setup_host; no device needed; any pointer may be NULL); lmax and
+ * lmin are the ones in use (a forced lmax included).  The coarsest level, which the cycle solves directly, gets bounds on request
+ * like any other: they serve sparsh_op_cheby and sparsh_bench_op there.
+ * sparsh_op_cheby: one leg of `degree` steps (0..16) of a level on host vectors; x_is_zero: x is taken as 0 (not read). */
+int sparsh_set_chebyshev(sparsh_handle h, double ratio, int lanczos_steps);
+int sparsh_set_chebyshev_lmax(sparsh_handle h, int level, double lmax);
+int sparsh_level_chebyshev(sparsh_handle h, int level, double *lmax, double *lmin, double *gershgorin, double *lanczos);
+int sparsh_op_cheby(sparsh_handle h, int level, const double *b, double *x, int degree, int x_is_zero);
 
 /* device memory helpers so a host language needs no HIP binding of its own */
 int sparsh_dev_alloc(sparsh_handle h, long nbytes, void **out);

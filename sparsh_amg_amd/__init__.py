@@ -26,11 +26,11 @@ SPARSH_AMG, SPARSH_CG, SPARSH_PCG, SPARSH_BICG, SPARSH_PBICG = 0, 1, 2, 3, 4
 SPARSH_GMRES, SPARSH_PGMRES = 5, 6
 METHODS = {"amg": SPARSH_AMG, "cg": SPARSH_CG, "pcg": SPARSH_PCG, "bicg": SPARSH_BICG, "pbicg": SPARSH_PBICG,
            "gmres": SPARSH_GMRES, "pgmres": SPARSH_PGMRES}
-SPARSH_SMOOTH_JACOBI, SPARSH_SMOOTH_SOR = 0, 1
+SPARSH_SMOOTH_JACOBI, SPARSH_SMOOTH_SOR, SPARSH_SMOOTH_CHEBYSHEV = 0, 1, 3
 SPARSH_SOR_FORWARD, SPARSH_SOR_SYMMETRIC = 0, 1
 SPARSH_BASIS_FP64, SPARSH_BASIS_FP32 = 0, 1
 GMRES_BASES = {"fp64": SPARSH_BASIS_FP64, "fp32": SPARSH_BASIS_FP32}
-SMOOTHERS = {"jacobi": SPARSH_SMOOTH_JACOBI, "sor": SPARSH_SMOOTH_SOR}
+SMOOTHERS = {"jacobi": SPARSH_SMOOTH_JACOBI, "sor": SPARSH_SMOOTH_SOR, "chebyshev": SPARSH_SMOOTH_CHEBYSHEV}
 SOR_ORDERS = {"forward": SPARSH_SOR_FORWARD, "symmetric": SPARSH_SOR_SYMMETRIC}
 SPARSH_OK, SPARSH_EINVAL, SPARSH_ENODEV, SPARSH_ESTATE, SPARSH_ENUMERIC, SPARSH_ENOCONV, SPARSH_ECOMM = 0, -1, -2, -3, -4, -5, -6
 
@@ -198,6 +198,10 @@ def _load():
         "sparsh_op_sor": (C.c_int, [H, C.c_int, c_dbl_p, c_dbl_p, C.c_int, C.c_int, C.c_int]),
         "sparsh_set_sor_path": (C.c_int, [H, C.c_int]),
         "sparsh_level_sor_layout": (C.c_int, [H, C.c_int, c_int_p, c_int_p, C.POINTER(C.c_long)]),
+        "sparsh_set_chebyshev": (C.c_int, [H, C.c_double, C.c_int]),
+        "sparsh_set_chebyshev_lmax": (C.c_int, [H, C.c_int, C.c_double]),
+        "sparsh_level_chebyshev": (C.c_int, [H, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p]),
+        "sparsh_op_cheby": (C.c_int, [H, C.c_int, c_dbl_p, c_dbl_p, C.c_int, C.c_int]),
         "sparsh_profile_read": (C.c_int, [H, c_dbl_p]),
         "sparsh_set_gmres": (C.c_int, [H, C.c_int]),
         "sparsh_gmres_info": (C.c_int, [H, c_int_p, C.POINTER(C.c_long)]),
@@ -501,12 +505,30 @@ class sp_matrix_mg:
 
     # -- smoother ------------------------------------------------------------------------------
     def set_smoother(self, kind="jacobi", sweeps=0, order="forward"):
-        """Smoother of the V-cycle: "jacobi" (default) or "sor" (multicolour SOR); sweeps per leg (0: params.sweeps for
-        Jacobi, 6 for SOR); order of the SOR post-smoothing: "forward" or "symmetric" (SPARSH_PCG needs "symmetric")."""
+        """Smoother of the V-cycle: "jacobi" (default), "sor" (multicolour SOR) or "chebyshev" (polynomial in D^-1 A); sweeps per
+        leg (0: params.sweeps for Jacobi, 6 for SOR; Chebyshev: the degree, 1..16, 0 = 4); order of the SOR post-smoothing:
+        "forward" or "symmetric" (SPARSH_PCG needs "symmetric")."""
         k = SMOOTHERS[kind] if isinstance(kind, str) else int(kind)
         o = SOR_ORDERS[order] if isinstance(order, str) else int(order)
         _check(lib.sparsh_set_smoother(self._h, k, int(sweeps), o))
         return self
+
+    def set_chebyshev(self, ratio=0.0, lanczos_steps=0):
+        """Chebyshev smoother: lmin = lmax / ratio (> 1; 0 = the default of 30) and the Lanczos steps of the lmax estimate (1..64;
+        0 = the default of 10).  A changed step count drops the computed bounds."""
+        _check(lib.sparsh_set_chebyshev(self._h, float(ratio), int(lanczos_steps)))
+        return self
+
+    def set_chebyshev_lmax(self, level, lmax=0.0):
+        """Force the upper spectral bound of a level (0 restores the estimate); dropped by the next setup."""
+        _check(lib.sparsh_set_chebyshev_lmax(self._h, int(level), float(lmax)))
+        return self
+
+    def level_chebyshev(self, level):
+        """dict(lmax, lmin, gershgorin, lanczos) of a level; needs the host setup only."""
+        out = [C.c_double() for _ in range(4)]
+        _check(lib.sparsh_level_chebyshev(self._h, int(level), *[C.byref(o) for o in out]))
+        return dict(zip(("lmax", "lmin", "gershgorin", "lanczos"), (o.value for o in out)))
 
     # -- restarted GMRES -----------------------------------------------------------------------
     def set_gmres(self, restart=0, basis=None):
@@ -867,7 +889,8 @@ class sp_matrix_mg:
     def bench_op(self, op, level=0, reps=20):
         ops = {"spmv": 0, "jacobi": 1, "residual": 2, "restrict": 3, "prolong": 4, "coarse": 5, "dot": 6, "axpby": 7, "copy_int": 8,
                "jacobi_pingpong": 9, "jacobi_pingpong_resident": 10, "jacobi_double": 11, "sor": 12,
-               "gmres_orth": 13, "gmres_orth_unfused": 14, "gmres_orth_fp32_basis": 15, "jacobi_dot_marching": 16}
+               "gmres_orth": 13, "gmres_orth_unfused": 14, "gmres_orth_fp32_basis": 15, "jacobi_dot_marching": 16,
+               "chebyshev_pingpong_resident": 17}
         sec = C.c_double()
         _check(lib.sparsh_bench_op(self._h, ops[op] if isinstance(op, str) else op, level, reps, C.byref(sec)))
         return sec.value
@@ -889,6 +912,13 @@ class sp_matrix_mg:
         b = np.ascontiguousarray(b, dtype=np.float64)
         x = np.array(x, dtype=np.float64)
         _check(lib.sparsh_op_sor(self._h, level, _dp(b), _dp(x), int(sweeps), 1 if reverse else 0, 1 if x_is_zero else 0))
+        return x
+
+    def op_cheby(self, level, b, x, degree, x_is_zero=False):
+        """One Chebyshev leg of `degree` steps on a level (host vectors), whatever the handle's smoother."""
+        b = np.ascontiguousarray(b, dtype=np.float64)
+        x = np.array(x, dtype=np.float64)
+        _check(lib.sparsh_op_cheby(self._h, int(level), _dp(b), _dp(x), int(degree), 1 if x_is_zero else 0))
         return x
 
     def op_residual(self, level, b, x):

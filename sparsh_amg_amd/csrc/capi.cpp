@@ -603,11 +603,19 @@ int sparsh_set_smoother(sparsh_handle h, int kind, int sweeps, int order)
 {
     if (!h || !h->eng) return fail(SPARSH_EINVAL, "null handle");
     Engine &E = *h->eng;
-    if (kind != SPARSH_SMOOTH_JACOBI && kind != SPARSH_SMOOTH_SOR)
-        return fail(SPARSH_EINVAL, "kind must be SPARSH_SMOOTH_JACOBI (0) or SPARSH_SMOOTH_SOR (1)");
+    if (kind != SPARSH_SMOOTH_JACOBI && kind != SPARSH_SMOOTH_SOR && kind != SPARSH_SMOOTH_CHEBYSHEV)
+        return fail(SPARSH_EINVAL, "kind must be SPARSH_SMOOTH_JACOBI (0), SPARSH_SMOOTH_SOR (1) or SPARSH_SMOOTH_CHEBYSHEV (3)");
     if (sweeps < 0) return fail(SPARSH_EINVAL, "sweeps < 0");
     if (order != SPARSH_SOR_FORWARD && order != SPARSH_SOR_SYMMETRIC)
         return fail(SPARSH_EINVAL, "order must be SPARSH_SOR_FORWARD (0) or SPARSH_SOR_SYMMETRIC (1)");
+    if (kind == SPARSH_SMOOTH_CHEBYSHEV) {
+        if (sweeps > kChebyMaxDegree) return fail(SPARSH_EINVAL, "the Chebyshev degree must be 1..16 (0: the default of 4)");
+        if (order != 0) return fail(SPARSH_EINVAL, "the Chebyshev smoother has no order: pass 0");
+        if (E.distributed() || (E.comm() && E.comm()->size > 1))
+            return fail(SPARSH_EINVAL, "the Chebyshev smoother is not available on a partitioned (multi-GPU) handle");
+        if ((E.host_ready() || E.ready()) && E.params().precond_fp32)
+            return fail(SPARSH_EINVAL, "the Chebyshev smoother has no fp32 hierarchy: unset params.precond_fp32");
+    }
     if (kind == SPARSH_SMOOTH_JACOBI && sweeps > 0 && E.ready() && E.distributed())
         return fail(SPARSH_EINVAL, "a partitioned handle sizes its ghost layers for the sweep count of its setup: change params.sweeps and call sparsh_setup");
     if (kind == SPARSH_SMOOTH_SOR) {
@@ -617,6 +625,36 @@ int sparsh_set_smoother(sparsh_handle h, int kind, int sweeps, int order)
             return fail(SPARSH_EINVAL, "the SOR smoother has no fp32 hierarchy: unset params.precond_fp32");
     }
     E.set_smoother(kind, sweeps, order);
+    return SPARSH_OK;
+}
+
+int sparsh_set_chebyshev(sparsh_handle h, double ratio, int lanczos_steps)
+{
+    if (!h || !h->eng) return fail(SPARSH_EINVAL, "null handle");
+    if (!(ratio == 0.0 || (ratio > 1.0 && std::isfinite(ratio)))) return fail(SPARSH_EINVAL, "ratio must be > 1 (0: the default of 30)");
+    if (lanczos_steps < 0 || lanczos_steps > kChebyMaxSteps) return fail(SPARSH_EINVAL, "lanczos_steps must be 1..64 (0: the default of 10)");
+    h->eng->set_chebyshev(ratio == 0.0 ? kChebyDefaultRatio : ratio, lanczos_steps == 0 ? kChebyDefaultSteps : lanczos_steps);
+    return SPARSH_OK;
+}
+
+int sparsh_set_chebyshev_lmax(sparsh_handle h, int level, double lmax)
+{
+    REQUIRE_HOST(h);
+    REQUIRE_LEVEL(h, level);
+    if (!(lmax >= 0.0 && std::isfinite(lmax))) return fail(SPARSH_EINVAL, "lmax must be > 0 and finite (0: the estimate)");
+    h->eng->set_cheby_lmax(level, lmax);
+    return SPARSH_OK;
+}
+
+int sparsh_level_chebyshev(sparsh_handle h, int level, double *lmax, double *lmin, double *gershgorin, double *lanczos)
+{
+    REQUIRE_HOST(h);
+    REQUIRE_LEVEL(h, level);
+    const ChebyLevel &c = h->eng->level_cheby(level);
+    if (lmax) *lmax = c.lmax();
+    if (lmin) *lmin = c.lmax() / h->eng->cheby_ratio();
+    if (gershgorin) *gershgorin = c.est.gershgorin;
+    if (lanczos) *lanczos = c.est.lanczos;
     return SPARSH_OK;
 }
 
@@ -1183,6 +1221,21 @@ int sparsh_op_sor(sparsh_handle h, int level, const double *b, double *x, int sw
     return done(E, dx.get(x));
 }
 
+int sparsh_op_cheby(sparsh_handle h, int level, const double *b, double *x, int degree, int x_is_zero)
+{
+    REQUIRE_READY(h);
+    REQUIRE_SINGLE(h);
+    REQUIRE_LEVEL(h, level);
+    if (degree < 0 || degree > kChebyMaxDegree) return fail(SPARSH_EINVAL, "degree must be 0..16");
+    Engine &E = *h->eng;
+    const size_t n = (size_t)E.level(level).n;
+    DBuf db(E, n, b), dx(E, n, x), dt(E, n);
+    if (!db.p || !dx.p || !dt.p) return fail(SPARSH_ENODEV, E.error);
+    if (x_is_zero && degree == 0) launch_fill((int)n, 0.0, dx.p, E.stream());
+    if (!E.op_cheby(level, db.p, dx.p, dt.p, degree, x_is_zero != 0)) return fail(E.fault() != SPARSH_OK ? E.fault() : SPARSH_ENUMERIC, E.error);
+    return done(E, dx.get(x));
+}
+
 int sparsh_op_residual(sparsh_handle h, int level, const double *b, const double *x, double *r)
 {
     REQUIRE_READY(h);
@@ -1452,13 +1505,15 @@ int sparsh_bench_op(sparsh_handle h, int op, int level, int reps, double *avg_se
             a.partial = E.partials();
             launch_box1(L.A, 1, a, L.fine, st);
         } break;
+        case 17: E.cheby_bench_step(level); break;
         case 13: E.gmres_bench_step(true); break;
         case 14: E.gmres_bench_step(false); break;
         case 15: E.gmres_bench_step(true); break;  // (the handle's float basis)
         default: break;
         }
     };
-    if (op < 0 || op > 16) return fail(SPARSH_EINVAL, "unknown op");
+    if (op < 0 || op > 17) return fail(SPARSH_EINVAL, "unknown op");
+    if (op == 17 && (E.distributed() || !E.build_cheby_level(level))) return fail(SPARSH_ESTATE, "no Chebyshev bounds on this handle");
     if (op == 13 || op == 14 || op == 15) {
         if (level != 0 || E.distributed()) return fail(SPARSH_EINVAL, "the GMRES orthogonalisation step runs on level 0 of a single-GPU handle");
         if ((op == 15) != (E.gmres_basis() == SPARSH_BASIS_FP32))
@@ -1470,7 +1525,7 @@ int sparsh_bench_op(sparsh_handle h, int op, int level, int reps, double *avg_se
     if (op == 16 && (E.distributed() || !box1_applies(L.A, E.kernel_cfg()))) return fail(SPARSH_ESTATE, "the level does not run the plane-marching kernel (sparsh_level_marching_ops)");
     // (the ops on the level's own buffers, 10, 11 and 16: ones as the right-hand side, as in Engine::tune_box_kernels -- on zeros every quotient
     // of div_const takes the plain-division branch)
-    if (op == 10 || op == 11 || op == 16) launch_fill(L.n, 1.0, L.r, st);
+    if (op == 10 || op == 11 || op == 16 || op == 17) launch_fill(L.n, 1.0, L.r, st);
     for (int i = 0; i < 3; ++i) run();
     hipEvent_t e0, e1;
     (void)hipEventCreate(&e0);
@@ -1483,7 +1538,7 @@ int sparsh_bench_op(sparsh_handle h, int op, int level, int reps, double *avg_se
     (void)hipEventElapsedTime(&ms, e0, e1);
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
-    if (op == 10 || op == 11 || op == 16) {
+    if (op == 10 || op == 11 || op == 16 || op == 17) {
         (void)hipMemsetAsync(L.x, 0, n * 8, st);
         (void)hipMemsetAsync(L.x2, 0, n * 8, st);
         (void)hipMemsetAsync(L.r, 0, n * 8, st);

@@ -499,6 +499,7 @@ int Engine::setup_host(const sparsh_params &p)
     host_ready_ = false;
     colors_.clear();
     sor_.clear();
+    cheb_.clear();
     SetupParams sp;
     sp.max_levels = p.max_levels;
     sp.limit_upper = p.limit_upper;
@@ -545,6 +546,8 @@ int Engine::setup_host(const sparsh_params &p)
     host_ready_ = true;
     if (sor_on())  // the smoother was chosen before the setup: colour every level now
         for (int l = 0; l < (int)H_.levels.size(); ++l) level_colors(l);
+    if (cheby_on())  // likewise: the spectral bounds of every smoothed level
+        for (int l = 0; l + 1 < (int)H_.levels.size(); ++l) level_cheby(l);
     return SPARSH_OK;
 }
 
@@ -1198,6 +1201,7 @@ int Engine::setup(const sparsh_params &p)
     gm_basisf_ = nullptr;
     gm_bytes_ = 0;
     sor_.clear();
+    cheb_.clear();  // (the d vectors are freed with the rest)
     coarse_.release();
     if (!comm_) comm_ = make_self_comm();
     const int G = comm_->size, me = comm_->rank;
@@ -1462,6 +1466,7 @@ int Engine::setup(const sparsh_params &p)
             return SPARSH_ENODEV;
     }
     if (sor_on() && !dist_ && !p.precond_fp32 && !build_sor_layouts()) return SPARSH_ENODEV;  // (otherwise refused at the solve)
+    if (cheby_on() && !dist_ && !p.precond_fp32 && cheby_prepare() != SPARSH_OK) return SPARSH_ENODEV;
     if (!check(hipStreamSynchronize(st_), "setup sync")) return SPARSH_ENODEV;
     if (!comm_->barrier(st_)) {
         error = "comm barrier after setup failed: " + comm_->error;
@@ -2141,11 +2146,197 @@ void Engine::vcycle_sor(const double *b0, bool x0_zero, double *dot_partial, int
     if (dot_partial) launch_dot(lev_[0].n, lev_[0].x, b0, dot_partial, dot_nblk, st_);
 }
 
+// ---------------------------------------------------------------------------- Chebyshev polynomial smoother
+
+void Engine::set_chebyshev(double ratio, int steps)
+{
+    cheby_ratio_ = ratio;
+    if (steps != cheby_steps_)
+        for (ChebyLevel &c : cheb_) c.have = false;
+    cheby_steps_ = steps;
+    config_changed();  // the coefficients are constants of a captured iteration
+}
+
+const ChebyLevel &Engine::level_cheby(int l)
+{
+    if (cheb_.size() != H_.levels.size()) cheb_.assign(H_.levels.size(), ChebyLevel());
+    ChebyLevel &c = cheb_[l];
+    if (!c.have) {
+        const HostLevel &h = H_.levels[l];
+        const int nthreads = prm_.host_threads > 0 ? prm_.host_threads : effective_cpus();
+        const int before = omp_get_max_threads();
+        omp_set_num_threads(std::max(1, nthreads));
+        c.est = cheby_bounds(h.A.nrow, h.A.rowptr, h.A.col, h.A.val, h.diag.data(), cheby_steps_);
+        omp_set_num_threads(before);
+        c.have = true;
+    }
+    return c;
+}
+
+void Engine::set_cheby_lmax(int l, double lmax)
+{
+    if (cheb_.size() != H_.levels.size()) cheb_.assign(H_.levels.size(), ChebyLevel());
+    cheb_[l].forced = lmax;
+    config_changed();
+}
+
+bool Engine::build_cheby_level(int l)
+{
+    const ChebyLevel &c = level_cheby(l);
+    if (!(c.lmax() > 0.0) || !std::isfinite(c.lmax())) {
+        error = "Chebyshev smoother: level " + std::to_string(l) + " has no positive finite upper bound of its spectrum";
+        return false;
+    }
+    if (!cheb_[l].d) {
+        const size_t bytes = (size_t)lev_[l].n * 8;
+        double *d = static_cast<double *>(dalloc(bytes));
+        if (!d || !check(hipMemsetAsync(d, 0, bytes, st_), "hipMemsetAsync")) return false;
+        cheb_[l].d = d;
+    }
+    return true;
+}
+
+int Engine::cheby_prepare()
+{
+    if (!cheby_on()) return SPARSH_OK;
+    if (dist_) {
+        error = "the Chebyshev smoother is not available on a partitioned (multi-GPU) handle";
+        return SPARSH_EINVAL;
+    }
+    if (prm_.precond_fp32) {
+        error = "the Chebyshev smoother has no fp32 hierarchy: unset params.precond_fp32";
+        return SPARSH_EINVAL;
+    }
+    for (int l = 0; l + 1 < (int)lev_.size(); ++l)
+        if (!build_cheby_level(l)) {
+            if (fault_ != SPARSH_OK) return fault_;
+            const double lm = cheb_[l].lmax();
+            return lm > 0.0 && std::isfinite(lm) ? SPARSH_ENODEV : SPARSH_ENUMERIC;
+        }
+    return SPARSH_OK;
+}
+
+// x_{k+1} = x_k + d_k, d_k = c1_k d_{k-1} + c2_k D^-1 (b - A x_k): one launch per step, the iterate ping-ponging through L.x / L.x2 as
+// under Jacobi, d updated in place.  From a zero guess x_1 = d_0 = c2_0 b / d is the zero-guess Jacobi launch with omega = c2_0, and
+// step 1 reads its d_0 from the iterate.
+void Engine::cheby_leg(int l, const double *b, bool x_zero, int degree, double *dot_partial, int *dot_nblk)
+{
+    if (degree <= 0) {
+        if (dot_partial) launch_dot(lev_[l].n, lev_[l].x, b, dot_partial, dot_nblk, st_);
+        return;
+    }
+    if (l < 0 || l >= (int)cheb_.size() || !cheb_[l].d || !cheb_[l].have) {
+        // every caller builds the level's state first (cheby_prepare / build_cheby_level)
+        error = "Chebyshev step on level " + std::to_string(l) + " without its bounds and correction vector";
+        if (fault_ == SPARSH_OK) fault_ = SPARSH_ESTATE;
+        return;
+    }
+    DevLevel &L = lev_[l];
+    double c1[kChebyMaxDegree], c2[kChebyMaxDegree];
+    cheby_coefficients(cheb_[l].lmax(), cheby_ratio_, std::min(degree, kChebyMaxDegree), c1, c2);
+    double *dvec = cheb_[l].d;
+    int k = 0;
+    bool dot_done = false;
+    const double *dprev = nullptr;
+    if (x_zero) {
+        launch_jacobi_zero(L.n, b, diag_stream(L), L.diag_const, c2[0], L.x, st_);
+        dprev = L.x;
+        k = 1;
+    }
+    for (; k < degree; ++k) {
+        CsrArgs a;
+        a.x = L.x;
+        a.b = b;
+        a.d = L.diag;
+        a.y = L.x2;
+        a.y2 = dvec;
+        a.dprev = dprev;
+        a.beta = c1[k];
+        a.omega = c2[k];
+        a.reverse = csr_alternates(L.A, cfg_) && (k & 1) == 0;
+        CsrOp op = OP_CHEBY;
+        if (k == degree - 1 && dot_partial) {
+            op = OP_CHEBY_DOT;
+            a.partial = dot_partial;
+            dot_done = true;
+        }
+        const int np = apply_A(L, op, a);
+        if (op == OP_CHEBY_DOT) *dot_nblk = np;
+        std::swap(L.x, L.x2);
+        dprev = dvec;
+    }
+    if (dot_partial && !dot_done) launch_dot(L.n, L.x, b, dot_partial, dot_nblk, st_);
+}
+
+bool Engine::op_cheby(int l, const double *b, double *x, double *tmp, int degree, bool x_is_zero)
+{
+    if (!build_cheby_level(l)) return false;
+    DevLevel &L = lev_[l];
+    double *sx = L.x, *sx2 = L.x2;
+    L.x = x;
+    L.x2 = tmp;
+    cheby_leg(l, b, x_is_zero, degree, nullptr, nullptr);
+    if (L.x != x) launch_copy(L.n, L.x, x, st_);
+    L.x = sx;
+    L.x2 = sx2;
+    return true;
+}
+
+void Engine::cheby_bench_step(int l)
+{
+    DevLevel &L = lev_[l];
+    double c1[2], c2[2];
+    cheby_coefficients(cheb_[l].lmax(), cheby_ratio_, 2, c1, c2);
+    CsrArgs a;
+    a.x = (cheby_flip_ & 1) ? L.x2 : L.x;
+    a.y = (cheby_flip_ & 1) ? L.x : L.x2;
+    a.b = L.r;
+    a.d = L.diag;
+    a.y2 = cheb_[l].d;
+    a.dprev = cheb_[l].d;
+    a.beta = c1[1];
+    a.omega = c2[1];
+    a.reverse = csr_alternates(L.A, cfg_) && (cheby_flip_ & 1);
+    ++cheby_flip_;
+    launch_csr(L.A, OP_CHEBY, a, L.fine, st_, cfg_);
+}
+
+// The Jacobi cycle's hierarchy and order of operations with plain residual, restriction, coarse-solve and prolongation launches, as
+// vcycle_sor; the smoothing legs are Chebyshev polynomials of the handle's degree.
+void Engine::vcycle_cheby(const double *b0, bool x0_zero, double *dot_partial, int *dot_nblk)
+{
+    const int last = (int)lev_.size() - 1;
+    const int m = cheby_degree();
+    lev_[0].b = const_cast<double *>(b0);
+    if (last == 0) {
+        op_coarse(b0, lev_[0].x);
+        if (dot_partial) launch_dot(lev_[0].n, lev_[0].x, b0, dot_partial, dot_nblk, st_);
+        return;
+    }
+    for (int l = 0; l < last; ++l) {
+        DevLevel &L = lev_[l];
+        cheby_leg(l, L.b, l > 0 || x0_zero, m, nullptr, nullptr);  // coarse levels start from x = 0
+        op_residual(l, L.b, L.x, L.r);                             // store_residual
+        op_restrict(l, L.r, lev_[l + 1].b, false);                 // transfer_residual
+    }
+    op_coarse(lev_[last].b, lev_[last].x);
+    for (int l = last; l > 0; --l) {
+        DevLevel &F = lev_[l - 1];
+        op_prolong(l - 1, lev_[l].x, F.x);  // transfer_solution
+        const bool want_dot = (l - 1 == 0) && dot_partial;
+        cheby_leg(l - 1, F.b, false, m, want_dot ? dot_partial : nullptr, dot_nblk);
+    }
+}
+
 // One V(nu,nu) cycle (body of the while loops in AMG_solve_jacobi, src/AMG_phases.cpp:198-216).
 void Engine::vcycle(const double *b0, bool x0_zero, double *dot_partial, int *dot_nblk, bool zero_done0)
 {
     if (sor_on()) {
         vcycle_sor(b0, x0_zero, dot_partial, dot_nblk);
+        return;
+    }
+    if (cheby_on()) {
+        vcycle_cheby(b0, x0_zero, dot_partial, dot_nblk);
         return;
     }
     const int last = (int)lev_.size() - 1;
@@ -2220,7 +2411,7 @@ void Engine::vcycle(const double *b0, bool x0_zero, double *dot_partial, int *do
 int Engine::amg_solve_dev(const double *b, double *x, int iterations, double *hist, int hist_cap, int *ncycles)
 {
     if (!ready_) return SPARSH_ESTATE;
-    if (int rc = sor_prepare(); rc != SPARSH_OK) return rc;
+    if (int rc = smoother_prepare(); rc != SPARSH_OK) return rc;
     DevLevel &L0 = lev_[0];
     const int n = L0.n;
     HIPCHK(hipMemcpyAsync(L0.x, x, (size_t)n * 8, hipMemcpyDeviceToDevice, st_));
@@ -2272,7 +2463,7 @@ int Engine::pcg_smoother_check()
         error = "SPARSH_PCG needs a symmetric preconditioner: the SOR smoother must use SPARSH_SOR_SYMMETRIC";
         return SPARSH_EINVAL;
     }
-    return sor_prepare();
+    return smoother_prepare();
 }
 
 int Engine::pcg_init(const double *b, double *x, bool precond)
@@ -2330,7 +2521,7 @@ void Engine::pcg_body(bool precond, int slot)
     // are reduced together with z.r after the V-cycle: one finalize launch (one all-reduce) less
     // with the fp64 V-cycle behind it the update also writes the cycle's zero-guess sweep of level 0 (z0 = omega r / d)
     // (... unless the cycle's first launch on level 0 is the three-sweep one, which reads r alone)
-    const bool fuse_zero = cfg_.fuse_cg_zero && precond && !f32_ready_ && !sor_on() && lev_.size() > 1 && !lev_[0].deep && prm_.sweeps > 0 &&
+    const bool fuse_zero = cfg_.fuse_cg_zero && precond && !f32_ready_ && !sor_on() && !cheby_on() && lev_.size() > 1 && !lev_[0].deep && prm_.sweeps > 0 &&
                            !(prm_.sweeps >= 3 && zero_start(lev_[0]));
     // with the fp64 V-cycle behind it x += alpha p waits for the direction update at the end of this iteration (one read of p for both)
     const bool defer_x = cfg_.defer_x && precond && !f32_ready_;
@@ -2452,7 +2643,7 @@ int Engine::pcg(const double *b, double *x, int max_iters, double *hist, int his
 int Engine::bicg(const double *b, double *x, int max_iters, double *hist, int hist_cap, int *iters, bool precond)
 {
     if (precond)
-        if (int rc = sor_prepare(); rc != SPARSH_OK) return rc;
+        if (int rc = smoother_prepare(); rc != SPARSH_OK) return rc;
     const int n = lev_[0].n;
     double *r0 = work_[0], *r = work_[1], *p = work_[2], *Ap = work_[3], *s = work_[4], *As = work_[5], *p1buf = work_[6];
     int nb = 0;
@@ -2526,7 +2717,7 @@ int Engine::bicg(const double *b, double *x, int max_iters, double *hist, int hi
 // z = M r, the preconditioner of SPARSH_PBICG / SPARSH_PGMRES: one V-cycle of the current smoother from a zero guess, or the fp32 cycle.
 int Engine::op_precond(const double *r, double *z)
 {
-    if (int rc = sor_prepare(); rc != SPARSH_OK) return rc;
+    if (int rc = smoother_prepare(); rc != SPARSH_OK) return rc;
     int nb = 0;
     if (f32_ready_) {
         vcycle_f32(r, z, part0_, &nb);
@@ -2651,7 +2842,7 @@ int Engine::gmres(const double *b, double *x, int max_iters, double *hist, int h
         return SPARSH_EINVAL;
     }
     if (precond)
-        if (int rc = sor_prepare(); rc != SPARSH_OK) return rc;
+        if (int rc = smoother_prepare(); rc != SPARSH_OK) return rc;
     if (int rc = gmres_reserve(); rc != SPARSH_OK) return rc;
     const int n = lev_[0].n, m = gm_restart_;
     const bool f32b = gm_prec_ == SPARSH_BASIS_FP32;

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/sparsh_amg.h"
+#include "cheby_bounds.hpp"
 #include "coarse.hpp"
 #include "comm.hpp"
 #include "dist.hpp"
@@ -61,6 +62,16 @@ struct SorLevel {
     bool nt = false;      // the per-colour launches stream the matrix past the caches (level larger than the Infinity Cache)
     bool single = false;  // small level: a whole leg is one launch (launch_sor_level)
     size_t bytes = 0;     // device bytes of the layout
+};
+
+// Chebyshev smoother state of one level: the spectral bounds (host, computed on first use after setup_host) and the
+// correction vector d of the three-term recurrence (device, allocated on first use after setup)
+struct ChebyLevel {
+    bool have = false;    // est holds the bounds of the current hierarchy and Lanczos step count
+    ChebyBounds est;
+    double forced = 0.0;  // > 0: the caller's upper bound (sparsh_set_chebyshev_lmax) replaces est.lmax
+    double *d = nullptr;
+    double lmax() const { return forced > 0.0 ? forced : est.lmax; }
 };
 
 struct KrylovState {
@@ -117,7 +128,8 @@ public:
     const CoarseSolver &coarse() const { return coarse_; }
     CoarseSolver &coarse_mut() { return coarse_; }
     const sparsh_params &params() const { return prm_; }
-    // ---- smoother (SPARSH_SMOOTH_JACOBI default / SPARSH_SMOOTH_SOR): sweeps 0 = default (params.sweeps / 6)
+    // ---- smoother (SPARSH_SMOOTH_JACOBI default / SPARSH_SMOOTH_SOR / SPARSH_SMOOTH_CHEBYSHEV): sweeps 0 = default (params.sweeps / 6 /
+    // degree 4)
     void set_smoother(int kind, int sweeps, int order);
     int smoother() const { return smoother_; }
     bool sor_on() const { return smoother_ == SPARSH_SMOOTH_SOR; }
@@ -137,6 +149,28 @@ public:
     bool op_sor(int l, const double *b, double *x, int sweeps, bool reverse, bool x_is_zero);
     bool build_sor_layouts();     // layouts of the smoothed levels (all but the coarsest); no-op once built for the current setup
     bool build_sor_level(int l);  // layout of level l alone (op_sor / bench on any level, the coarsest included)
+    // ---- Chebyshev polynomial smoother (cheby_bounds.hpp)
+    bool cheby_on() const { return smoother_ == SPARSH_SMOOTH_CHEBYSHEV; }
+    int cheby_degree() const { return sm_sweeps_ > 0 ? sm_sweeps_ : kChebyDefaultDegree; }
+    double cheby_ratio() const { return cheby_ratio_; }
+    int cheby_steps() const { return cheby_steps_; }
+    void set_chebyshev(double ratio, int steps);  // a changed step count drops the computed bounds
+    // bounds of level l (host; computed on first use after setup_host -- at the setup for the smoothed levels, every level but the
+    // coarsest, when Chebyshev was selected before it; the coarsest level's serve op_cheby and the bench alone)
+    const ChebyLevel &level_cheby(int l);
+    void set_cheby_lmax(int l, double lmax);  // 0: back to the estimate
+    // bounds and d vectors ready for a solve on this handle; SPARSH_* code
+    int cheby_prepare();
+    bool build_cheby_level(int l);  // bounds + d vector of level l alone (op_cheby / bench)
+    // one leg of `degree` steps on level l: iterate in lev_[l].x on entry and exit (x_zero: taken as 0, not read), lev_[l].x2 is scratch;
+    // dot_partial: the last step also leaves the partial sums of x.b there
+    void cheby_leg(int l, const double *b, bool x_zero, int degree, double *dot_partial, int *dot_nblk);
+    // the same as a test hook on caller vectors, whatever the smoother; false if the level's state cannot be built
+    bool op_cheby(int l, const double *b, double *x, double *tmp, int degree, bool x_is_zero);
+    // bench: one step of the k >= 1 form on the level's resident buffers (x, x2, d; r as the right-hand side)
+    void cheby_bench_step(int l);
+    // both of the above for whichever smoother is selected (every solver entry calls it)
+    int smoother_prepare() { return cheby_on() ? cheby_prepare() : sor_prepare(); }
     static constexpr int kSorDefaultSweeps = 6;  // AMG_solve_SOR's count (src/AMG_phases.cpp:252)
     // levels with at most this many entries run a leg as one launch: 0, the single launch was slower than the per-colour launches on
     // every level measured on the MI355X, down to 3 774 rows / 25 940 entries
@@ -322,6 +356,12 @@ private:
 
     // one V(nu,nu) cycle with the SOR smoother: the Jacobi cycle's order of operations without any fused Jacobi step
     void vcycle_sor(const double *b0, bool x0_zero, double *dot_partial, int *dot_nblk);
+    // ... with the Chebyshev smoother: likewise, the last post-smoothing step of level 0 carrying the dot (OP_CHEBY_DOT)
+    void vcycle_cheby(const double *b0, bool x0_zero, double *dot_partial, int *dot_nblk);
+    std::vector<ChebyLevel> cheb_;  // per level (empty until first use)
+    double cheby_ratio_ = kChebyDefaultRatio;
+    int cheby_steps_ = kChebyDefaultSteps;
+    int cheby_flip_ = 0;  // cheby_bench_step
     void adopt_sweeps();
     int pcg_smoother_check();  // SPARSH_PCG under the current smoother: symmetric SOR order, layouts built  // prm_.sweeps = the Jacobi sweep count this handle's smoother selection asks for
     int smoother_ = SPARSH_SMOOTH_JACOBI;

@@ -115,13 +115,15 @@ __device__ __forceinline__ int ld_stream(const int *p)
 //  * sell_kernel (kind 2): sliced-ELL mirror, lane = row, no LDS: every load of a wave is one
 //    contiguous segment (and for stencil matrices so is the x gather).
 
-constexpr bool op_needs_b(int OP) { return OP == OP_RESID || OP == OP_JACOBI || OP == OP_JACOBI_DOT || OP == OP_RESNORM || OP == OP_RESID_PAIR || OP == OP_JACOBI_PROLONG; }
-constexpr bool op_needs_d(int OP) { return OP == OP_JACOBI || OP == OP_JACOBI_DOT || OP == OP_JACOBI_PROLONG; }
-constexpr bool op_needs_xi(int OP) { return OP == OP_JACOBI || OP == OP_JACOBI_DOT || OP == OP_SPMV_DOT || OP == OP_JACOBI_PROLONG; }
-constexpr bool op_reduces(int OP) { return OP == OP_SPMV_DOT || OP == OP_RESNORM || OP == OP_JACOBI_DOT; }
+constexpr bool op_is_cheby(int OP) { return OP == OP_CHEBY || OP == OP_CHEBY_DOT; }
+constexpr bool op_needs_b(int OP) { return OP == OP_RESID || OP == OP_JACOBI || OP == OP_JACOBI_DOT || OP == OP_RESNORM || OP == OP_RESID_PAIR || OP == OP_JACOBI_PROLONG || op_is_cheby(OP); }
+constexpr bool op_needs_d(int OP) { return OP == OP_JACOBI || OP == OP_JACOBI_DOT || OP == OP_JACOBI_PROLONG || op_is_cheby(OP); }
+constexpr bool op_needs_xi(int OP) { return OP == OP_JACOBI || OP == OP_JACOBI_DOT || OP == OP_SPMV_DOT || OP == OP_JACOBI_PROLONG || op_is_cheby(OP); }
+constexpr bool op_reduces(int OP) { return OP == OP_SPMV_DOT || OP == OP_RESNORM || OP == OP_JACOBI_DOT || OP == OP_CHEBY_DOT; }
 
 struct RowOperands {
     double bi = 0.0, di = 1.0, xi = 0.0;
+    double pi = 0.0;  // CHEBY: the previous step's correction of this row
 };
 
 // LOAD_D = false: the kernel picks the diagonal out of the matrix stream it reads anyway (the
@@ -134,6 +136,8 @@ __device__ __forceinline__ RowOperands load_row_operands(const CsrArgs &a, int r
     if constexpr (op_needs_d(OP) && LOAD_D) o.di = a.d[row];
     if constexpr (op_needs_d(OP) && !LOAD_D) o.di = 0.0;  // a row without a diagonal entry keeps diag[] = 0
     if constexpr (op_needs_xi(OP) && LOAD_XI) o.xi = a.x[row];
+    if constexpr (op_is_cheby(OP))
+        if (a.dprev) o.pi = a.dprev[row];  // launch-uniform: the first step of a leg has no previous correction
     return o;
 }
 
@@ -150,6 +154,14 @@ __device__ __forceinline__ double row_epilogue(const CsrArgs &a, int row, double
         const double xn = o.xi + a.omega * h / o.di;
         a.y[row] = xn;
         if constexpr (OP == OP_JACOBI_DOT) return xn * o.bi;
+    } else if constexpr (op_is_cheby(OP)) {
+        const double h = 1.0 * o.bi + (-1.0) * sum;
+        const double t = a.omega * h / o.di;
+        const double dn = a.dprev ? a.beta * o.pi + t : t;
+        const double xn = o.xi + dn;
+        a.y[row] = xn;
+        a.y2[row] = dn;
+        if constexpr (OP == OP_CHEBY_DOT) return xn * o.bi;
     } else if constexpr (OP == OP_JACOBI_PROLONG) {
         const double h = 1.0 * o.bi + (-1.0) * sum;
         const double xn = o.xi + a.omega * h / o.di;
@@ -272,6 +284,44 @@ __device__ __forceinline__ double row_sum_lds(const double *__restrict__ prod, i
     return sum;
 }
 
+// One long row (more products than the LDS buffer holds) with the products added in stored order: parked chunk by chunk by all `nthr`
+// threads, added by thread 0.  The Chebyshev ops use it, so that a step is the stated arithmetic on every row; the older ops keep the
+// strided, tree-combined partial sums they have always had on such a row.  WAVE: the threads are one wave (no workgroup barrier).
+// dv (may be nullptr): the row's diagonal entry, for the kernels that pick it out of the stream; valid in thread 0.
+template <bool NT, bool WAVE>
+__device__ __forceinline__ double long_row_ordered(const int *__restrict__ col, const double *__restrict__ val, const double *__restrict__ x,
+                                                   int j0, int j1, int t, int nthr, double *__restrict__ prod, int cap, int row, double *dv)
+{
+    double sum = 0.0, d = 0.0;
+    for (int c0 = j0; c0 < j1; c0 += cap) {
+        const int c1 = c0 + cap < j1 ? c0 + cap : j1;
+        for (int j = c0 + t; j < c1; j += nthr) {
+            const int c = ld_stream<NT>(col + j);
+            const double v = ld_stream<NT>(val + j);
+            prod[j - c0] = v * x[c];
+            if (c == row && d == 0.0) d = v;
+        }
+        if constexpr (WAVE) {
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        } else {
+            __syncthreads();
+        }
+        if (t == 0)
+            for (int k = 0; k < c1 - c0; ++k) sum += prod[k];
+        if constexpr (WAVE) {
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        } else {
+            __syncthreads();
+        }
+    }
+    if (dv) *dv = d;
+    return sum;
+}
+
 // TAG: 1 for launches on the finest level.  Identical code; a distinct symbol lets profiler
 // summaries (rocprofv3 --stats) separate the dominant finest-level launches from coarse ones.
 template <int OP, bool NT, int VEC, int TAG>
@@ -306,7 +356,10 @@ __global__ __launch_bounds__(kBlock) void csr_block_kernel(const int *__restrict
 
     double sum = 0.0;
     bool store = has_row;
-    if (nrows == 1 && j1 - j0 > kStreamNnz) {  // one long row: strided partial sums, tree-combined
+    if (nrows == 1 && j1 - j0 > kStreamNnz && op_is_cheby(OP)) {  // one long row, stored order
+        sum = long_row_ordered<NT, false>(col, val, x, j0, j1, tid, kBlock, prod, kStreamNnz, r0, nullptr);
+        store = (tid == 0);
+    } else if (nrows == 1 && j1 - j0 > kStreamNnz) {  // one long row: strided partial sums, tree-combined
         double part = 0.0;
         for (int j = j0 + tid; j < j1; j += kBlock) part += ld_stream<NT>(val + j) * x[ld_stream<NT>(col + j)];
         part = block_sum(part, red);
@@ -453,7 +506,13 @@ __device__ __forceinline__ void csr_rowlane_body(const int *__restrict__ rowblk,
     }
     double sum = 0.0;
     bool store = has_row;
-    if (nrows == 1 && j1 - j0 > kStreamNnz) {  // one long row: strided partial sums, tree-combined (as csr_block_kernel)
+    if (nrows == 1 && j1 - j0 > kStreamNnz && op_is_cheby(OP)) {  // one long row, stored order (as csr_block_kernel)
+        double dv = 0.0, dsum = 0.0;
+        sum = long_row_ordered<NT, false>(col, val, x, j0, j1, tid, kBlock, sval, kStreamNnz, r0, &dv);
+        dsum = block_sum(dv, red);  // the thread that met the diagonal entry holds it (others 0): an exact sum, valid in thread 0
+        o.di = dsum;
+        store = (tid == 0);
+    } else if (nrows == 1 && j1 - j0 > kStreamNnz) {  // one long row: strided partial sums, tree-combined (as csr_block_kernel)
         double part = 0.0, dv = 0.0;
         for (int j = j0 + tid; j < j1; j += kBlock) {
             const int c = ld_stream<NT>(col + j);
@@ -529,7 +588,10 @@ __global__ __launch_bounds__(kBlock) void csr_wave_kernel(const int *__restrict_
         }
         double sum = 0.0;
         bool store = has_row;
-        if (nrows == 1 && j1 - j0 > kWaveNnz) {
+        if (nrows == 1 && j1 - j0 > kWaveNnz && op_is_cheby(OP)) {
+            sum = long_row_ordered<NT, true>(col, val, x, j0, j1, lane, 64, prod, kWaveNnz, r0, nullptr);
+            store = (lane == 0);
+        } else if (nrows == 1 && j1 - j0 > kWaveNnz) {
             double part = 0.0;
             for (int j = j0 + lane; j < j1; j += 64) part += ld_stream<NT>(val + j) * x[ld_stream<NT>(col + j)];
             sum = wave_sum(part);
@@ -2573,6 +2635,8 @@ int launch_csr(const DevCsr &A, CsrOp op, const CsrArgs &a, bool finest, hipStre
     case OP_RESNORM: return launch_csr_op<OP_RESNORM>(A, a, finest, st, cfg);
     case OP_JACOBI_DOT: return launch_csr_op<OP_JACOBI_DOT>(A, a, finest, st, cfg);
     case OP_JACOBI_PROLONG: return launch_csr_op<OP_JACOBI_PROLONG>(A, a, finest, st, cfg);
+    case OP_CHEBY: return launch_csr_op<OP_CHEBY>(A, a, finest, st, cfg);
+    case OP_CHEBY_DOT: return launch_csr_op<OP_CHEBY_DOT>(A, a, finest, st, cfg);
     case OP_RESID_PAIR: break;  // table kernel only: launch_resid_pair
     }
     return 0;

@@ -156,6 +156,9 @@ enum CsrOp : int {
     OP_JACOBI_PROLONG = 8, // Jacobi sweep whose result is not stored but added to the finer level's iterate: y2_f = 1.0*xn_i + y2_f
                            // for the (at most two) fine rows f of aggregate i -- the last post-sweep of a level and
                            // transfer_solution into the level above in one launch (aggregation P only: every fine row has one owner)
+    OP_CHEBY = 9,     // one Chebyshev step: dn_i = beta*dprev_i + (omega*(b_i - s_i))/d_i (dprev == nullptr: the first step of a leg,
+                      // dn_i = (omega*(b_i - s_i))/d_i) ; y_i = x_i + dn_i ; y2_i = dn_i   (y != x; dprev may be y2 or x)
+    OP_CHEBY_DOT = 10, // the same ; partial += y_i*b_i                 (last post-smoothing step of PCG: z.r)
     OP_RESID_PAIR = 7  // levels whose aggregates are the row pairs (2J, 2J+1): y_J = (b - s)_2J + (b - s)_2J+1 and
                        // y2_J = omega*y_J/d_J -- residual, restriction and the coarse level's zero-guess sweep in one
                        // launch (table kernel only: launch_resid_pair)
@@ -166,12 +169,15 @@ struct CsrArgs {
     const double *b = nullptr;   // rhs (RESID/JACOBI/RESNORM)
     const double *d = nullptr;   // diagonal (JACOBI)
     double *y = nullptr;         // output
-    double *y2 = nullptr;        // second output (RESID_PAIR: the coarse level's zero-guess sweep; d is then the coarse diagonal;
+    double *y2 = nullptr;        // second output (CHEBY: the step's correction dn; RESID_PAIR: the coarse level's zero-guess sweep; d is then the coarse diagonal;
                                  // JACOBI_PROLONG: the finer level's iterate)
     double dconst = 0.0;         // RESID_PAIR with d == nullptr: the coarse level's constant diagonal
     const int *members = nullptr; // JACOBI_PROLONG: two fine rows per row (second -1 for a single); nullptr = rows (2i, 2i+1)
     int nfine = 0;                // JACOBI_PROLONG: rows of the finer level
-    double omega = 0.0;
+    double omega = 0.0;          // (CHEBY: the step's coefficient c2)
+    const double *dprev = nullptr; // CHEBY: the previous step's correction (entry i is read by row i alone: may alias y2, or x after a
+                                   // zero-guess step, whose iterate is its correction); nullptr on the first step of a leg
+    double beta = 0.0;           // CHEBY: the step's coefficient c1
     double *partial = nullptr;   // per-block partial sums (reductions), size >= nblk
     // optional subset launch of the sliced kernels (multi-GPU overlap): process only the slices
     // listed, write reduction partials from index partial_off on

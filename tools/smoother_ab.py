@@ -3,6 +3,12 @@ SOR layout's byte model, per-sweep timings of both SOR launch paths per level an
 
     python tools/smoother_ab.py [--problems p216,p216_noconst,p216_csr,fem,c0] [--tol 1e-8] [--reps 3] [--out FILE]
     python tools/smoother_ab.py --sweep-only [--problems p216] [--reps 200]   # level-0 SOR sweeps alone (run under rocprofv3)
+    python tools/smoother_ab.py --chebyshev [--problems p216_noconst,p216_csr,fem,p216] [--reps 3] [--out FILE]
+
+--chebyshev: Jacobi (the default sweep count) against the Chebyshev smoother of degree 4 and 6 inside PCG, the solves alternating
+in one process after a warm-up; one Chebyshev step against one Jacobi sweep on the finest level's resident buffers (bench_op 17
+against 10, alternating repeats) beside the byte model's expectation (+16 B per row: the correction vector read and written); and
+the host time of the spectral-bound estimate beside the setup's.
 
 One handle per problem; the smoother is switched on it between timed solves (sparsh_set_smoother; the SOR layouts are built at
 the first SOR solve).  Times are HIP-event times of whole solves on device vectors (sparsh_solve_dev), best of --reps after
@@ -84,12 +90,72 @@ def cycle_launches(A, single):
     return total + smooth + 1, smooth  # + the dot product of z.r
 
 
+def jacobi_sweep_bytes(A, level):
+    """bytes one Jacobi sweep of the level streams under the kernel it launches (the layout models of csr_placement)"""
+    li = A.level_info(level)
+    n, nnz = li["nrow"], li["nnz"]
+    k = A.level_kernel(level)
+    if k == "sdia_tab_kernel":
+        return 24 * n + 68 * ((n + 63) // 64)
+    if k == "sdia_kernel":
+        return 8 * nnz + 24 * n + 24 * ((n + 63) // 64) * 8
+    if k == "sell_kernel":
+        return 12 * nnz + 28 * n
+    return (10 if k == "csr_rowlane16_kernel" else 12) * nnz + 36 * n
+
+
+def chebyshev_ab(A, name, b, args):
+    import time
+
+    n = A.nrow
+    rec = {"problem": name, "rows": n, "levels": A.nlevels, "level0_kernel": A.level_kernel(0), "setup_seconds": round(A.setup_seconds(), 3)}
+    t0 = time.perf_counter()
+    bounds = [A.level_chebyshev(l) for l in range(A.nlevels - 1)]
+    rec["bounds_seconds"] = round(time.perf_counter() - t0, 3)
+    rec["bounds"] = [{k: round(v, 5) for k, v in c.items()} for c in bounds]
+    # one step against one sweep on the finest level, alternating
+    A.set_smoother("chebyshev", 4)
+    A.op_precond(np.zeros(n))  # d vectors
+    t10, t17 = [], []
+    for _ in range(5):
+        t10.append(A.bench_op(10, 0, 50) * 1e6)
+        t17.append(A.bench_op(17, 0, 50) * 1e6)
+    jb = jacobi_sweep_bytes(A, 0)
+    rec["level0_jacobi_sweep_us"] = [round(t, 2) for t in t10]
+    rec["level0_chebyshev_step_us"] = [round(t, 2) for t in t17]
+    rec["step_over_sweep_measured"] = round(float(np.median(t17) / np.median(t10)), 4)
+    rec["step_over_sweep_byte_model"] = round((jb + 16 * n) / jb, 4)
+    rec["jacobi_sweep_model_bytes"] = int(jb)
+    print(rec, flush=True)
+    bd, xd = A.dev_alloc(8 * n), A.dev_alloc(8 * n)
+    A.h2d(bd, b)
+    configs = [("jacobi", 0), ("chebyshev", 4), ("chebyshev", 6)]
+    runs = {c: [] for c in configs}
+    for k in range(args.reps + 1):  # first round: warm-up
+        for c in configs:
+            A.set_smoother(c[0], c[1])
+            A.dev_fill(xd, n, 0.0)
+            h, it, sec, rc = A.solve_dev("pcg", bd, xd)
+            assert rc == 0, (c, rc)
+            if k > 0:
+                runs[c].append((len(h), sec))
+    for c in configs:
+        its = runs[c][0][0]
+        secs = [s for _, s in runs[c]]
+        rec[f"{c[0]}_{c[1]}"] = {"iterations": its, "time_to_solution_ms": [round(s * 1e3, 3) for s in secs],
+                                 "best_ms": round(min(secs) * 1e3, 3), "ms_per_iteration": round(min(secs) * 1e3 / its, 4)}
+        print(name, c, rec[f"{c[0]}_{c[1]}"], flush=True)
+    A.set_smoother("jacobi")
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--problems", default="p216,p216_noconst,p216_csr,fem,c0")
     ap.add_argument("--tol", type=float, default=1e-8)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--sweep-only", action="store_true")
+    ap.add_argument("--chebyshev", action="store_true")
     ap.add_argument("--levels-max-nnz", type=int, default=4_000_000, help="time the single-launch path on levels up to this nnz")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -104,6 +170,14 @@ def main():
             A.op_sor(0, np.zeros(n), np.zeros(n), 1)  # builds the layouts
             sec = A.bench_op("sor", 0, args.reps)
             print(json.dumps({"problem": name, "level0_sor_sweep_us": round(sec * 1e6, 2)}), flush=True)
+            A.close()
+            continue
+        if args.chebyshev:
+            rec = chebyshev_ab(A, name, b, args)
+            print(json.dumps(rec), flush=True)
+            if args.out:
+                with open(args.out, "a") as f:
+                    f.write(json.dumps(rec) + "\n")
             A.close()
             continue
         bd, xd = A.dev_alloc(8 * n), A.dev_alloc(8 * n)
