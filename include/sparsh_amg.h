@@ -416,6 +416,27 @@ int sparsh_op_precond(sparsh_handle h, const double *r, double *z);
 int sparsh_op_dot(sparsh_handle h, int n, const double *x, const double *y, double *out);
 int sparsh_op_nrm2(sparsh_handle h, int n, const double *x, double *out);
 int sparsh_op_axpby(sparsh_handle h, int n, double a, const double *x, double bcoef, double *y);
+/* Test hooks of the GMRES kernels.  They need a ready single-GPU handle for its stream and allocator only:
+ * n is free and independent of the handle's matrix.  V is the host basis V[nv][n] (row k = v_k); the device basis is laid out by the
+ * engine's own code (stride = n rounded up to 2 doubles / 4 floats; under SPARSH_BASIS_FP32 V is rounded to float on the host and
+ * zero-padded).  Bad arguments (NULL handle or array, n <= 0, nv outside 1..65, another precision) are SPARSH_EINVAL, device or not.
+ * sparsh_op_gs_dot: launch_gs_dot + launch_gs_finalize; sums[k] = v_k . w for k < nv, and sums[nv] = w . w when want_ww.
+ * sparsh_op_gs_update: launch_gs_update + launch_gs_finalize.  w_out = w_in - sum of coef[k] v_k, k ascending; w_in NULL: from 0;
+ * in_place: w_in and w_out are one device vector.  want_dots: sums[k] = v_k . w_out; want_ww: sums[nv] = w_out . w_out; sums has
+ * nv + 1 entries and those not asked for come back 0.  The device w_out holds `stride` elements, filled with `sentinel` before the
+ * launch; the *ntail (<= 3) elements behind row n come back in tail.
+ * sparsh_op_gs_scale: launch_gs_scale with the scalar d on the device.  SPARSH_BASIS_FP64: v = w / d in place (vd, tail unused,
+ * *ntail = 0).  SPARSH_BASIS_FP32: v = the float vector widened to double, vd = its fp64 copy, tail = the *ntail (<= 3) stored
+ * elements behind row n of the float vector.
+ * sparsh_op_gmres_small: launch_gmres_step for j = 0..m-1 on a freshly zeroed GmresState, then launch_gmres_solve(k), 0 <= k <= m <= 64.
+ * hcol / ccol: the two Gram-Schmidt coefficient columns, packed (column j has j + 1 entries, m (m + 1) / 2 in all); ww_partial[m][nblk]:
+ * the partial sums of w . w of step j.  Out: hist[m], R[64 * 64] (column j at R + 64 j), cs[64], sn[64], g[65], ny[64]. */
+int sparsh_op_gs_dot(sparsh_handle h, int n, int nv, int precision, const double *V, const double *w, int want_ww, double *sums);
+int sparsh_op_gs_update(sparsh_handle h, int n, int nv, int precision, const double *V, const double *coef, const double *w_in,
+                        int in_place, int want_dots, int want_ww, double sentinel, double *w_out, double *sums, double *tail, int *ntail);
+int sparsh_op_gs_scale(sparsh_handle h, int n, int precision, const double *w, double d, double *v, double *vd, double *tail, int *ntail);
+int sparsh_op_gmres_small(sparsh_handle h, int m, int nblk, const double *hcol, const double *ccol, const double *ww_partial, double beta,
+                          int k, double *hist, double *R, double *cs, double *sn, double *g, double *ny);
 
 /* Time `reps` back-to-back launches of one operator on resident device data with HIP events
  * on the engine's stream; returns average seconds per launch.  op: 0 spmv, 1 fused jacobi

@@ -208,6 +208,12 @@ def _load():
         "sparsh_set_gmres_basis": (C.c_int, [H, C.c_int]),
         "sparsh_gmres_basis": (C.c_int, [H, c_int_p]),
         "sparsh_op_precond": (C.c_int, [H, c_dbl_p, c_dbl_p]),
+        "sparsh_op_gs_dot": (C.c_int, [H, C.c_int, C.c_int, C.c_int, c_dbl_p, c_dbl_p, C.c_int, c_dbl_p]),
+        "sparsh_op_gs_update": (C.c_int, [H, C.c_int, C.c_int, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p, C.c_int, C.c_int, C.c_int, C.c_double,
+                                          c_dbl_p, c_dbl_p, c_dbl_p, c_int_p]),
+        "sparsh_op_gs_scale": (C.c_int, [H, C.c_int, C.c_int, c_dbl_p, C.c_double, c_dbl_p, c_dbl_p, c_dbl_p, c_int_p]),
+        "sparsh_op_gmres_small": (C.c_int, [H, C.c_int, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p, C.c_double, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p,
+                                            c_dbl_p, c_dbl_p, c_dbl_p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here = header/library mismatch: fail loudly
@@ -1011,6 +1017,58 @@ class sp_matrix_mg:
         y = np.array(y, dtype=np.float64)
         _check(lib.sparsh_op_axpby(self._h, len(x), a, _dp(x), b, _dp(y)))
         return y
+
+    # ---- test hooks of the GMRES kernels: n and nv come from the arrays, not from the handle's matrix
+    def op_gs_dot(self, V, w, basis="fp64", ww=False):
+        """(v_k . w for every row v_k of V[nv][n], w . w or None) through launch_gs_dot + launch_gs_finalize"""
+        V = np.ascontiguousarray(V, dtype=np.float64)
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        nv, n = V.shape
+        assert w.shape == (n,)
+        sums = np.zeros(nv + 1)
+        _check(lib.sparsh_op_gs_dot(self._h, n, nv, GMRES_BASES[basis], _dp(V), _dp(w), int(ww), _dp(sums)))
+        return sums[:nv], (sums[nv] if ww else None)
+
+    def op_gs_update(self, V, h, w_in, basis="fp64", in_place=False, dots=False, ww=False, sentinel=-7.25):
+        """w_out = w_in (None: 0) - sum of h[k] V[k] through launch_gs_update: (w_out, V w_out or None, w_out . w_out or None, the
+        elements of the device vector behind row n, which was filled with `sentinel`)"""
+        V = np.ascontiguousarray(V, dtype=np.float64)
+        h = np.ascontiguousarray(h, dtype=np.float64)
+        nv, n = V.shape
+        assert h.shape == (nv,)
+        if w_in is not None:
+            w_in = np.ascontiguousarray(w_in, dtype=np.float64)
+            assert w_in.shape == (n,)
+        w_out, sums, tail, ntail = np.zeros(n), np.zeros(nv + 1), np.zeros(3), C.c_int()
+        _check(lib.sparsh_op_gs_update(self._h, n, nv, GMRES_BASES[basis], _dp(V), _dp(h), None if w_in is None else _dp(w_in), int(in_place),
+                                       int(dots), int(ww), sentinel, _dp(w_out), _dp(sums), _dp(tail), C.byref(ntail)))
+        return w_out, (sums[:nv] if dots else None), (sums[nv] if ww else None), tail[: ntail.value]
+
+    def op_gs_scale(self, w, d, basis="fp64"):
+        """v = w / d (0 when d is not > 0) through launch_gs_scale.  fp64: v.  fp32: (the float vector widened to double, its fp64 copy,
+        the stored elements behind row n of the float vector)"""
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        n = len(w)
+        v, vd, tail, ntail = np.zeros(n), np.zeros(n), np.zeros(3), C.c_int()
+        _check(lib.sparsh_op_gs_scale(self._h, n, GMRES_BASES[basis], _dp(w), float(d), _dp(v), _dp(vd), _dp(tail), C.byref(ntail)))
+        return v if basis == "fp64" else (v, vd, tail[: ntail.value])
+
+    def op_gmres_small(self, hcols, ccols, ww_partial, beta, k=None):
+        """launch_gmres_step for j = 0..m-1 on a zeroed state, then launch_gmres_solve(k).  hcols[j], ccols[j]: the j + 1 coefficients
+        of the two Gram-Schmidt passes of step j; ww_partial[m][nblk].  Returns dict(hist[m], R[m][m] upper triangular, cs, sn, g[m+1], ny[k])"""
+        m = len(hcols)
+        ww_partial = np.ascontiguousarray(ww_partial, dtype=np.float64)
+        assert len(ccols) == m and ww_partial.ndim == 2 and ww_partial.shape[0] == m
+        assert all(len(hcols[j]) == j + 1 and len(ccols[j]) == j + 1 for j in range(m))
+        k = m if k is None else int(k)
+        hp = np.concatenate([np.asarray(c, dtype=np.float64) for c in hcols]) if m else np.zeros(1)
+        cp = np.concatenate([np.asarray(c, dtype=np.float64) for c in ccols]) if m else np.zeros(1)
+        M = 64
+        hist, R, cs, sn, g, ny = np.zeros(max(m, 1)), np.zeros((M, M)), np.zeros(M), np.zeros(M), np.zeros(M + 1), np.zeros(M)
+        _check(lib.sparsh_op_gmres_small(self._h, m, ww_partial.shape[1], _dp(hp), _dp(cp), _dp(ww_partial), float(beta), k, _dp(hist), _dp(R),
+                                         _dp(cs), _dp(sn), _dp(g), _dp(ny)))
+        return dict(hist=hist[:m], R=R[:m, :m].T.copy(), cs=cs[:m], sn=sn[:m], g=g[: m + 1], ny=ny[:k])
+
 
 
 # ---- entry points named as in the reference's include/AMG.hpp:40-85 --------------------------

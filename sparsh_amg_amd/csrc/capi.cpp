@@ -60,6 +60,7 @@ struct DBuf {
         p = static_cast<double *>(E.dalloc(count * sizeof(double)));
         if (p && src) (void)hipMemcpy(p, src, count * sizeof(double), hipMemcpyHostToDevice);
     }
+    DBuf(Engine &e, GmresState &s) : E(e), p(e.gmres_state_alloc(s)), n((size_t)kGmresStateDoubles) {}  // the block behind a GmresState
     ~DBuf() { E.dfree(p); }
     bool get(double *dst)
     {
@@ -1428,6 +1429,181 @@ int sparsh_op_axpby(sparsh_handle h, int n, double a, const double *x, double bc
     DBuf dx(E, (size_t)n, x), dy(E, (size_t)n, y);
     launch_axpby(n, a, dx.p, bcoef, dy.p, E.stream());
     return done(E, dy.get(y));
+}
+
+// ---- operator-level hooks of the GMRES kernels (krylov_kernels.hip): the handle lends its stream and allocator only
+}  // extern "C"
+
+namespace {
+
+// nv host vectors V[nv][n] (nullptr: none copied in) in the engine's basis layout (Engine::gmres_basis_alloc); fp32: rounded to float
+// on the host, zero-padded
+struct GsBasis {
+    Engine &E;
+    double *d = nullptr;
+    float *f = nullptr;
+    long stride = 0;
+    bool ok = false;
+    GsBasis(Engine &e, int n, int nv, int precision, const double *V) : E(e)
+    {
+        if (!E.gmres_basis_alloc(n, nv, precision, d, f, stride)) return;
+        if (hipStreamSynchronize(E.stream()) != hipSuccess) return;  // (the zeroing runs on the stream, the copies below do not)
+        if (!V) {
+            ok = true;  // left as allocated
+        } else if (f) {
+            std::vector<float> host((size_t)nv * (size_t)stride, 0.f);
+            for (int k = 0; k < nv; ++k)
+                for (int i = 0; i < n; ++i) host[(size_t)k * stride + i] = (float)V[(size_t)k * n + i];
+            ok = hipMemcpy(f, host.data(), host.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
+        } else {
+            ok = true;
+            for (int k = 0; k < nv && ok; ++k)
+                ok = hipMemcpy(d + (size_t)k * stride, V + (size_t)k * n, (size_t)n * 8, hipMemcpyHostToDevice) == hipSuccess;
+        }
+    }
+    ~GsBasis()
+    {
+        E.dfree(d);
+        E.dfree(f);
+    }
+};
+
+// a vector of `stride` doubles: src (or `fill`) in rows [0, n), `fill` behind them
+bool fill_padded(DBuf &b, int n, const double *src, double fill)
+{
+    std::vector<double> host(b.n, fill);
+    if (src) std::copy(src, src + n, host.begin());
+    return b.p && hipMemcpy(b.p, host.data(), b.n * 8, hipMemcpyHostToDevice) == hipSuccess;
+}
+
+int gs_args(sparsh_handle h, int n, int nv, int precision)
+{
+    if (!h || !h->eng) return fail(SPARSH_EINVAL, "null handle");
+    if (n <= 0) return fail(SPARSH_EINVAL, "n <= 0");
+    if (nv < 1 || nv > kGmresMaxRestart + 1) return fail(SPARSH_EINVAL, "nv must be in 1.." + std::to_string(kGmresMaxRestart + 1));
+    if (precision != SPARSH_BASIS_FP64 && precision != SPARSH_BASIS_FP32)
+        return fail(SPARSH_EINVAL, "basis precision must be SPARSH_BASIS_FP64 (0) or SPARSH_BASIS_FP32 (1)");
+    return SPARSH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sparsh_op_gs_dot(sparsh_handle h, int n, int nv, int precision, const double *V, const double *w, int want_ww, double *sums)
+{
+    if (int rc = gs_args(h, n, nv, precision); rc != SPARSH_OK) return rc;
+    if (!V || !w || !sums) return fail(SPARSH_EINVAL, "null array");
+    REQUIRE_READY(h);
+    REQUIRE_SINGLE(h);
+    Engine &E = *h->eng;
+    const int g = gs_grid(n), cnt = nv + (want_ww ? 1 : 0);
+    GsBasis B(E, n, nv, precision, V);
+    DBuf dw(E, (size_t)B.stride), part(E, (size_t)(nv + 1) * g), out(E, (size_t)cnt);
+    if (!B.ok || !part.p || !out.p || !fill_padded(dw, n, w, 0.0)) return fail(SPARSH_ENODEV, "device allocation or H2D copy failed");
+    double *ww = want_ww ? part.p + (size_t)nv * g : nullptr;
+    if (B.f) launch_gs_dot(n, B.stride, B.f, nv, dw.p, part.p, ww, E.stream());
+    else launch_gs_dot(n, B.stride, B.d, nv, dw.p, part.p, ww, E.stream());
+    launch_gs_finalize(part.p, g, cnt, out.p, E.stream());  // (w.w is row nv of the partial sums)
+    return done(E, out.get(sums));
+}
+
+int sparsh_op_gs_update(sparsh_handle h, int n, int nv, int precision, const double *V, const double *coef, const double *w_in,
+                        int in_place, int want_dots, int want_ww, double sentinel, double *w_out, double *sums, double *tail, int *ntail)
+{
+    if (int rc = gs_args(h, n, nv, precision); rc != SPARSH_OK) return rc;
+    if (!V || !coef || !w_out || !sums || !tail || !ntail) return fail(SPARSH_EINVAL, "null array");
+    if (in_place && !w_in) return fail(SPARSH_EINVAL, "an update in place needs w_in");
+    REQUIRE_READY(h);
+    REQUIRE_SINGLE(h);
+    Engine &E = *h->eng;
+    const int g = gs_grid(n);
+    GsBasis B(E, n, nv, precision, V);
+    const size_t stride = (size_t)B.stride;
+    DBuf dh(E, (size_t)nv, coef), din(E, (w_in && !in_place) ? stride : 1), dout(E, stride), part(E, (size_t)(nv + 1) * g), out(E, (size_t)nv + 1);
+    if (!B.ok || !dh.p || !din.p || !part.p || !out.p) return fail(SPARSH_ENODEV, "device allocation or H2D copy failed");
+    if (!fill_padded(dout, n, in_place ? w_in : nullptr, sentinel)) return fail(SPARSH_ENODEV, "H2D failed");
+    if (w_in && !in_place && !fill_padded(din, n, w_in, sentinel)) return fail(SPARSH_ENODEV, "H2D failed");
+    if (!fill_padded(out, 0, nullptr, 0.0)) return fail(SPARSH_ENODEV, "H2D failed");  // (sums not asked for read 0)
+    const double *src = !w_in ? nullptr : in_place ? dout.p : din.p;
+    double *dots = want_dots ? part.p : nullptr, *ww = want_ww ? part.p + (size_t)nv * g : nullptr;
+    if (B.f) launch_gs_update(n, B.stride, B.f, nv, dh.p, src, dout.p, dots, ww, E.stream());
+    else launch_gs_update(n, B.stride, B.d, nv, dh.p, src, dout.p, dots, ww, E.stream());
+    if (want_dots) launch_gs_finalize(part.p, g, nv, out.p, E.stream());
+    if (want_ww) launch_gs_finalize(ww, g, 1, out.p + nv, E.stream());
+    std::vector<double> full(stride);
+    if (!dout.get(full.data()) || !out.get(sums)) return done(E, false);
+    std::copy(full.begin(), full.begin() + n, w_out);
+    std::copy(full.begin() + n, full.end(), tail);
+    *ntail = (int)(stride - (size_t)n);
+    return done(E, true);
+}
+
+int sparsh_op_gs_scale(sparsh_handle h, int n, int precision, const double *w, double d, double *v, double *vd, double *tail, int *ntail)
+{
+    if (int rc = gs_args(h, n, 1, precision); rc != SPARSH_OK) return rc;
+    if (!w || !v || !ntail) return fail(SPARSH_EINVAL, "null array");
+    if (precision == SPARSH_BASIS_FP32 && (!vd || !tail)) return fail(SPARSH_EINVAL, "a float basis returns vd and the padding");
+    REQUIRE_READY(h);
+    REQUIRE_SINGLE(h);
+    Engine &E = *h->eng;
+    GsBasis B(E, n, 1, precision, precision == SPARSH_BASIS_FP64 ? w : nullptr);  // a double vector is scaled in place
+    const size_t stride = (size_t)B.stride;
+    DBuf dd(E, 1, &d);
+    if (!B.ok || !dd.p) return fail(SPARSH_ENODEV, "device allocation or H2D copy failed");
+    *ntail = 0;
+    if (!B.f) {
+        launch_gs_scale(n, B.d, dd.p, E.stream());
+        (void)hipStreamSynchronize(E.stream());
+        return done(E, hipMemcpy(v, B.d, (size_t)n * 8, hipMemcpyDeviceToHost) == hipSuccess);
+    }
+    DBuf dw(E, stride), dvd(E, stride);
+    if (!fill_padded(dw, n, w, 0.0) || !fill_padded(dvd, 0, nullptr, -1.0)) return fail(SPARSH_ENODEV, "device allocation or H2D copy failed");  // (vd: every row is to be written)
+    launch_gs_scale(n, dw.p, B.f, dvd.p, dd.p, E.stream());
+    std::vector<double> full(stride);
+    std::vector<float> stored(stride);
+    (void)hipStreamSynchronize(E.stream());
+    if (!dvd.get(full.data()) || hipMemcpy(stored.data(), B.f, stride * 4, hipMemcpyDeviceToHost) != hipSuccess) return done(E, false);
+    std::copy(full.begin(), full.begin() + n, vd);
+    for (int i = 0; i < n; ++i) v[i] = (double)stored[i];
+    for (size_t i = (size_t)n; i < stride; ++i) tail[i - (size_t)n] = (double)stored[i];
+    *ntail = (int)(stride - (size_t)n);
+    return done(E, true);
+}
+
+int sparsh_op_gmres_small(sparsh_handle h, int m, int nblk, const double *hcol, const double *ccol, const double *ww_partial, double beta,
+                          int k, double *hist, double *R, double *cs, double *sn, double *g, double *ny)
+{
+    if (!h || !h->eng) return fail(SPARSH_EINVAL, "null handle");
+    if (m < 1 || m > kGmresMaxRestart) return fail(SPARSH_EINVAL, "m must be in 1.." + std::to_string(kGmresMaxRestart));
+    if (nblk < 1) return fail(SPARSH_EINVAL, "nblk < 1");
+    if (k < 0 || k > m) return fail(SPARSH_EINVAL, "k must be in 0..m");
+    if (!hcol || !ccol || !ww_partial || !hist || !R || !cs || !sn || !g || !ny) return fail(SPARSH_EINVAL, "null array");
+    REQUIRE_READY(h);
+    REQUIRE_SINGLE(h);
+    Engine &E = *h->eng;
+    const size_t tri = (size_t)m * (m + 1) / 2;
+    DBuf dh(E, tri, hcol), dc(E, tri, ccol), dww(E, (size_t)m * nblk, ww_partial), dbeta(E, 1, &beta), dhist(E, (size_t)m);
+    GmresState s;  // freshly zeroed, carved as the solver's
+    DBuf state(E, s);
+    if (!state.p || !dh.p || !dc.p || !dww.p || !dbeta.p || !dhist.p) return fail(SPARSH_ENODEV, "device allocation failed");
+    hipStream_t st = E.stream();
+    size_t off = 0;
+    for (int j = 0; j < m; off += (size_t)j + 1, ++j) {  // the columns arrive as the finalize kernels leave them: j + 1 entries each
+        E.note_hip(hipMemcpyAsync(s.hcol, dh.p + off, ((size_t)j + 1) * 8, hipMemcpyDeviceToDevice, st), "hipMemcpyAsync");
+        E.note_hip(hipMemcpyAsync(s.ccol, dc.p + off, ((size_t)j + 1) * 8, hipMemcpyDeviceToDevice, st), "hipMemcpyAsync");
+        launch_gmres_step(j, dww.p + (size_t)j * nblk, nblk, s, dbeta.p, dhist.p, j, st);
+    }
+    launch_gmres_solve(k, s, st);
+    std::vector<double> all((size_t)kGmresStateDoubles);
+    if (!state.get(all.data()) || !dhist.get(hist)) return done(E, false);
+    auto take = [&](const double *dev, size_t count, double *dst) { std::copy(all.begin() + (dev - state.p), all.begin() + (dev - state.p) + count, dst); };
+    take(s.R, (size_t)kGmresMaxRestart * kGmresMaxRestart, R);
+    take(s.cs, kGmresMaxRestart, cs);
+    take(s.sn, kGmresMaxRestart, sn);
+    take(s.g, kGmresMaxRestart + 1, g);
+    take(s.ny, kGmresMaxRestart, ny);
+    return done(E, true);
 }
 
 int sparsh_bench_op(sparsh_handle h, int op, int level, int reps, double *avg_seconds)

@@ -2765,44 +2765,64 @@ void Engine::gmres_release()
     gm_bytes_ = 0;
 }
 
+// The layout the Gram-Schmidt kernels read: 16-byte aligned vectors (n rounded up to 2 doubles or to 4 floats); the float kernels
+// load whole groups of 4 rows, so a float basis is zeroed: zeros behind row n, which no kernel overwrites with anything else.
+size_t Engine::gmres_basis_alloc(int n, int nvec, int precision, double *&basis, float *&basisf, long &stride)
+{
+    const bool f32b = precision == SPARSH_BASIS_FP32;
+    basis = nullptr, basisf = nullptr;
+    stride = f32b ? ((long)n + 3) & ~3L : ((long)n + 1) & ~1L;
+    const size_t bytes = (size_t)nvec * (size_t)stride * (f32b ? 4 : 8);
+    void *p = dalloc(bytes);
+    if (!p) return 0;
+    if (f32b && !check(hipMemsetAsync(p, 0, bytes, st_), "hipMemsetAsync")) {
+        dfree(p);
+        return 0;
+    }
+    if (f32b) basisf = static_cast<float *>(p);
+    else basis = static_cast<double *>(p);
+    return bytes;
+}
+
+double *Engine::gmres_state_alloc(GmresState &s)
+{
+    double *mem = static_cast<double *>(dalloc((size_t)kGmresStateDoubles * 8));
+    if (!mem) return nullptr;
+    if (!check(hipMemsetAsync(mem, 0, (size_t)kGmresStateDoubles * 8, st_), "hipMemsetAsync")) {
+        dfree(mem);
+        return nullptr;
+    }
+    double *q = mem;
+    s.hcol = q, q += kGmresMaxRestart + 2;
+    s.ccol = q, q += kGmresMaxRestart + 2;
+    s.R = q, q += kGmresMaxRestart * kGmresMaxRestart;
+    s.cs = q, q += kGmresMaxRestart;
+    s.sn = q, q += kGmresMaxRestart;
+    s.g = q, q += kGmresMaxRestart + 1;
+    s.ny = q, q += kGmresMaxRestart;
+    s.hnext = q;
+    return mem;
+}
+
 int Engine::gmres_reserve()
 {
     if (gm_basis_ || gm_basisf_) return SPARSH_OK;
     const int n = lev_[0].n, m = gm_restart_;
     const bool f32b = gm_prec_ == SPARSH_BASIS_FP32;
-    // 16-byte aligned vectors: n rounded up to 2 doubles or to 4 floats
-    gm_stride_ = f32b ? ((long)n + 3) & ~3L : ((long)n + 1) & ~1L;
-    const size_t basis = (size_t)(m + 1) * (size_t)gm_stride_ * (f32b ? 4 : 8);
+    const size_t basis = gmres_basis_alloc(n, m + 1, gm_prec_, gm_basis_, gm_basisf_, gm_stride_);
     const size_t wvec = f32b ? (size_t)gm_stride_ * 8 : 0;
     const size_t part = (size_t)(m + 1) * (size_t)gs_grid(n) * 8;  // m sums against the basis + w.w, gs_grid(n) workgroups each
-    if (f32b) {
-        gm_basisf_ = static_cast<float *>(dalloc(basis));
-        gm_w_ = static_cast<double *>(dalloc(wvec));
-    } else {
-        gm_basis_ = static_cast<double *>(dalloc(basis));
-    }
-    gm_part_ = static_cast<double *>(dalloc(part));
-    gm_state_ = static_cast<double *>(dalloc((size_t)kGmresStateDoubles * 8));
-    if (!(f32b ? gm_basisf_ && gm_w_ : gm_basis_ != nullptr) || !gm_part_ || !gm_state_) {
+    if (basis && f32b) gm_w_ = static_cast<double *>(dalloc(wvec));
+    if (basis) gm_part_ = static_cast<double *>(dalloc(part));
+    if (basis) gm_state_ = gmres_state_alloc(gm_);
+    if (!basis || (f32b && !gm_w_) || !gm_part_ || !gm_state_) {
         gmres_release();
-        error = "GMRES basis of " + std::to_string(m + 1) + " vectors (" + std::to_string(basis >> 20) + " MiB) does not fit the device: " + error;
+        const size_t want = (size_t)(m + 1) * (size_t)gm_stride_ * (f32b ? 4 : 8);
+        error = "GMRES basis of " + std::to_string(m + 1) + " vectors (" + std::to_string(want >> 20) + " MiB) does not fit the device: " + error;
         return SPARSH_ENODEV;
     }
-    if (!check(hipMemsetAsync(gm_state_, 0, (size_t)kGmresStateDoubles * 8, st_), "hipMemsetAsync")) return SPARSH_ENODEV;
-    if (f32b) {  // the float kernels load whole groups of 4 rows: zeros behind row n, which no kernel overwrites with anything else
-        if (!check(hipMemsetAsync(gm_basisf_, 0, basis, st_), "hipMemsetAsync")) return SPARSH_ENODEV;
-        if (!check(hipMemsetAsync(gm_w_, 0, wvec, st_), "hipMemsetAsync")) return SPARSH_ENODEV;
-    }
+    if (f32b && !check(hipMemsetAsync(gm_w_, 0, wvec, st_), "hipMemsetAsync")) return SPARSH_ENODEV;
     gm_bytes_ = basis + part + wvec;
-    double *q = gm_state_;
-    gm_.hcol = q, q += kGmresMaxRestart + 2;
-    gm_.ccol = q, q += kGmresMaxRestart + 2;
-    gm_.R = q, q += kGmresMaxRestart * kGmresMaxRestart;
-    gm_.cs = q, q += kGmresMaxRestart;
-    gm_.sn = q, q += kGmresMaxRestart;
-    gm_.g = q, q += kGmresMaxRestart + 1;
-    gm_.ny = q, q += kGmresMaxRestart;
-    gm_.hnext = q;
     return SPARSH_OK;
 }
 

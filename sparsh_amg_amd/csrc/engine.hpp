@@ -308,6 +308,11 @@ public:
     int gmres_bench_prepare();
     void gmres_bench_step(bool fused);
     double op_dot(int n, const double *x, const double *y);
+    // nvec vectors of n rows as the Gram-Schmidt kernels read them, used by gmres_reserve and by the sparsh_op_gs_* hooks: stride = n
+    // rounded up to 2 doubles / 4 floats, a float basis zeroed on the stream.  Returns the bytes held (0: error set); free with dfree.
+    size_t gmres_basis_alloc(int n, int nvec, int precision, double *&basis, float *&basisf, long &stride);
+    // the device block behind a GmresState, zeroed on the stream, and s pointing into it (nullptr: error set); free with dfree
+    double *gmres_state_alloc(GmresState &s);
 
     // device memory helpers
     void *dalloc(size_t bytes);

@@ -135,3 +135,47 @@ def test_create_csr_validates_its_input():
         sa.sp_matrix_mg(rp2, ci, v)
     assert e.value.code == sa.SPARSH_EINVAL and "rowptr" in str(e.value)
     sa.sp_matrix_mg(rp, ci, v).close()  # the untouched arrays pass
+
+
+def test_gmres_kernel_hooks_reject_bad_arguments():
+    """sparsh_op_gs_* / sparsh_op_gmres_small: a bad argument is SPARSH_EINVAL before any device is asked for"""
+    rp, ci, v = problems.poisson2d(8)
+    A = sa.sp_matrix_mg(rp, ci, v)
+    A.setup(sa.default_params(print_setup=0), host_only=True)
+    dp = C.POINTER(C.c_double)
+    buf = np.zeros(70 * 70)
+    p = buf.ctypes.data_as(dp)
+    nt = C.c_int()
+    h = A._h
+    dot = lambda h, n, nv, prec: sa.lib.sparsh_op_gs_dot(h, n, nv, prec, p, p, 1, p)
+    update = lambda h, n, nv, prec: sa.lib.sparsh_op_gs_update(h, n, nv, prec, p, p, p, 0, 1, 1, -1.0, p, p, p, C.byref(nt))
+    scale = lambda h, n, nv, prec: sa.lib.sparsh_op_gs_scale(h, n, prec, p, 2.0, p, p, p, C.byref(nt))
+    for call in (dot, update, scale):
+        assert call(None, 4, 3, sa.SPARSH_BASIS_FP64) == sa.SPARSH_EINVAL
+        assert b"null handle" in sa.lib.sparsh_last_error()
+        for n in (0, -5):
+            assert call(h, n, 3, sa.SPARSH_BASIS_FP32) == sa.SPARSH_EINVAL
+            assert b"n <= 0" in sa.lib.sparsh_last_error()
+        for prec in (-1, 2):
+            assert call(h, 4, 3, prec) == sa.SPARSH_EINVAL
+            assert b"precision" in sa.lib.sparsh_last_error()
+    for call in (dot, update):
+        for nv in (0, -1, 66):
+            assert call(h, 4, nv, sa.SPARSH_BASIS_FP64) == sa.SPARSH_EINVAL
+            assert b"nv" in sa.lib.sparsh_last_error()
+    # an update in place has to be given the vector it updates
+    assert sa.lib.sparsh_op_gs_update(h, 4, 3, 0, p, p, None, 1, 0, 0, -1.0, p, p, p, C.byref(nt)) == sa.SPARSH_EINVAL
+    assert sa.lib.sparsh_op_gs_dot(h, 4, 3, 0, None, p, 0, p) == sa.SPARSH_EINVAL
+    small = lambda h, m, nblk, k: sa.lib.sparsh_op_gmres_small(h, m, nblk, p, p, p, 1.0, k, p, p, p, p, p, p)
+    assert small(None, 3, 1, 3) == sa.SPARSH_EINVAL
+    for m, nblk, k in ((0, 1, 0), (65, 1, 3), (3, 0, 3), (3, 1, 4), (3, 1, -1)):
+        assert small(h, m, nblk, k) == sa.SPARSH_EINVAL, (m, nblk, k)
+    # good arguments on a handle without a device setup: a state error, not a bad argument
+    for rc in (dot(h, 4, 3, 0), update(h, 4, 3, 1), scale(h, 4, 1, 0), small(h, 3, 1, 3)):
+        assert rc == sa.SPARSH_ESTATE
+    with pytest.raises(sa.SparshError) as e:
+        A.op_gs_dot(np.zeros((66, 4)), np.zeros(4))
+    assert e.value.code == sa.SPARSH_EINVAL
+    with pytest.raises(sa.SparshError) as e:
+        A.op_gs_scale(np.zeros(4), 1.0, basis="fp32")
+    assert e.value.code == sa.SPARSH_ESTATE
