@@ -1465,8 +1465,7 @@ int Engine::setup(const sparsh_params &p)
             !check(hipEventCreateWithFlags(&ev_halo_, hipEventDisableTiming), "hipEventCreate"))
             return SPARSH_ENODEV;
     }
-    if (sor_on() && !dist_ && !p.precond_fp32 && !build_sor_layouts()) return SPARSH_ENODEV;  // (otherwise refused at the solve)
-    if (cheby_on() && !dist_ && !p.precond_fp32 && cheby_prepare() != SPARSH_OK) return SPARSH_ENODEV;
+    if (!dist_ && !p.precond_fp32 && smoother_prepare() != SPARSH_OK) return SPARSH_ENODEV;  // (otherwise refused at the solve)
     if (!check(hipStreamSynchronize(st_), "setup sync")) return SPARSH_ENODEV;
     if (!comm_->barrier(st_)) {
         error = "comm barrier after setup failed: " + comm_->error;
@@ -1866,6 +1865,11 @@ double Engine::op_dot(int n, const double *x, const double *y)
 void Engine::smooth(DevLevel &L, const double *b, int sweeps, bool x_zero, double *dot_partial, int *dot_nblk, bool zero_done,
                     DevLevel *prolong_to)
 {
+    auto close_timed_run = [&](int launches) {
+        HIPCHK(hipEventRecord(prof.ev[prof.used + 1], st_));
+        prof.run_launches.push_back(launches);
+        prof.used += 2;
+    };
     if (L.deep) {
         // Deep-halo leg: no exchange inside.  On entry b is valid on the layers <= K-1 and (unless x = 0) x on the
         // layers <= K; sweep s leaves the layers <= K-s valid, so after `sweeps` <= K-1 sweeps the own rows and the
@@ -1892,11 +1896,7 @@ void Engine::smooth(DevLevel &L, const double *b, int sweeps, bool x_zero, doubl
             ++in_run;
             std::swap(L.x, L.x2);
         }
-        if (timed) {
-            HIPCHK(hipEventRecord(prof.ev[prof.used + 1], st_));
-            prof.run_launches.push_back(in_run);
-            prof.used += 2;
-        }
+        if (timed) close_timed_run(in_run);
         if (dot_partial) launch_dot(L.n, L.x, b, dot_partial, dot_nblk, st_);  // own rows only
         return;
     }
@@ -1925,9 +1925,7 @@ void Engine::smooth(DevLevel &L, const double *b, int sweeps, bool x_zero, doubl
             std::swap(L.x, L.x2);
             // profiling a level that runs double sweeps: the timed run is its double-sweep launches alone
             if (timed_open && !(k + 3 <= sweeps - (special_last ? 1 : 0))) {
-                HIPCHK(hipEventRecord(prof.ev[prof.used + 1], st_));
-                prof.run_launches.push_back(in_run);
-                prof.used += 2;
+                close_timed_run(in_run);
                 timed_open = false;
             }
             continue;
@@ -1955,30 +1953,31 @@ void Engine::smooth(DevLevel &L, const double *b, int sweeps, bool x_zero, doubl
         ++in_run;
         std::swap(L.x, L.x2);
     }
-    if (timed_open && !pairs) {
-        HIPCHK(hipEventRecord(prof.ev[prof.used + 1], st_));
-        prof.run_launches.push_back(in_run);
-        prof.used += 2;
-    }
+    if (timed_open && !pairs) close_timed_run(in_run);
     if (dot_partial && !dot_done) launch_dot(L.n, L.x, b, dot_partial, dot_nblk, st_);
 }
 
-void Engine::op_jacobi(int l, const double *b, double *x, double *tmp, int sweeps, bool x_is_zero)
+// run on caller buffers by temporarily borrowing the level's ping-pong slots (an odd number of swaps leaves the result in tmp)
+template <class Fn> void Engine::with_borrowed_slots(int l, double *x, double *tmp, Fn fn)
 {
-    // run on caller buffers by temporarily borrowing the level's ping-pong slots
     DevLevel &L = lev_[l];
     double *sx = L.x, *sx2 = L.x2;
     L.x = x;
     L.x2 = tmp;
-    smooth(L, b, sweeps, x_is_zero, nullptr, nullptr);
+    fn(L);
     if (L.x != x) launch_copy(L.n, L.x, x, st_);
     L.x = sx;
     L.x2 = sx2;
 }
 
+void Engine::op_jacobi(int l, const double *b, double *x, double *tmp, int sweeps, bool x_is_zero)
+{
+    with_borrowed_slots(l, x, tmp, [&](DevLevel &L) { smooth(L, b, sweeps, x_is_zero, nullptr, nullptr); });
+}
+
 // ---------------------------------------------------------------------------- multicolour SOR smoother
 
-void Engine::adopt_sweeps() { prm_.sweeps = (smoother_ == SPARSH_SMOOTH_JACOBI && sm_sweeps_ > 0) ? sm_sweeps_ : base_sweeps_; }
+void Engine::adopt_sweeps() { prm_.sweeps = (jacobi_on() && sm_sweeps_ > 0) ? sm_sweeps_ : base_sweeps_; }
 
 void Engine::set_smoother(int kind, int sweeps, int order)
 {
@@ -2055,26 +2054,27 @@ bool Engine::build_sor_level(int l)
     return true;
 }
 
-// the levels a V-cycle smooths (every level but the coarsest, which is solved directly)
-bool Engine::build_sor_layouts()
+// What a solve with the selected smoother needs beyond the Jacobi hierarchy, on the levels a V-cycle smooths (every level but the
+// coarsest, which is solved directly).
+int Engine::smoother_prepare()
 {
-    for (int l = 0; l + 1 < (int)lev_.size(); ++l)
-        if (!build_sor_level(l)) return false;
-    return true;
-}
-
-int Engine::sor_prepare()
-{
-    if (!sor_on()) return SPARSH_OK;
+    if (jacobi_on()) return SPARSH_OK;
+    const std::string name = sor_on() ? "SOR" : "Chebyshev";
     if (dist_) {
-        error = "the SOR smoother is not available on a partitioned (multi-GPU) handle";
+        error = "the " + name + " smoother is not available on a partitioned (multi-GPU) handle";
         return SPARSH_EINVAL;
     }
     if (prm_.precond_fp32) {
-        error = "the SOR smoother has no fp32 hierarchy: unset params.precond_fp32";
+        error = "the " + name + " smoother has no fp32 hierarchy: unset params.precond_fp32";
         return SPARSH_EINVAL;
     }
-    if (!build_sor_layouts()) return fault_ != SPARSH_OK ? fault_ : SPARSH_ENODEV;
+    for (int l = 0; l + 1 < (int)lev_.size(); ++l)
+        if (!(sor_on() ? build_sor_level(l) : build_cheby_level(l))) {
+            if (fault_ != SPARSH_OK) return fault_;
+            if (sor_on()) return SPARSH_ENODEV;
+            const double lm = cheb_[l].lmax();  // no positive finite bound: the level's operator, not the device, is at fault
+            return lm > 0.0 && std::isfinite(lm) ? SPARSH_ENODEV : SPARSH_ENUMERIC;
+        }
     return SPARSH_OK;
 }
 
@@ -2082,7 +2082,7 @@ void Engine::sor_leg(int l, const double *b, double *x, int sweeps, bool reverse
 {
     if (sweeps <= 0) return;
     if (l < 0 || l >= (int)sor_.size() || !sor_[l].rows) {
-        // every caller builds the layouts first (sor_prepare / build_sor_level): nothing may run on a missing layout
+        // every caller builds the layouts first (smoother_prepare / build_sor_level): nothing may run on a missing layout
         error = "SOR sweep on level " + std::to_string(l) + " without its colour layout";
         if (fault_ == SPARSH_OK) fault_ = SPARSH_ESTATE;
         return;
@@ -2115,35 +2115,6 @@ bool Engine::op_sor(int l, const double *b, double *x, int sweeps, bool reverse,
     if (x_is_zero && sweeps > 0) launch_fill(lev_[l].n, 0.0, x, st_);
     sor_leg(l, b, x, sweeps, reverse);
     return true;
-}
-
-// AMG_solve_SOR (src/AMG_phases.cpp:234-306): the Jacobi cycle's hierarchy and order of operations, with plain residual,
-// restriction, coarse-solve and prolongation launches and nothing of the Jacobi smoother fused into them.
-void Engine::vcycle_sor(const double *b0, bool x0_zero, double *dot_partial, int *dot_nblk)
-{
-    const int last = (int)lev_.size() - 1;
-    const int nu = sor_sweeps();
-    lev_[0].b = const_cast<double *>(b0);
-    if (last == 0) {
-        op_coarse(b0, lev_[0].x);
-        if (dot_partial) launch_dot(lev_[0].n, lev_[0].x, b0, dot_partial, dot_nblk, st_);
-        return;
-    }
-    for (int l = 0; l < last; ++l) {
-        DevLevel &L = lev_[l];
-        if (l > 0 || x0_zero) launch_fill(L.n, 0.0, L.x, st_);  // fill(Xv[l1+1], ..., 0.0)
-        sor_leg(l, L.b, L.x, nu, false);                        // pre-smoothing: colours 1..C
-        op_residual(l, L.b, L.x, L.r);                           // store_residual
-        op_restrict(l, L.r, lev_[l + 1].b, false);               // transfer_residual
-    }
-    op_coarse(lev_[last].b, lev_[last].x);  // Direct_Solver_Pardiso_solve
-    const bool rev = sor_order_ == SPARSH_SOR_SYMMETRIC;
-    for (int l = last; l > 0; --l) {
-        DevLevel &F = lev_[l - 1];
-        op_prolong(l - 1, lev_[l].x, F.x);  // transfer_solution
-        sor_leg(l - 1, F.b, F.x, nu, rev);
-    }
-    if (dot_partial) launch_dot(lev_[0].n, lev_[0].x, b0, dot_partial, dot_nblk, st_);
 }
 
 // ---------------------------------------------------------------------------- Chebyshev polynomial smoother
@@ -2196,26 +2167,6 @@ bool Engine::build_cheby_level(int l)
     return true;
 }
 
-int Engine::cheby_prepare()
-{
-    if (!cheby_on()) return SPARSH_OK;
-    if (dist_) {
-        error = "the Chebyshev smoother is not available on a partitioned (multi-GPU) handle";
-        return SPARSH_EINVAL;
-    }
-    if (prm_.precond_fp32) {
-        error = "the Chebyshev smoother has no fp32 hierarchy: unset params.precond_fp32";
-        return SPARSH_EINVAL;
-    }
-    for (int l = 0; l + 1 < (int)lev_.size(); ++l)
-        if (!build_cheby_level(l)) {
-            if (fault_ != SPARSH_OK) return fault_;
-            const double lm = cheb_[l].lmax();
-            return lm > 0.0 && std::isfinite(lm) ? SPARSH_ENODEV : SPARSH_ENUMERIC;
-        }
-    return SPARSH_OK;
-}
-
 // x_{k+1} = x_k + d_k, d_k = c1_k d_{k-1} + c2_k D^-1 (b - A x_k): one launch per step, the iterate ping-ponging through L.x / L.x2 as
 // under Jacobi, d updated in place.  From a zero guess x_1 = d_0 = c2_0 b / d is the zero-guess Jacobi launch with omega = c2_0, and
 // step 1 reads its d_0 from the iterate.
@@ -2226,7 +2177,7 @@ void Engine::cheby_leg(int l, const double *b, bool x_zero, int degree, double *
         return;
     }
     if (l < 0 || l >= (int)cheb_.size() || !cheb_[l].d || !cheb_[l].have) {
-        // every caller builds the level's state first (cheby_prepare / build_cheby_level)
+        // every caller builds the level's state first (smoother_prepare / build_cheby_level)
         error = "Chebyshev step on level " + std::to_string(l) + " without its bounds and correction vector";
         if (fault_ == SPARSH_OK) fault_ = SPARSH_ESTATE;
         return;
@@ -2271,14 +2222,7 @@ void Engine::cheby_leg(int l, const double *b, bool x_zero, int degree, double *
 bool Engine::op_cheby(int l, const double *b, double *x, double *tmp, int degree, bool x_is_zero)
 {
     if (!build_cheby_level(l)) return false;
-    DevLevel &L = lev_[l];
-    double *sx = L.x, *sx2 = L.x2;
-    L.x = x;
-    L.x2 = tmp;
-    cheby_leg(l, b, x_is_zero, degree, nullptr, nullptr);
-    if (L.x != x) launch_copy(L.n, L.x, x, st_);
-    L.x = sx;
-    L.x2 = sx2;
+    with_borrowed_slots(l, x, tmp, [&](DevLevel &) { cheby_leg(l, b, x_is_zero, degree, nullptr, nullptr); });
     return true;
 }
 
@@ -2301,12 +2245,28 @@ void Engine::cheby_bench_step(int l)
     launch_csr(L.A, OP_CHEBY, a, L.fine, st_, cfg_);
 }
 
-// The Jacobi cycle's hierarchy and order of operations with plain residual, restriction, coarse-solve and prolongation launches, as
-// vcycle_sor; the smoothing legs are Chebyshev polynomials of the handle's degree.
-void Engine::vcycle_cheby(const double *b0, bool x0_zero, double *dot_partial, int *dot_nblk)
+// ---------------------------------------------------------------------------- the cycle of the smoothers that fuse nothing
+
+// One smoothing leg of vcycle_plain.  SOR: colours 1..C before the coarse correction, C..1 after it under the symmetric order; the zero
+// guess is a fill and the dot a launch of its own.  Chebyshev: the zero guess is the leg's first launch and the dot rides in its last.
+void Engine::plain_leg(int l, bool x_zero, bool post, double *dot_partial, int *dot_nblk)
+{
+    DevLevel &L = lev_[l];
+    if (cheby_on()) {
+        cheby_leg(l, L.b, x_zero, cheby_degree(), dot_partial, dot_nblk);
+        return;
+    }
+    if (x_zero) launch_fill(L.n, 0.0, L.x, st_);  // fill(Xv[l1+1], ..., 0.0)
+    sor_leg(l, L.b, L.x, sor_sweeps(), post && sor_order_ == SPARSH_SOR_SYMMETRIC);
+    if (dot_partial) launch_dot(L.n, L.x, L.b, dot_partial, dot_nblk, st_);
+}
+
+// AMG_solve_SOR (src/AMG_phases.cpp:234-306): the Jacobi cycle's hierarchy and order of operations, with plain residual,
+// restriction, coarse-solve and prolongation launches and nothing of the Jacobi smoother fused into them; the smoothing legs are
+// SOR sweeps or Chebyshev polynomials of the handle's degree.
+void Engine::vcycle_plain(const double *b0, bool x0_zero, double *dot_partial, int *dot_nblk)
 {
     const int last = (int)lev_.size() - 1;
-    const int m = cheby_degree();
     lev_[0].b = const_cast<double *>(b0);
     if (last == 0) {
         op_coarse(b0, lev_[0].x);
@@ -2315,28 +2275,22 @@ void Engine::vcycle_cheby(const double *b0, bool x0_zero, double *dot_partial, i
     }
     for (int l = 0; l < last; ++l) {
         DevLevel &L = lev_[l];
-        cheby_leg(l, L.b, l > 0 || x0_zero, m, nullptr, nullptr);  // coarse levels start from x = 0
-        op_residual(l, L.b, L.x, L.r);                             // store_residual
-        op_restrict(l, L.r, lev_[l + 1].b, false);                 // transfer_residual
+        plain_leg(l, l > 0 || x0_zero, false, nullptr, nullptr);  // pre-smoothing; coarse levels start from x = 0
+        op_residual(l, L.b, L.x, L.r);                            // store_residual
+        op_restrict(l, L.r, lev_[l + 1].b, false);                // transfer_residual
     }
-    op_coarse(lev_[last].b, lev_[last].x);
+    op_coarse(lev_[last].b, lev_[last].x);  // Direct_Solver_Pardiso_solve
     for (int l = last; l > 0; --l) {
-        DevLevel &F = lev_[l - 1];
-        op_prolong(l - 1, lev_[l].x, F.x);  // transfer_solution
-        const bool want_dot = (l - 1 == 0) && dot_partial;
-        cheby_leg(l - 1, F.b, false, m, want_dot ? dot_partial : nullptr, dot_nblk);
+        op_prolong(l - 1, lev_[l].x, lev_[l - 1].x);  // transfer_solution
+        plain_leg(l - 1, false, true, l == 1 ? dot_partial : nullptr, dot_nblk);
     }
 }
 
 // One V(nu,nu) cycle (body of the while loops in AMG_solve_jacobi, src/AMG_phases.cpp:198-216).
 void Engine::vcycle(const double *b0, bool x0_zero, double *dot_partial, int *dot_nblk, bool zero_done0)
 {
-    if (sor_on()) {
-        vcycle_sor(b0, x0_zero, dot_partial, dot_nblk);
-        return;
-    }
-    if (cheby_on()) {
-        vcycle_cheby(b0, x0_zero, dot_partial, dot_nblk);
+    if (!jacobi_on()) {
+        vcycle_plain(b0, x0_zero, dot_partial, dot_nblk);
         return;
     }
     const int last = (int)lev_.size() - 1;
@@ -2452,6 +2406,17 @@ int Engine::amg_solve_dev(const double *b, double *x, int iterations, double *hi
     return fault_ != SPARSH_OK ? fault_ : rc;
 }
 
+const double *Engine::precondition(const double *r, double *scratch, double *dot_partial, int *dot_nblk, bool zero_done0)
+{
+    if (f32_ready_) {
+        int nb = 0;
+        vcycle_f32(r, scratch, dot_partial ? dot_partial : part0_, dot_partial ? dot_nblk : &nb);
+        return scratch;
+    }
+    vcycle(r, true, dot_partial, dot_nblk, zero_done0);  // z = 0 ; z = V(r), zero initial guess
+    return lev_[0].x;
+}
+
 // Solver_CG_1 (precond = false) / Solver_PCG_1 (precond = true), split into the part before
 // the while loop (pcg_init: r0, ||r0||, z0 = V(r0), p = z0; src/AMG_main_solvers.cpp:124-133)
 // and the loop body (pcg_steps: :136-159) so a caller can time exactly k iterations.
@@ -2487,17 +2452,12 @@ int Engine::pcg_init(const double *b, double *x, bool precond)
     if (!precond) finalize(FIN_STORE, part0_, nullptr, nb, S_RR, nullptr, 0);
     finalize(FIN_SQRT, part0_, nullptr, nb, S_RES, nullptr, 0);
     ks_.r1 = read_scalar(S_RES);
-    if (precond && f32_ready_) {
-        vcycle_f32(r, work_[4], part0_, &nb);  // z0 = V32(r0)
+    const double *z = r;
+    if (precond) {
+        z = precondition(r, work_[4], part0_, &nb);  // z0 = M r0 ; z0.r0
         finalize(FIN_STORE, part0_, nullptr, nb, S_RZ, nullptr, 0);
-        launch_copy(n, work_[4], p, st_);
-    } else if (precond) {
-        vcycle(r, true, part0_, &nb);  // z0 = V(r0), zero initial guess
-        finalize(FIN_STORE, part0_, nullptr, nb, S_RZ, nullptr, 0);
-        launch_copy(n, lev_[0].x, p, st_);
-    } else {
-        launch_copy(n, r, p, st_);
     }
+    launch_copy(n, z, p, st_);
     ks_.active = true;
     return fault_;
 }
@@ -2521,7 +2481,7 @@ void Engine::pcg_body(bool precond, int slot)
     // are reduced together with z.r after the V-cycle: one finalize launch (one all-reduce) less
     // with the fp64 V-cycle behind it the update also writes the cycle's zero-guess sweep of level 0 (z0 = omega r / d)
     // (... unless the cycle's first launch on level 0 is the three-sweep one, which reads r alone)
-    const bool fuse_zero = cfg_.fuse_cg_zero && precond && !f32_ready_ && !sor_on() && !cheby_on() && lev_.size() > 1 && !lev_[0].deep && prm_.sweeps > 0 &&
+    const bool fuse_zero = cfg_.fuse_cg_zero && precond && !f32_ready_ && jacobi_on() && lev_.size() > 1 && !lev_[0].deep && prm_.sweeps > 0 &&
                            !(prm_.sweeps >= 3 && zero_start(lev_[0]));
     // with the fp64 V-cycle behind it x += alpha p waits for the direction update at the end of this iteration (one read of p for both)
     const bool defer_x = cfg_.defer_x && precond && !f32_ready_;
@@ -2530,17 +2490,12 @@ void Engine::pcg_body(bool precond, int slot)
         launch_cg_update_zero(n, scal_, p, Ap, x_now, r, part1_, &nb, diag_stream(lev_[0]), lev_[0].diag_const, prm_.omega, lev_[0].x, st_, cfg_.cg_nt);
     else
         launch_cg_update(n, scal_, p, Ap, x_now, r, precond ? part1_ : part0_, &nb, st_);
-    if (precond && f32_ready_) {
+    if (precond) {
         const int nb_rr = nb;
-        vcycle_f32(r, work_[4], part0_, &nb);  // float hierarchy, fp64 in/out, fused z0.r0
+        const double *z = precondition(r, work_[4], part0_, &nb, fuse_zero);  // z0 = M r0 ; fused z0.r0
         finalize(FIN_PCG_BETA_RES, part0_, part1_, nb, 0, hist_dev_, slot, nb_rr);
-        launch_p_update(n, scal_, work_[4], p, st_);
-    } else if (precond) {
-        const int nb_rr = nb;
-        vcycle(r, true, part0_, &nb, fuse_zero);  // z0 = 0 ; z0 = V(r0) ; fused z0.r0
-        finalize(FIN_PCG_BETA_RES, part0_, part1_, nb, 0, hist_dev_, slot, nb_rr);
-        if (defer_x) launch_xp_update(n, scal_, lev_[0].x, p, x, st_);  // x += alpha p ; p = z0 + beta p
-        else launch_p_update(n, scal_, lev_[0].x, p, st_);                // p = z0 + beta p
+        if (defer_x) launch_xp_update(n, scal_, z, p, x, st_);  // x += alpha p ; p = z0 + beta p
+        else launch_p_update(n, scal_, z, p, st_);                // p = z0 + beta p
     } else {
         finalize(FIN_CG_BETA, part0_, nullptr, nb, 0, hist_dev_, slot);
         launch_p_update(n, scal_, r, p, st_);
@@ -2668,12 +2623,9 @@ int Engine::bicg(const double *b, double *x, int max_iters, double *hist, int hi
             break;
         }
         const double *p1 = p;
-        if (precond && f32_ready_) {
-            vcycle_f32(p, p1buf, part0_, &nb);  // float hierarchy (opt-in), fp64 in/out
-            p1 = p1buf;
-        } else if (precond) {
-            vcycle(p, true, nullptr, nullptr);  // p1 = 0 ; p1 = V(p)
-            launch_copy(n, lev_[0].x, p1buf, st_);
+        if (precond) {
+            const double *z = precondition(p, p1buf);  // p1 = M p, kept in p1buf: the second application overwrites the cycle's own buffer
+            if (z != p1buf) launch_copy(n, z, p1buf, st_);
             p1 = p1buf;
         }
         op_spmv(0, p1, Ap);
@@ -2681,13 +2633,7 @@ int Engine::bicg(const double *b, double *x, int max_iters, double *hist, int hi
         finalize(FIN_BICG_ALPHA, part0_, part1_, nb, 0, nullptr, 0);
         launch_bicg_s(n, scal_, r, Ap, s, st_);
         const double *s1 = s;
-        if (precond && f32_ready_) {
-            vcycle_f32(s, work_[7], part0_, &nb);
-            s1 = work_[7];
-        } else if (precond) {
-            vcycle(s, true, nullptr, nullptr);  // s1 = 0 ; s1 = V(s)
-            s1 = lev_[0].x;
-        }
+        if (precond) s1 = precondition(s, work_[7]);  // s1 = M s
         op_spmv(0, s1, As);
         launch_dot2(n, As, s, As, As, part0_, part1_, &nb, st_);
         finalize(FIN_BICG_OMEGA, part0_, part1_, nb, 0, nullptr, 0);
@@ -2718,13 +2664,8 @@ int Engine::bicg(const double *b, double *x, int max_iters, double *hist, int hi
 int Engine::op_precond(const double *r, double *z)
 {
     if (int rc = smoother_prepare(); rc != SPARSH_OK) return rc;
-    int nb = 0;
-    if (f32_ready_) {
-        vcycle_f32(r, z, part0_, &nb);
-    } else {
-        vcycle(r, true, nullptr, nullptr);
-        launch_copy(lev_[0].n, lev_[0].x, z, st_);
-    }
+    const double *zc = precondition(r, z);
+    if (zc != z) launch_copy(lev_[0].n, zc, z, st_);
     return fault_;
 }
 
@@ -2834,25 +2775,21 @@ void Engine::gmres_orthogonalise(int j, int slot, double *feed)
 {
     const int n = lev_[0].n, nv = j + 1, g = gs_grid(n), m = gm_restart_;
     double *ww = gm_part_ + (size_t)m * g;
-    if (gm_prec_ == SPARSH_BASIS_FP32) {
-        double *w = gm_w_;
-        launch_gs_dot(n, gm_stride_, gm_basisf_, nv, w, gm_part_, nullptr, st_);
+    auto against = [&](auto *basis, double *w) {  // the launches are overloaded on the basis' type
+        launch_gs_dot(n, gm_stride_, basis, nv, w, gm_part_, nullptr, st_);
         launch_gs_finalize(gm_part_, g, nv, gm_.hcol, st_);
-        launch_gs_update(n, gm_stride_, gm_basisf_, nv, gm_.hcol, w, w, gm_part_, nullptr, st_);
+        launch_gs_update(n, gm_stride_, basis, nv, gm_.hcol, w, w, gm_part_, nullptr, st_);
         launch_gs_finalize(gm_part_, g, nv, gm_.ccol, st_);
-        launch_gs_update(n, gm_stride_, gm_basisf_, nv, gm_.ccol, w, w, nullptr, ww, st_);
+        launch_gs_update(n, gm_stride_, basis, nv, gm_.ccol, w, w, nullptr, ww, st_);
         launch_gmres_step(j, ww, g, gm_, scal_ + S_RES, hist_dev_, slot, st_);
-        launch_gs_scale(n, w, gm_vecf(j + 1), feed, gm_.hnext, st_);
-        return;
+    };
+    if (gm_prec_ == SPARSH_BASIS_FP32) {
+        against(gm_basisf_, gm_w_);
+        launch_gs_scale(n, gm_w_, gm_vecf(j + 1), feed, gm_.hnext, st_);
+    } else {
+        against(gm_basis_, gm_vec(j + 1));
+        launch_gs_scale(n, gm_vec(j + 1), gm_.hnext, st_);
     }
-    double *w = gm_vec(j + 1);
-    launch_gs_dot(n, gm_stride_, gm_basis_, nv, w, gm_part_, nullptr, st_);
-    launch_gs_finalize(gm_part_, g, nv, gm_.hcol, st_);
-    launch_gs_update(n, gm_stride_, gm_basis_, nv, gm_.hcol, w, w, gm_part_, nullptr, st_);
-    launch_gs_finalize(gm_part_, g, nv, gm_.ccol, st_);
-    launch_gs_update(n, gm_stride_, gm_basis_, nv, gm_.ccol, w, w, nullptr, ww, st_);
-    launch_gmres_step(j, ww, g, gm_, scal_ + S_RES, hist_dev_, slot, st_);
-    launch_gs_scale(n, w, gm_.hnext, st_);
 }
 
 int Engine::gmres(const double *b, double *x, int max_iters, double *hist, int hist_cap, int *iters, bool precond)
@@ -2871,15 +2808,7 @@ int Engine::gmres(const double *b, double *x, int max_iters, double *hist, int h
     double *feed = work_[2];  // float basis: v_j as stored, widened to double
     int nb = 0, it = 0, rc = SPARSH_OK;
     // z = M v (nullptr: the identity); the fp64 cycle leaves z in lev_[0].x, which belongs to the cycle: consumed by the next launch
-    auto apply_M = [&](const double *v) -> const double * {
-        if (!precond) return v;
-        if (f32_ready_) {
-            vcycle_f32(v, z32, part0_, &nb);
-            return z32;
-        }
-        vcycle(v, true, nullptr, nullptr);
-        return lev_[0].x;
-    };
+    auto apply_M = [&](const double *v) { return precond ? precondition(v, z32) : v; };
     // The only exit with SPARSH_OK is the true residual of a cycle start being <= tol.  |g_{j+1}| <= tol only ends the cycle, which
     // matters under a float basis, where |g_{j+1}| is an estimate of the residual: the next cycle start decides.
     for (;;) {  // one restart cycle

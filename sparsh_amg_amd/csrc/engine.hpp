@@ -132,6 +132,7 @@ public:
     // degree 4)
     void set_smoother(int kind, int sweeps, int order);
     int smoother() const { return smoother_; }
+    bool jacobi_on() const { return smoother_ == SPARSH_SMOOTH_JACOBI; }
     bool sor_on() const { return smoother_ == SPARSH_SMOOTH_SOR; }
     int sor_sweeps() const { return sm_sweeps_ > 0 ? sm_sweeps_ : kSorDefaultSweeps; }
     int sor_order() const { return sor_order_; }
@@ -139,16 +140,13 @@ public:
     void set_sor_path(int mode) { sor_path_ = mode; }
     // colour classes of level l (host; computed on first use after setup_host)
     const ColorClasses &level_colors(int l);
-    // SOR layouts ready for a solve on this handle (built now if the smoother was chosen after setup); SPARSH_* code
-    int sor_prepare();
     const SorLevel *sor_level(int l) const { return l >= 0 && l < (int)sor_.size() && sor_[l].rows ? &sor_[l] : nullptr; }
     bool sor_single(int l) const { return sor_path_ == 2 || (sor_path_ == 0 && sor_[l].single); }  // a leg of level l is one launch
     // `sweeps` SOR sweeps of level l on x in place (colours C..1 when reverse), issued as a smoothing leg issues them
     void sor_leg(int l, const double *b, double *x, int sweeps, bool reverse);
     // the same as a test hook on any level whatever the smoother (x_is_zero: x is taken as 0); false if the layouts cannot be built
     bool op_sor(int l, const double *b, double *x, int sweeps, bool reverse, bool x_is_zero);
-    bool build_sor_layouts();     // layouts of the smoothed levels (all but the coarsest); no-op once built for the current setup
-    bool build_sor_level(int l);  // layout of level l alone (op_sor / bench on any level, the coarsest included)
+    bool build_sor_level(int l);  // layout of level l alone, the coarsest included (op_sor / bench); no-op once built for the current setup
     // ---- Chebyshev polynomial smoother (cheby_bounds.hpp)
     bool cheby_on() const { return smoother_ == SPARSH_SMOOTH_CHEBYSHEV; }
     int cheby_degree() const { return sm_sweeps_ > 0 ? sm_sweeps_ : kChebyDefaultDegree; }
@@ -159,8 +157,6 @@ public:
     // coarsest, when Chebyshev was selected before it; the coarsest level's serve op_cheby and the bench alone)
     const ChebyLevel &level_cheby(int l);
     void set_cheby_lmax(int l, double lmax);  // 0: back to the estimate
-    // bounds and d vectors ready for a solve on this handle; SPARSH_* code
-    int cheby_prepare();
     bool build_cheby_level(int l);  // bounds + d vector of level l alone (op_cheby / bench)
     // one leg of `degree` steps on level l: iterate in lev_[l].x on entry and exit (x_zero: taken as 0, not read), lev_[l].x2 is scratch;
     // dot_partial: the last step also leaves the partial sums of x.b there
@@ -169,8 +165,9 @@ public:
     bool op_cheby(int l, const double *b, double *x, double *tmp, int degree, bool x_is_zero);
     // bench: one step of the k >= 1 form on the level's resident buffers (x, x2, d; r as the right-hand side)
     void cheby_bench_step(int l);
-    // both of the above for whichever smoother is selected (every solver entry calls it)
-    int smoother_prepare() { return cheby_on() ? cheby_prepare() : sor_prepare(); }
+    // SOR layouts / Chebyshev bounds and d vectors of the smoothed levels (all but the coarsest) ready for a solve on this handle, built
+    // now if the smoother was chosen after setup; SPARSH_* code (every solver entry calls it)
+    int smoother_prepare();
     static constexpr int kSorDefaultSweeps = 6;  // AMG_solve_SOR's count (src/AMG_phases.cpp:252)
     // levels with at most this many entries run a leg as one launch: 0, the single launch was slower than the per-colour launches on
     // every level measured on the MI355X, down to 3 774 rows / 25 940 entries
@@ -359,10 +356,17 @@ private:
     double read_scalar(int slot);
     double read_hist(int it);
 
-    // one V(nu,nu) cycle with the SOR smoother: the Jacobi cycle's order of operations without any fused Jacobi step
-    void vcycle_sor(const double *b0, bool x0_zero, double *dot_partial, int *dot_nblk);
-    // ... with the Chebyshev smoother: likewise, the last post-smoothing step of level 0 carrying the dot (OP_CHEBY_DOT)
-    void vcycle_cheby(const double *b0, bool x0_zero, double *dot_partial, int *dot_nblk);
+    // z = M r from a zero guess, the one place that applies the preconditioner: the float hierarchy when it is built (z in scratch),
+    // otherwise vcycle of the handle's smoother (z in lev_[0].x, which belongs to the cycle: valid until the next one).  Returns where
+    // z lies.  The fp32 cycle always writes the partial sums of z.r: a null dot_partial means part0_ and a local block count.
+    const double *precondition(const double *r, double *scratch, double *dot_partial = nullptr, int *dot_nblk = nullptr, bool zero_done0 = false);
+    // one V(nu,nu) cycle with the SOR or the Chebyshev smoother: the Jacobi cycle's order of operations without any fused Jacobi step
+    void vcycle_plain(const double *b0, bool x0_zero, double *dot_partial, int *dot_nblk);
+    // one smoothing leg of that cycle on level l, iterate in lev_[l].x (x_zero: taken as 0); post: after the coarse correction;
+    // dot_partial: the leg also leaves the partial sums of x.b there (Chebyshev: fused into its last step, OP_CHEBY_DOT)
+    void plain_leg(int l, bool x_zero, bool post, double *dot_partial, int *dot_nblk);
+    // run fn with lev_[l]'s ping-pong slots pointing at the caller's x / tmp; the result ends in x
+    template <class Fn> void with_borrowed_slots(int l, double *x, double *tmp, Fn fn);
     std::vector<ChebyLevel> cheb_;  // per level (empty until first use)
     double cheby_ratio_ = kChebyDefaultRatio;
     int cheby_steps_ = kChebyDefaultSteps;
