@@ -549,6 +549,50 @@ int sparsh_set_chebyshev_lmax(sparsh_handle h, int level, double lmax);
 int sparsh_level_chebyshev(sparsh_handle h, int level, double *lmax, double *lmin, double *gershgorin, double *lanczos);
 int sparsh_op_cheby(sparsh_handle h, int level, const double *b, double *x, int degree, int x_is_zero);
 
+/* ---- a block of up to SPARSH_MAX_RHS right-hand sides in one AMG-PCG run ----
+ * k systems with one matrix -- load cases, solution components, columns of a block method -- solved together: every kernel of the
+ * V-cycle and of the Krylov loop reads the operator once for all columns.  Arrays are column-major: column c at B + c * ldb, ldb >= n
+ * (ldx likewise); inside the engine the block is row-interleaved with width 2, 4 or 8 (nrhs rounded up; padding columns hold zeros
+ * and are frozen from the start) and callers never see that layout.  Per column the arithmetic is that of the single-vector kernels
+ * (row sums in stored order, the epilogues of the Jacobi cycle, the recurrences of SPARSH_PCG); the cycle is the plain Jacobi
+ * V(nu,nu) cycle from a zero guess with nothing fused, so column c follows sparsh_solve(SPARSH_PCG) of the same right-hand side up to
+ * the last bits of the reductions and of the box-grid kernels' fused launches.
+ * method: SPARSH_PCG only.  X: initial guesses in, solutions out.  hist[c * hist_cap + k] = column c's residual after iteration
+ * k + 1; entries from iters[c] on are left untouched.  iters / status: nrhs ints each.  All scalars stay on the device, one set per
+ * column; a column whose residual is <= tol (at the start or after an iteration) is frozen there and then: its x and r are never
+ * written again (predicated writes) and its iteration count stands, so it ends with the iterate a single solve with check_every = 1
+ * returns whatever check_every the block uses; a column with a NaN residual is frozen with status SPARSH_ENUMERIC and the others go
+ * on.  The host reads the flags every params.check_every iterations and stops when every column is frozen or at params.max_iter
+ * (max_iters of the _dev form when > 0; never more than n iterations); the columns still running then get SPARSH_ENOCONV with x
+ * updated.  Returns SPARSH_OK if every column converged, else SPARSH_ENUMERIC if any column has it, else SPARSH_ENOCONV.
+ * SPARSH_EINVAL (with or without a device): nrhs outside 1..8, a NULL array, ldb or ldx below n, another method, a partitioned
+ * (multi-GPU) handle, params.precond_fp32, a smoother other than Jacobi.  SPARSH_ESTATE before sparsh_setup.  params.use_graph is
+ * accepted and ignored.  The block vectors (x, x2, b, r of every level; x, r, p, Ap of the loop; scalars, partial sums, histories)
+ * are allocated at the first block call for a width and replaced by a call with another width; sparsh_setup and sparsh_destroy
+ * free them.  sparsh_multi_info: the width in force and the device bytes held, both 0 until the first block call. */
+#define SPARSH_MAX_RHS 8
+int sparsh_solve_multi(sparsh_handle h, int method, int nrhs, const double *B, long ldb, double *X, long ldx, double *hist, int hist_cap,
+                       int *iters, int *status);
+/* the same on device arrays; *seconds (may be NULL): HIP-event time of the whole call on the engine's stream */
+int sparsh_solve_multi_dev(sparsh_handle h, int method, int nrhs, const double *B_dev, long ldb, double *X_dev, long ldx, int max_iters,
+                           double *hist, int hist_cap, int *iters, int *status, double *seconds);
+int sparsh_multi_info(sparsh_handle h, int *width, long *bytes);
+/* Operator-level hooks of the block kernels: column-major host arrays with ld = the level's rows (restrict: BC has the coarser
+ * level's rows; prolong: XC the coarser level's, XF in/out).  Each interleaves, runs the block launch of the V-cycle and
+ * de-interleaves.  spmv_dot: Y = A_l X and dots[c] = x_c . y_c; jacobi: `sweeps` sweeps in X (x_is_zero: X is taken as 0, not read);
+ * coarse: the coarsest level's solve (the dense inverse read once for all columns; a factored coarsest level is solved column by
+ * column); precond: one block V-cycle from a zero guess, Z = M R (refused like sparsh_solve_multi). */
+int sparsh_op_spmv_dot_multi(sparsh_handle h, int level, int nrhs, const double *X, double *Y, double *dots);
+int sparsh_op_residual_multi(sparsh_handle h, int level, int nrhs, const double *B, const double *X, double *R);
+int sparsh_op_jacobi_multi(sparsh_handle h, int level, int nrhs, const double *B, double *X, int sweeps, int x_is_zero);
+int sparsh_op_restrict_multi(sparsh_handle h, int level, int nrhs, const double *R, double *BC);
+int sparsh_op_prolong_multi(sparsh_handle h, int level, int nrhs, const double *XC, double *XF);
+int sparsh_op_coarse_multi(sparsh_handle h, int nrhs, const double *B, double *X);
+int sparsh_op_precond_multi(sparsh_handle h, int nrhs, const double *R, double *Z);
+/* average seconds of `reps` back-to-back block launches on the level's resident block buffers: op 0 = SpMV + dot, 1 = Jacobi
+ * sweeps ping-ponging (the counterpart of sparsh_bench_op 10) */
+int sparsh_bench_op_multi(sparsh_handle h, int op, int level, int nrhs, int reps, double *avg_seconds);
+
 /* device memory helpers so a host language needs no HIP binding of its own */
 int sparsh_dev_alloc(sparsh_handle h, long nbytes, void **out);
 int sparsh_dev_free(sparsh_handle h, void *p);

@@ -208,6 +208,18 @@ def _load():
         "sparsh_set_gmres_basis": (C.c_int, [H, C.c_int]),
         "sparsh_gmres_basis": (C.c_int, [H, c_int_p]),
         "sparsh_op_precond": (C.c_int, [H, c_dbl_p, c_dbl_p]),
+        "sparsh_solve_multi": (C.c_int, [H, C.c_int, C.c_int, c_dbl_p, C.c_long, c_dbl_p, C.c_long, c_dbl_p, C.c_int, c_int_p, c_int_p]),
+        "sparsh_solve_multi_dev": (C.c_int, [H, C.c_int, C.c_int, C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_int, c_dbl_p, C.c_int,
+                                             c_int_p, c_int_p, c_dbl_p]),
+        "sparsh_multi_info": (C.c_int, [H, c_int_p, C.POINTER(C.c_long)]),
+        "sparsh_op_spmv_dot_multi": (C.c_int, [H, C.c_int, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p]),
+        "sparsh_op_residual_multi": (C.c_int, [H, C.c_int, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p]),
+        "sparsh_op_jacobi_multi": (C.c_int, [H, C.c_int, C.c_int, c_dbl_p, c_dbl_p, C.c_int, C.c_int]),
+        "sparsh_op_restrict_multi": (C.c_int, [H, C.c_int, C.c_int, c_dbl_p, c_dbl_p]),
+        "sparsh_op_prolong_multi": (C.c_int, [H, C.c_int, C.c_int, c_dbl_p, c_dbl_p]),
+        "sparsh_op_coarse_multi": (C.c_int, [H, C.c_int, c_dbl_p, c_dbl_p]),
+        "sparsh_op_precond_multi": (C.c_int, [H, C.c_int, c_dbl_p, c_dbl_p]),
+        "sparsh_bench_op_multi": (C.c_int, [H, C.c_int, C.c_int, C.c_int, C.c_int, c_dbl_p]),
         "sparsh_op_gs_dot": (C.c_int, [H, C.c_int, C.c_int, C.c_int, c_dbl_p, c_dbl_p, C.c_int, c_dbl_p]),
         "sparsh_op_gs_update": (C.c_int, [H, C.c_int, C.c_int, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p, C.c_int, C.c_int, C.c_int, C.c_double,
                                           c_dbl_p, c_dbl_p, c_dbl_p, c_int_p]),
@@ -998,6 +1010,97 @@ class sp_matrix_mg:
         z = np.zeros_like(r)
         _check(lib.sparsh_op_precond(self._h, _dp(r), _dp(z)))
         return z
+
+    # -- a block of up to 8 right-hand sides (arrays of shape (n, nrhs); handed over column-major) ------------------
+    @staticmethod
+    def _block(a, rows=None):
+        a = np.asarray(a, dtype=np.float64)
+        if a.ndim != 2:
+            raise ValueError("a block is an array of shape (n, nrhs)")
+        if rows is not None and a.shape[0] != rows:
+            raise ValueError(f"the block has {a.shape[0]} rows, the level {rows}")
+        return np.array(a, dtype=np.float64, order="F")  # a column-major copy of the caller's array
+
+    def solve_multi(self, method, B, X, hist_cap=8192, allow=()):
+        """Block AMG-PCG: X (n, nrhs) holds the initial guesses on entry and the solutions on return.  Returns (histories, iters,
+        status, rc): histories[c] = column c's residual after every iteration it ran; SPARSH_ENOCONV / SPARSH_ENUMERIC are handed
+        back in rc and per column in status, other codes raise."""
+        Bf, Xf = self._block(B), self._block(X)
+        nrhs = Bf.shape[1]
+        hist = np.zeros((max(nrhs, 1), hist_cap))
+        iters, status = np.zeros(max(nrhs, 1), dtype=np.int32), np.zeros(max(nrhs, 1), dtype=np.int32)
+        m = METHODS[method] if isinstance(method, str) else method
+        rc = _check(lib.sparsh_solve_multi(self._h, m, nrhs, _dp(Bf), max(Bf.shape[0], 1), _dp(Xf), max(Xf.shape[0], 1), _dp(hist), hist_cap,
+                                           _ip(iters), _ip(status)), allow=(SPARSH_ENOCONV, SPARSH_ENUMERIC) + tuple(allow))
+        X[...] = Xf
+        return [hist[c, : min(iters[c], hist_cap)].copy() for c in range(nrhs)], iters[:nrhs].copy(), status[:nrhs].copy(), rc
+
+    def solve_multi_dev(self, method, nrhs, B_dev, ldb, X_dev, ldx, max_iters=0, hist_cap=8192):
+        """The same on column-major device arrays (dev_alloc / h2d).  Returns (histories, iters, status, seconds, rc)."""
+        hist = np.zeros((max(nrhs, 1), hist_cap))
+        iters, status = np.zeros(max(nrhs, 1), dtype=np.int32), np.zeros(max(nrhs, 1), dtype=np.int32)
+        sec = C.c_double()
+        m = METHODS[method] if isinstance(method, str) else method
+        rc = _check(lib.sparsh_solve_multi_dev(self._h, m, nrhs, B_dev, ldb, X_dev, ldx, max_iters, _dp(hist), hist_cap, _ip(iters),
+                                               _ip(status), C.byref(sec)), allow=(SPARSH_ENOCONV, SPARSH_ENUMERIC))
+        return [hist[c, : min(iters[c], hist_cap)].copy() for c in range(nrhs)], iters[:nrhs].copy(), status[:nrhs].copy(), sec.value, rc
+
+    def multi_info(self):
+        """Width in force and device bytes held by the block vectors (both 0 until the first block call)."""
+        w, b = C.c_int(), C.c_long()
+        _check(lib.sparsh_multi_info(self._h, C.byref(w), C.byref(b)))
+        return dict(width=w.value, bytes=b.value)
+
+    def op_spmv_dot_multi(self, level, X):
+        """(A_l X, [x_c . (A_l x_c)]) through the block launch PCG uses for A p and p.Ap."""
+        Xf = self._block(X, self.level_info(level)["nrow"])
+        Y, dots = np.zeros_like(Xf, order="F"), np.zeros(Xf.shape[1])
+        _check(lib.sparsh_op_spmv_dot_multi(self._h, int(level), Xf.shape[1], _dp(Xf), _dp(Y), _dp(dots)))
+        return Y, dots
+
+    def op_residual_multi(self, level, B, X):
+        n = self.level_info(level)["nrow"]
+        Bf, Xf = self._block(B, n), self._block(X, n)
+        R = np.zeros_like(Bf, order="F")
+        _check(lib.sparsh_op_residual_multi(self._h, int(level), Bf.shape[1], _dp(Bf), _dp(Xf), _dp(R)))
+        return R
+
+    def op_jacobi_multi(self, level, B, X, sweeps, x_is_zero=False):
+        n = self.level_info(level)["nrow"]
+        Bf, Xf = self._block(B, n), self._block(X, n)
+        _check(lib.sparsh_op_jacobi_multi(self._h, int(level), Bf.shape[1], _dp(Bf), _dp(Xf), int(sweeps), 1 if x_is_zero else 0))
+        return Xf
+
+    def op_restrict_multi(self, level, R):
+        Rf = self._block(R, self.level_info(level)["nrow"])
+        BC = np.zeros((self.level_info(level + 1)["nrow"], Rf.shape[1]), order="F")
+        _check(lib.sparsh_op_restrict_multi(self._h, int(level), Rf.shape[1], _dp(Rf), _dp(BC)))
+        return BC
+
+    def op_prolong_multi(self, level, XC, XF):
+        XCf, XFf = self._block(XC, self.level_info(level + 1)["nrow"]), self._block(XF, self.level_info(level)["nrow"])
+        _check(lib.sparsh_op_prolong_multi(self._h, int(level), XCf.shape[1], _dp(XCf), _dp(XFf)))
+        return XFf
+
+    def op_coarse_multi(self, B):
+        Bf = self._block(B, self.level_info(self.nlevels - 1)["nrow"])
+        X = np.zeros_like(Bf, order="F")
+        _check(lib.sparsh_op_coarse_multi(self._h, Bf.shape[1], _dp(Bf), _dp(X)))
+        return X
+
+    def op_precond_multi(self, R):
+        """Z = M R: one block V-cycle (Jacobi) from a zero guess, column c = the preconditioner applied to R[:, c]."""
+        Rf = self._block(R, self.nrow)
+        Z = np.zeros_like(Rf, order="F")
+        _check(lib.sparsh_op_precond_multi(self._h, Rf.shape[1], _dp(Rf), _dp(Z)))
+        return Z
+
+    def bench_op_multi(self, op, level=0, nrhs=8, reps=20):
+        """Average seconds of one block launch on the level's resident block buffers: "spmv_dot" (0) or "jacobi_pingpong_resident" (1)."""
+        ops = {"spmv_dot": 0, "jacobi_pingpong_resident": 1}
+        sec = C.c_double()
+        _check(lib.sparsh_bench_op_multi(self._h, ops[op] if isinstance(op, str) else op, int(level), int(nrhs), int(reps), C.byref(sec)))
+        return sec.value
 
     def op_dot(self, x, y):
         x = np.ascontiguousarray(x, dtype=np.float64)

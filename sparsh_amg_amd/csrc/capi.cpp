@@ -1790,4 +1790,176 @@ int sparsh_profile_read(sparsh_handle h, double *out4)
     return SPARSH_OK;
 }
 
+// ---- block of up to SPARSH_MAX_RHS right-hand sides ----
+
+// bad arguments and handles no setup can make fit are SPARSH_EINVAL with or without a device, so they are checked before readiness
+#define REQUIRE_MULTI_ARGS(h, nrhs)                                                                               \
+    if (!(h) || !(h)->eng) return fail(SPARSH_EINVAL, "null handle");                                             \
+    if ((nrhs) < 1 || (nrhs) > SPARSH_MAX_RHS) return fail(SPARSH_EINVAL, "nrhs must be 1 .. SPARSH_MAX_RHS (8)")
+
+#define REQUIRE_MULTI_FITS(h) \
+    if (const char *why_ = (h)->eng->multi_refusal()) return fail(SPARSH_EINVAL, why_)
+
+int sparsh_solve_multi_dev(sparsh_handle h, int method, int nrhs, const double *B_dev, long ldb, double *X_dev, long ldx, int max_iters,
+                           double *hist, int hist_cap, int *iters, int *status, double *seconds)
+{
+    REQUIRE_MULTI_ARGS(h, nrhs);
+    if (method != SPARSH_PCG) return fail(SPARSH_EINVAL, "block solves take SPARSH_PCG only");
+    if (!B_dev || !X_dev || !iters || !status || (hist_cap > 0 && !hist)) return fail(SPARSH_EINVAL, "NULL array");
+    if (hist_cap < 0) return fail(SPARSH_EINVAL, "hist_cap < 0");
+    if (ldb < h->eng->n0() || ldx < h->eng->n0()) return fail(SPARSH_EINVAL, "ldb and ldx must be at least the number of rows");
+    REQUIRE_MULTI_FITS(h);
+    REQUIRE_READY(h);
+    int rc = h->eng->solve_multi_dev(nrhs, B_dev, ldb, X_dev, ldx, max_iters, hist, hist_cap, iters, status, seconds);
+    if (rc != SPARSH_OK) return fail(rc, h->eng->error);
+    return rc;
+}
+
+int sparsh_solve_multi(sparsh_handle h, int method, int nrhs, const double *B, long ldb, double *X, long ldx, double *hist, int hist_cap,
+                       int *iters, int *status)
+{
+    REQUIRE_MULTI_ARGS(h, nrhs);
+    if (method != SPARSH_PCG) return fail(SPARSH_EINVAL, "block solves take SPARSH_PCG only");
+    if (!B || !X || !iters || !status || (hist_cap > 0 && !hist)) return fail(SPARSH_EINVAL, "NULL array");
+    if (hist_cap < 0) return fail(SPARSH_EINVAL, "hist_cap < 0");
+    if (ldb < h->eng->n0() || ldx < h->eng->n0()) return fail(SPARSH_EINVAL, "ldb and ldx must be at least the number of rows");
+    REQUIRE_MULTI_FITS(h);
+    REQUIRE_READY(h);
+    Engine &E = *h->eng;
+    const size_t n = (size_t)E.n0();
+    // the device copies are packed (leading dimension n): only the n rows of every column travel
+    DBuf db(E, n * nrhs), dx(E, n * nrhs);
+    if (!db.p || !dx.p) return fail(SPARSH_ENODEV, E.error);
+    for (int c = 0; c < nrhs; ++c) {
+        (void)hipMemcpy(db.p + (size_t)c * n, B + (size_t)c * ldb, n * 8, hipMemcpyHostToDevice);
+        (void)hipMemcpy(dx.p + (size_t)c * n, X + (size_t)c * ldx, n * 8, hipMemcpyHostToDevice);
+    }
+    int rc = E.solve_multi_dev(nrhs, db.p, (long)n, dx.p, (long)n, 0, hist, hist_cap, iters, status, nullptr);
+    (void)hipStreamSynchronize(E.stream());
+    for (int c = 0; c < nrhs; ++c) (void)hipMemcpy(X + (size_t)c * ldx, dx.p + (size_t)c * n, n * 8, hipMemcpyDeviceToHost);
+    if (rc != SPARSH_OK) return fail(rc, E.error);
+    return rc;
+}
+
+int sparsh_multi_info(sparsh_handle h, int *width, long *bytes)
+{
+    if (!h || !h->eng) return fail(SPARSH_EINVAL, "null handle");
+    if (width) *width = h->eng->multi_width_now();
+    if (bytes) *bytes = (long)h->eng->multi_bytes();
+    return SPARSH_OK;
+}
+
+namespace {
+
+// the operator hooks: column-major host blocks in (b: rows_b x nrhs, x: rows_x x nrhs; either may be absent) and out (rows_y x nrhs;
+// y_in: the output block is also an input)
+int op_multi_host(sparsh_handle h, int which, int level, int nrhs, const double *b, const double *x, double *y, bool y_in, double *dots,
+                  int sweeps, bool x_is_zero)
+{
+    Engine &E = *h->eng;
+    const int last = E.nlevels() - 1;
+    const int l = which == 5 ? last : (which == 6 ? 0 : level);
+    if ((which == 3 || which == 4) && l >= last) return fail(SPARSH_EINVAL, "no coarser level");
+    const size_t n = (size_t)E.level(l).n, nc = l < last ? (size_t)E.level(l + 1).n : 0;
+    const size_t rows_x = which == 4 ? nc : n, rows_y = which == 3 ? nc : n;
+    DBuf db(E, std::max<size_t>(n * nrhs, 1), nullptr), dx(E, std::max<size_t>(rows_x * nrhs, 1), nullptr), dy(E, rows_y * nrhs, y_in ? y : nullptr);
+    if (!db.p || !dx.p || !dy.p) return fail(SPARSH_ENODEV, E.error);
+    if (b) (void)hipMemcpy(db.p, b, n * nrhs * 8, hipMemcpyHostToDevice);
+    if (x) (void)hipMemcpy(dx.p, x, rows_x * nrhs * 8, hipMemcpyHostToDevice);
+    if (int rc = E.op_multi(which, l, nrhs, b ? db.p : nullptr, x ? dx.p : nullptr, dy.p, dots, sweeps, x_is_zero); rc != SPARSH_OK)
+        return fail(rc, E.error);
+    return done(E, dy.get(y));
+}
+
+}  // namespace
+
+#define REQUIRE_MULTI_OP(h, nrhs)  \
+    REQUIRE_MULTI_ARGS(h, nrhs);   \
+    REQUIRE_READY(h);              \
+    REQUIRE_SINGLE(h)
+
+int sparsh_op_spmv_dot_multi(sparsh_handle h, int level, int nrhs, const double *X, double *Y, double *dots)
+{
+    REQUIRE_MULTI_OP(h, nrhs);
+    REQUIRE_LEVEL(h, level);
+    if (!X || !Y || !dots) return fail(SPARSH_EINVAL, "NULL array");
+    return op_multi_host(h, 0, level, nrhs, nullptr, X, Y, false, dots, 0, false);
+}
+
+int sparsh_op_residual_multi(sparsh_handle h, int level, int nrhs, const double *B, const double *X, double *R)
+{
+    REQUIRE_MULTI_OP(h, nrhs);
+    REQUIRE_LEVEL(h, level);
+    if (!B || !X || !R) return fail(SPARSH_EINVAL, "NULL array");
+    return op_multi_host(h, 1, level, nrhs, B, X, R, false, nullptr, 0, false);
+}
+
+int sparsh_op_jacobi_multi(sparsh_handle h, int level, int nrhs, const double *B, double *X, int sweeps, int x_is_zero)
+{
+    REQUIRE_MULTI_OP(h, nrhs);
+    REQUIRE_LEVEL(h, level);
+    if (!B || !X) return fail(SPARSH_EINVAL, "NULL array");
+    if (sweeps < 0) return fail(SPARSH_EINVAL, "sweeps < 0");
+    return op_multi_host(h, 2, level, nrhs, B, x_is_zero ? nullptr : X, X, false, nullptr, sweeps, x_is_zero != 0);
+}
+
+int sparsh_op_restrict_multi(sparsh_handle h, int level, int nrhs, const double *R, double *BC)
+{
+    REQUIRE_MULTI_OP(h, nrhs);
+    REQUIRE_LEVEL(h, level);
+    if (!R || !BC) return fail(SPARSH_EINVAL, "NULL array");
+    return op_multi_host(h, 3, level, nrhs, nullptr, R, BC, false, nullptr, 0, false);
+}
+
+int sparsh_op_prolong_multi(sparsh_handle h, int level, int nrhs, const double *XC, double *XF)
+{
+    REQUIRE_MULTI_OP(h, nrhs);
+    REQUIRE_LEVEL(h, level);
+    if (!XC || !XF) return fail(SPARSH_EINVAL, "NULL array");
+    return op_multi_host(h, 4, level, nrhs, nullptr, XC, XF, true, nullptr, 0, false);
+}
+
+int sparsh_op_coarse_multi(sparsh_handle h, int nrhs, const double *B, double *X)
+{
+    REQUIRE_MULTI_OP(h, nrhs);
+    if (!B || !X) return fail(SPARSH_EINVAL, "NULL array");
+    return op_multi_host(h, 5, 0, nrhs, B, nullptr, X, false, nullptr, 0, false);
+}
+
+int sparsh_op_precond_multi(sparsh_handle h, int nrhs, const double *R, double *Z)
+{
+    REQUIRE_MULTI_ARGS(h, nrhs);
+    if (!R || !Z) return fail(SPARSH_EINVAL, "NULL array");
+    REQUIRE_MULTI_FITS(h);
+    REQUIRE_READY(h);
+    return op_multi_host(h, 6, 0, nrhs, R, nullptr, Z, false, nullptr, 0, false);
+}
+
+int sparsh_bench_op_multi(sparsh_handle h, int op, int level, int nrhs, int reps, double *avg_seconds)
+{
+    REQUIRE_MULTI_ARGS(h, nrhs);
+    if (op < 0 || op > 1) return fail(SPARSH_EINVAL, "unknown op");
+    if (reps <= 0 || !avg_seconds) return fail(SPARSH_EINVAL, "bad reps");
+    REQUIRE_READY(h);
+    REQUIRE_SINGLE(h);
+    REQUIRE_LEVEL(h, level);
+    Engine &E = *h->eng;
+    if (int rc = E.multi_reserve(nrhs); rc != SPARSH_OK) return fail(rc, E.error);
+    hipStream_t st = E.stream();
+    for (int i = 0; i < 3; ++i) E.bench_multi_launch(op, level);
+    hipEvent_t e0, e1;
+    (void)hipEventCreate(&e0);
+    (void)hipEventCreate(&e1);
+    (void)hipEventRecord(e0, st);
+    for (int i = 0; i < reps; ++i) E.bench_multi_launch(op, level);
+    (void)hipEventRecord(e1, st);
+    (void)hipEventSynchronize(e1);
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, e0, e1);
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    *avg_seconds = ms * 1e-3 / reps;
+    return done(E, true);
+}
+
 }  // extern "C"

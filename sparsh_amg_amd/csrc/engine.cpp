@@ -1200,6 +1200,7 @@ int Engine::setup(const sparsh_params &p)
     gm_basis_ = gm_part_ = gm_state_ = gm_w_ = nullptr;  // (freed with the rest: the next GMRES solve reallocates the basis)
     gm_basisf_ = nullptr;
     gm_bytes_ = 0;
+    multi_forget();  // (the block vectors too: the next block call reallocates them)
     sor_.clear();
     cheb_.clear();  // (the d vectors are freed with the rest)
     coarse_.release();

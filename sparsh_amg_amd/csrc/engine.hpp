@@ -311,6 +311,26 @@ public:
     // the device block behind a GmresState, zeroed on the stream, and s pointing into it (nullptr: error set); free with dfree
     double *gmres_state_alloc(GmresState &s);
 
+    // ---- block of up to 8 right-hand sides (engine_multi.cpp).  Blocks are row-interleaved with width
+    // multi_width(nrhs); callers hand over column-major device arrays.  Single-GPU handles, Jacobi smoother, fp64 cycle.
+    // why a block call cannot run on this handle (nullptr: it can); needs no device
+    const char *multi_refusal() const;
+    // the block vectors of every level and of the Krylov loop for nrhs columns, allocated on first use and replaced when the width
+    // changes; SPARSH_* code
+    int multi_reserve(int nrhs);
+    void multi_release();
+    int multi_width_now() const { return mw_; }
+    size_t multi_bytes() const { return multi_bytes_; }
+    // block PCG on column-major device arrays: X = initial guesses in, solutions out; hist[c * hist_cap + k], iters[c], status[c]
+    int solve_multi_dev(int nrhs, const double *B, long ldb, double *X, long ldx, int max_iters, double *hist, int hist_cap, int *iters,
+                        int *status, double *seconds);
+    // operator-level hooks on column-major device arrays (ld = rows of the level): each interleaves, runs the block launch and
+    // de-interleaves.  which: 0 Y = A X with dots, 1 residual, 2 Jacobi leg (sweeps, x_is_zero), 3 restriction, 4 prolongation
+    // (X = coarse block, Y = fine block in/out), 5 coarse solve, 6 one vcycle_multi from a zero guess (level 0)
+    int op_multi(int which, int l, int nrhs, const double *B, const double *X, double *Y, double *dots, int sweeps, bool x_is_zero);
+    // bench: op 0 = SpMV + dot, 1 = Jacobi sweeps ping-ponging, on level l's block buffers of the width in force
+    int bench_multi_launch(int op, int l);
+
     // device memory helpers
     void *dalloc(size_t bytes);
     void dfree(void *p);
@@ -403,6 +423,35 @@ private:
     GmresState gm_;
     long gm_stride_ = 0;
     size_t gm_bytes_ = 0;
+
+    // block vectors of one level (interleaved, n * width doubles each); level 0 has no b: the cycle's right-hand side is the
+    // Krylov residual
+    struct MultiLevel {
+        double *x = nullptr, *x2 = nullptr, *b = nullptr, *r = nullptr;
+    };
+    // one V(nu,nu) Jacobi cycle from a zero guess on a block: the order of vcycle_plain, nothing fused; result in mlev_[0].x
+    void vcycle_multi(const double *b0);
+    // one Jacobi leg of `sweeps` sweeps on level l: iterate in x on entry and exit (x_zero: taken as 0), x2 is scratch; the two
+    // pointers are swapped as the sweeps ping-pong
+    void multi_leg(int l, const double *b, double *&x, double *&x2, int sweeps, bool x_zero);
+    void multi_residual(int l, const double *b, const double *x, double *r);
+    void multi_restrict(int l, const double *r, double *bc);
+    void multi_prolong(int l, const double *xc, double *xf);
+    void multi_coarse(const double *b, double *x);
+    int multi_spmv_dot(int l, const double *x, double *y, double *partial);
+    void multi_forget();  // the buffers went with allocs_ (setup): drop the pointers
+    int mw_ = 0;          // width in force (0: nothing allocated)
+    size_t multi_bytes_ = 0;
+    std::vector<MultiLevel> mlev_;
+    double *mx_ = nullptr, *mr_ = nullptr, *mp_ = nullptr, *mAp_ = nullptr;  // block PCG: iterate, residual, direction, A p
+    double *mpart0_ = nullptr, *mpart1_ = nullptr;                          // kMultiMax * mpart_cap_ partial sums each
+    int mpart_cap_ = 0;
+    double *mcs_in_ = nullptr, *mcs_out_ = nullptr;  // factored coarsest level: the block as contiguous vectors for CoarseSolver::solve
+    double *mhist_ = nullptr;                        // kMultiMax * hist_cap_dev_ residual histories
+    int *mflags_ = nullptr;                          // frozen, iters, status: kMultiMax ints each
+    MultiState ms_;
+    int mflip_ = 0;  // bench_multi_launch
+    std::vector<void *> multi_allocs_;
 
     std::unique_ptr<Comm> comm_;
     std::vector<Partition> parts_;  // row partition of every level

@@ -386,4 +386,52 @@ void launch_gmres_step(int j, const double *ww_partial, int nblk, const GmresSta
 // ny = -R^{-1} g over the first k columns (zero pivot: that y is 0)
 void launch_gmres_solve(int k, const GmresState &s, hipStream_t st);
 
+// ---- block of up to 8 right-hand sides (multi_kernels.hip).  A block of W = 2, 4 or 8 vectors is row-interleaved:
+// element (row i, column c) at v[i * W + c].  Per column the arithmetic is that of the single-vector kernels above; reducing launches
+// write one partial per column and workgroup to partial[c * nblk + workgroup] and return nblk.
+constexpr int kMultiMax = 8;  // SPARSH_MAX_RHS
+inline int multi_width(int nrhs) { return nrhs <= 2 ? 2 : (nrhs <= 4 ? 4 : 8); }
+struct MultiArgs {
+    const double *x = nullptr;  // input block (gathered)
+    const double *b = nullptr;  // RESID / JACOBI (may be y: element i is read before it is written, by the same thread)
+    const double *d = nullptr;  // JACOBI: the level's diagonal, one entry per row
+    double *y = nullptr;        // output block (ADD: read and written)
+    double omega = 0.0;
+    double *partial = nullptr;  // SPMV_DOT: W * nblk partial sums of x_c . (A x)_c
+};
+// OP_SPMV, OP_SPMV_DOT, OP_RESID, OP_JACOBI or OP_ADD on A's CSR arrays and row-block records; a row longer than kStreamNnz is summed
+// in stored order, chunk by chunk.  Blocks must be 16-byte aligned (a lane owns two neighbouring columns).  multi_placement: the
+// non-temporal / XCD-remap choice of the launch under cfg, the rule of csr_placement applied to the bytes one block sweep streams.
+int launch_csr_multi(const DevCsr &A, int W, CsrOp op, const MultiArgs &a, hipStream_t st, const KernelConfig &cfg);
+void multi_placement(const DevCsr &A, int W, const KernelConfig &cfg, bool *nt, int *remap);
+// column-major (column c at B + c * ld) <-> interleaved; the padding columns nrhs .. W - 1 are written as zeros / not read
+void launch_interleave(int n, int nrhs, int W, const double *B, long ld, double *v, hipStream_t st);
+void launch_deinterleave(int n, int nrhs, int W, const double *v, double *X, long ld, hipStream_t st);
+// launch_jacobi_zero / launch_prolong_agg / launch_restrict_agg / launch_gemv per column (gemv: the inverse is read once for all columns)
+void launch_jacobi_zero_multi(int n, int W, const double *b, const double *d, double dconst, double omega, double *x, hipStream_t st);
+void launch_prolong_agg_multi(int n, int W, const int *agg, const double *xc, double *xf, hipStream_t st);
+void launch_restrict_agg_multi(int nc, int W, const int *rowptr, const int *col, const double *r, double *bc, hipStream_t st);
+void launch_gemv_multi(int n, int W, const double *M, const double *b, double *x, hipStream_t st);
+// device-resident state of block PCG: scal[slot * kMultiMax + c], and per column whether it is frozen, its iteration count and status
+enum MultiSlot : int { MS_RZ = 0, MS_PAP, MS_ALPHA, MS_NALPHA, MS_BETA, MS_RES, MS_TMP, MS_COUNT };
+constexpr int kMultiStatusNumeric = 1;  // status of a column frozen on a NaN residual (0: converged or still running)
+struct MultiState {
+    double *scal = nullptr;  // MS_COUNT * kMultiMax
+    int *frozen = nullptr, *iters = nullptr, *status = nullptr;  // kMultiMax each
+};
+enum MultiFin : int {
+    MFIN_STORE = 0,    // scal[slot][c] = sum0
+    MFIN_INIT = 1,     // res = sqrt(sum0); freezes the padding columns and the columns with res <= tol (iters 0) or a NaN
+    MFIN_ALPHA = 2,    // FIN_PCG_ALPHA per column
+    MFIN_BETA_RES = 3  // FIN_PCG_BETA_RES per column; on a column that is not frozen: hist[c * hist_cap + it] = res, iters = it + 1, and the freeze
+};
+int launch_dot_multi(int n, int W, const double *x, const double *y, double *partial, hipStream_t st);
+// x += alpha_c p ; r += (-alpha_c) Ap on the columns that are not frozen (predicated writes) ; partials of r.r
+int launch_cg_update_multi(int n, int W, const MultiState &s, const double *p, const double *Ap, double *x, double *r, double *partial, hipStream_t st);
+// p = 1.0 z + beta_c p on the columns that are not frozen
+void launch_p_update_multi(int n, int W, const MultiState &s, const double *z, double *p, hipStream_t st);
+// one workgroup: p0 (W x n0 partials) and p1 (W x n1, may be nullptr) added per column in a fixed order, then `code`
+void launch_finalize_multi(MultiFin code, int W, int nrhs, const double *p0, int n0, const double *p1, int n1, const MultiState &s, int slot,
+                           double tol, double *hist, int hist_cap, int it, hipStream_t st);
+
 }  // namespace sparsh
