@@ -64,6 +64,7 @@ void Solver_PBiCG_3(sp_matrix_mg &A, double *&b, double *&x);
 void Solver_PBiCG_4(sp_matrix_mg &A, double *&b, double *&x);
 void Solver_GMRES_1(sp_matrix_mg &A, double *&b, double *&x);           // restarted GMRES(30); not in the reference
 void Solver_PGMRES_1(sp_matrix_mg &A, double *&b, double *&x);          // ... right-preconditioned with the V-cycle
+void Solver_FCG_1(sp_matrix_mg &A, double *&b, double *&x);             // flexible preconditioned CG; not in the reference
 void coarsening_2(sp_matrix_mg &A, double *&b, double *&x);             // SOR test stub: not in this build
 
 #endif

@@ -38,6 +38,7 @@ extern "C" {
 #define SPARSH_PBICG 4  /* Solver_PBiCG_1..4                (src/AMG_main_solvers.cpp:358-458) */
 #define SPARSH_GMRES 5  /* restarted GMRES without a preconditioner (sparsh_set_gmres) */
 #define SPARSH_PGMRES 6 /* restarted GMRES, right-preconditioned with one V-cycle from a zero guess: the z = M v of SPARSH_PBICG */
+#define SPARSH_FCG 7    /* flexible preconditioned CG (Notay's FCG(1)): the Krylov method that takes the K-cycle; see "W- and K-cycles" below */
 
 /* Smoother of the V-cycle (sparsh_set_smoother). */
 #define SPARSH_SMOOTH_JACOBI 0  /* weighted Jacobi, parallel::jacobi_smoother (default) */
@@ -548,6 +549,53 @@ int sparsh_set_chebyshev(sparsh_handle h, double ratio, int lanczos_steps);
 int sparsh_set_chebyshev_lmax(sparsh_handle h, int level, double lmax);
 int sparsh_level_chebyshev(sparsh_handle h, int level, double *lmax, double *lmin, double *gershgorin, double *lanczos);
 int sparsh_op_cheby(sparsh_handle h, int level, const double *b, double *x, int degree, int x_is_zero);
+
+/* ---- W- and K-cycles at chosen levels, and flexible CG ----
+ * Opt-in: under SPARSH_CYCLE_V (the default) every path, launch and bit is what it was.  Level l is a "WK level" when 1 <= l < last and
+ * l % stride == 0; the coarsest level is solved exactly and never recurses.  A level is visited 2^(number of WK levels <= l) times per cycle.
+ * The cycle, with the legs of the handle's current smoother and nothing fused across launches (Jacobi: params.sweeps plain sweeps,
+ * SOR in its chosen order, Chebyshev of its degree -- exactly what sparsh_op_jacobi, sparsh_op_sor and sparsh_op_cheby compute):
+ *   cycle(l, b), from a zero guess (level 0 of the stand-alone iteration: from the caller's x):
+ *     l last: x = coarse solve of b.
+ *     else:   x = pre-leg(b) ; r = b - A_l x ; b_c = R r ; x_c = solve_coarse(l + 1, b_c) ; x += P x_c ; x = post-leg(b, x).
+ *   solve_coarse(l, b):
+ *     not a WK level, or kind V:  cycle(l, b).
+ *     W:  c = cycle(l, b) ; r = b - A_l c ; d = cycle(l, r) ; x = c + d.
+ *     K:  c = cycle(l, b) ; v = A_l c ; rho1 = c.v ; alpha1 = c.b ; q = alpha1 / rho1 ;
+ *         r_i = b_i - q v_i ; d = cycle(l, r) ; w = A_l d ;
+ *         gamma = d.v ; beta = d.w ; alpha2 = d.r ; rho2 = beta - gamma^2 / rho1 ;
+ *         k1 = q - gamma alpha2 / (rho1 rho2) ; k2 = alpha2 / rho2 ; x_i = k1 c_i + k2 d_i.
+ *         Guards, decided on the device without a host read: rho1 not finite and > 0: q = 1, k1 = 1, k2 = 1 (the W step; rho2 is then not
+ *         formed and reported as 0); else rho2 not finite and > 0: k1 = q, k2 = 0.  No early exit after the first step: the launch
+ *         sequence does not depend on data.  Every product and sum of the two vector updates is rounded on its own (no contraction);
+ *         the five sums are per-workgroup partial sums added in a fixed order (no atomics, bitwise reproducible run to run).
+ * sparsh_set_cycle: kind SPARSH_CYCLE_V / _W / _K; stride 1..8, 0 = the default of 3; anything else is SPARSH_EINVAL and changes nothing.
+ * Callable before or after sparsh_setup, needs no device, drops a captured graph.  Selecting V again restores the V-cycle exactly.
+ * What accepts what.  W: every method that takes a preconditioner, the stand-alone SPARSH_AMG iteration and sparsh_op_precond (under W
+ * params.use_graph is accepted and ignored).  K is not a fixed linear operator: SPARSH_FCG, SPARSH_AMG and sparsh_op_precond only;
+ * SPARSH_PCG, SPARSH_PBICG, SPARSH_PGMRES and the stepwise calls return SPARSH_EINVAL and name SPARSH_FCG.  W and K are refused
+ * (SPARSH_EINVAL) on partitioned (multi-GPU) handles, with params.precond_fp32 and by sparsh_solve_multi.  A configuration with more
+ * than 1024 level visits per cycle, all levels together, is SPARSH_EINVAL at the solve; the message names the strides that fit.
+ * sparsh_cycle_info / sparsh_level_cycle: the counts above, available after sparsh_setup_host (no device; any pointer may be NULL;
+ * before it nlevels_wk and level_visits are 0).  bytes = device memory held for the cycle's extra vectors (per WK level c and r, under
+ * K also v, plus the K step's partial sums and scalars): allocated at first use, 0 until then and after every sparsh_setup; freed by
+ * sparsh_setup and sparsh_destroy.
+ * SPARSH_FCG: r = b - A x ; z = M r ; p = z ; rho = z.r ; then per iteration q = A p ; sigma = p.q ; alpha = rho / sigma ; x += alpha p ;
+ * r -= alpha q ; hist = ||r|| ; z = M r ; rho = z.r and tau = z.q in one pass ; beta = -tau / sigma ; p = z + beta p.  Equal to
+ * SPARSH_PCG in exact arithmetic when M is fixed, linear and symmetric.  Scalars stay on the device; check_every, max_iter, the history,
+ * SPARSH_ENOCONV and SPARSH_ENUMERIC behave as in SPARSH_PBICG; params.use_graph is accepted and ignored.  One GPU, fp64 recurrences; takes
+ * every cycle, every smoother (SOR under the symmetric-order rule of SPARSH_PCG) and the fp32 preconditioner.  The stepwise
+ * sparsh_krylov_* calls refuse it with SPARSH_EINVAL.
+ * sparsh_op_kstep (test hook): the K step's own launches on host vectors of the level's rows with c and d given -- v = A c, the two
+ * sums, q, r ; w = A d, the three sums, the scalars, x; returns r, x and scal8 = {rho1, alpha1, gamma, beta, alpha2, rho2, k1, k2}.  Any
+ * level is valid, the coarsest included. */
+#define SPARSH_CYCLE_V 0 /* default */
+#define SPARSH_CYCLE_W 1
+#define SPARSH_CYCLE_K 2
+int sparsh_set_cycle(sparsh_handle h, int kind, int stride);
+int sparsh_cycle_info(sparsh_handle h, int *kind, int *stride, int *nlevels_wk, long *level_visits, long *bytes);
+int sparsh_level_cycle(sparsh_handle h, int level, int *is_wk, long *visits);
+int sparsh_op_kstep(sparsh_handle h, int level, const double *b, const double *c, const double *d, double *r, double *x, double *scal8);
 
 /* ---- a block of up to SPARSH_MAX_RHS right-hand sides in one AMG-PCG run ----
  * k systems with one matrix -- load cases, solution components, columns of a block method -- solved together: every kernel of the

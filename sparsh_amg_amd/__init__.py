@@ -24,8 +24,12 @@ LIB_PATH = os.path.join(_HERE, "libsparsh_amg.so")
 
 SPARSH_AMG, SPARSH_CG, SPARSH_PCG, SPARSH_BICG, SPARSH_PBICG = 0, 1, 2, 3, 4
 SPARSH_GMRES, SPARSH_PGMRES = 5, 6
+SPARSH_FCG = 7
 METHODS = {"amg": SPARSH_AMG, "cg": SPARSH_CG, "pcg": SPARSH_PCG, "bicg": SPARSH_BICG, "pbicg": SPARSH_PBICG,
            "gmres": SPARSH_GMRES, "pgmres": SPARSH_PGMRES}
+FLEXIBLE_METHODS = {"fcg": SPARSH_FCG}  # methods whose preconditioner may change between applications (the K-cycle)
+SPARSH_CYCLE_V, SPARSH_CYCLE_W, SPARSH_CYCLE_K = 0, 1, 2
+CYCLES = {"v": SPARSH_CYCLE_V, "w": SPARSH_CYCLE_W, "k": SPARSH_CYCLE_K}
 SPARSH_SMOOTH_JACOBI, SPARSH_SMOOTH_SOR, SPARSH_SMOOTH_CHEBYSHEV = 0, 1, 3
 SPARSH_SOR_FORWARD, SPARSH_SOR_SYMMETRIC = 0, 1
 SPARSH_BASIS_FP64, SPARSH_BASIS_FP32 = 0, 1
@@ -33,6 +37,15 @@ GMRES_BASES = {"fp64": SPARSH_BASIS_FP64, "fp32": SPARSH_BASIS_FP32}
 SMOOTHERS = {"jacobi": SPARSH_SMOOTH_JACOBI, "sor": SPARSH_SMOOTH_SOR, "chebyshev": SPARSH_SMOOTH_CHEBYSHEV}
 SOR_ORDERS = {"forward": SPARSH_SOR_FORWARD, "symmetric": SPARSH_SOR_SYMMETRIC}
 SPARSH_OK, SPARSH_EINVAL, SPARSH_ENODEV, SPARSH_ESTATE, SPARSH_ENUMERIC, SPARSH_ENOCONV, SPARSH_ECOMM = 0, -1, -2, -3, -4, -5, -6
+
+
+
+def _method(method):
+    """method code of a name ("pcg", "fcg", ...) or the code itself"""
+    if isinstance(method, str):
+        return METHODS[method] if method in METHODS else FLEXIBLE_METHODS[method]
+    return method
+
 
 c_int_p = C.POINTER(C.c_int)
 c_dbl_p = C.POINTER(C.c_double)
@@ -203,6 +216,10 @@ def _load():
         "sparsh_level_chebyshev": (C.c_int, [H, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p]),
         "sparsh_op_cheby": (C.c_int, [H, C.c_int, c_dbl_p, c_dbl_p, C.c_int, C.c_int]),
         "sparsh_profile_read": (C.c_int, [H, c_dbl_p]),
+        "sparsh_set_cycle": (C.c_int, [H, C.c_int, C.c_int]),
+        "sparsh_cycle_info": (C.c_int, [H, c_int_p, c_int_p, c_int_p, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
+        "sparsh_level_cycle": (C.c_int, [H, C.c_int, c_int_p, C.POINTER(C.c_long)]),
+        "sparsh_op_kstep": (C.c_int, [H, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p]),
         "sparsh_set_gmres": (C.c_int, [H, C.c_int]),
         "sparsh_gmres_info": (C.c_int, [H, c_int_p, C.POINTER(C.c_long)]),
         "sparsh_set_gmres_basis": (C.c_int, [H, C.c_int]),
@@ -548,6 +565,37 @@ class sp_matrix_mg:
         _check(lib.sparsh_level_chebyshev(self._h, int(level), *[C.byref(o) for o in out]))
         return dict(zip(("lmax", "lmin", "gershgorin", "lanczos"), (o.value for o in out)))
 
+    # -- W- and K-cycles ------------------------------------------------------------------------
+    def set_cycle(self, kind="v", stride=0):
+        """Cycle of the preconditioner: "v" (default), "w" or "k" (Notay's K-cycle: two flexible-CG steps) at every stride-th level
+        (1..8, 0 = the default of 3).  "k" is not a fixed linear operator: solve it with "fcg" (or "amg")."""
+        k = CYCLES[kind.lower()] if isinstance(kind, str) else int(kind)
+        _check(lib.sparsh_set_cycle(self._h, k, int(stride)))
+        return self
+
+    def cycle_info(self):
+        """dict(kind, stride, nlevels_wk, level_visits, bytes): levels that recurse twice and level visits of one cycle (0 before the
+        host setup), device bytes held for the cycle's extra vectors (0 until first use)."""
+        k, st, nwk = C.c_int(), C.c_int(), C.c_int()
+        vis, nbytes = C.c_long(), C.c_long()
+        _check(lib.sparsh_cycle_info(self._h, C.byref(k), C.byref(st), C.byref(nwk), C.byref(vis), C.byref(nbytes)))
+        return dict(kind={v: n for n, v in CYCLES.items()}[k.value], stride=st.value, nlevels_wk=nwk.value, level_visits=vis.value,
+                    bytes=nbytes.value)
+
+    def level_cycle(self, level):
+        """(is_wk, visits) of a level under the current cycle; needs the host setup only."""
+        wk, vis = C.c_int(), C.c_long()
+        _check(lib.sparsh_level_cycle(self._h, int(level), C.byref(wk), C.byref(vis)))
+        return bool(wk.value), vis.value
+
+    def op_kstep(self, level, b, c, d):
+        """(r, x, scal8) of the K step's own launches on a level with c and d given (host vectors); scal8 = rho1, alpha1, gamma, beta,
+        alpha2, rho2, k1, k2."""
+        b, c, d = (np.ascontiguousarray(a, dtype=np.float64) for a in (b, c, d))
+        r, x, s = np.zeros_like(b), np.zeros_like(b), np.zeros(8)
+        _check(lib.sparsh_op_kstep(self._h, int(level), _dp(b), _dp(c), _dp(d), _dp(r), _dp(x), _dp(s)))
+        return r, x, s
+
     # -- restarted GMRES -----------------------------------------------------------------------
     def set_gmres(self, restart=0, basis=None):
         """Restart length of "gmres" / "pgmres": 1..64, 0 = the default of 30.  basis: "fp64" (the default of a handle) or "fp32" =
@@ -843,7 +891,7 @@ class sp_matrix_mg:
         assert x.dtype == np.float64 and x.flags.c_contiguous
         hist = np.zeros(hist_cap)
         n = C.c_int()
-        m = METHODS[method] if isinstance(method, str) else method
+        m = _method(method)
         rc = _check(lib.sparsh_solve(self._h, m, _dp(b), _dp(x), _dp(hist), hist_cap, C.byref(n)), allow=(SPARSH_ENOCONV,) + tuple(allow))
         return hist[: min(n.value, hist_cap)].copy(), rc
 
@@ -873,7 +921,7 @@ class sp_matrix_mg:
         hist = np.zeros(hist_cap)
         n = C.c_int()
         sec = C.c_double()
-        m = METHODS[method] if isinstance(method, str) else method
+        m = _method(method)
         rc = _check(
             lib.sparsh_solve_dev(self._h, m, b_dev, x_dev, max_iters, _dp(hist), hist_cap, C.byref(n), C.byref(sec)),
             allow=(SPARSH_ENOCONV,),
@@ -881,7 +929,7 @@ class sp_matrix_mg:
         return hist[: min(n.value, hist_cap)].copy(), n.value, sec.value, rc
 
     def krylov_init_dev(self, method, b_dev, x_dev):
-        m = METHODS[method] if isinstance(method, str) else method
+        m = _method(method)
         _check(lib.sparsh_krylov_init_dev(self._h, m, b_dev, x_dev))
 
     def krylov_step_dev(self, nsteps):
@@ -1029,7 +1077,7 @@ class sp_matrix_mg:
         nrhs = Bf.shape[1]
         hist = np.zeros((max(nrhs, 1), hist_cap))
         iters, status = np.zeros(max(nrhs, 1), dtype=np.int32), np.zeros(max(nrhs, 1), dtype=np.int32)
-        m = METHODS[method] if isinstance(method, str) else method
+        m = _method(method)
         rc = _check(lib.sparsh_solve_multi(self._h, m, nrhs, _dp(Bf), max(Bf.shape[0], 1), _dp(Xf), max(Xf.shape[0], 1), _dp(hist), hist_cap,
                                            _ip(iters), _ip(status)), allow=(SPARSH_ENOCONV, SPARSH_ENUMERIC) + tuple(allow))
         X[...] = Xf
@@ -1040,7 +1088,7 @@ class sp_matrix_mg:
         hist = np.zeros((max(nrhs, 1), hist_cap))
         iters, status = np.zeros(max(nrhs, 1), dtype=np.int32), np.zeros(max(nrhs, 1), dtype=np.int32)
         sec = C.c_double()
-        m = METHODS[method] if isinstance(method, str) else method
+        m = _method(method)
         rc = _check(lib.sparsh_solve_multi_dev(self._h, m, nrhs, B_dev, ldb, X_dev, ldx, max_iters, _dp(hist), hist_cap, _ip(iters),
                                                _ip(status), C.byref(sec)), allow=(SPARSH_ENOCONV, SPARSH_ENUMERIC))
         return [hist[c, : min(iters[c], hist_cap)].copy() for c in range(nrhs)], iters[:nrhs].copy(), status[:nrhs].copy(), sec.value, rc
@@ -1196,6 +1244,7 @@ Solver_BiCG_1 = _entry("bicg")
 Solver_PBiCG_1 = Solver_PBiCG_2 = Solver_PBiCG_3 = Solver_PBiCG_4 = _entry("pbicg")
 Solver_GMRES_1 = _entry("gmres")
 Solver_PGMRES_1 = _entry("pgmres")
+Solver_FCG_1 = _entry("fcg")
 
 
 def readcoo(matrixfile: str, rhsfile: str):

@@ -435,6 +435,7 @@ SPARSH_KRYLOV_ENTRY(Solver_PBiCG_3, SPARSH_PBICG)
 SPARSH_KRYLOV_ENTRY(Solver_PBiCG_4, SPARSH_PBICG)
 SPARSH_KRYLOV_ENTRY(Solver_GMRES_1, SPARSH_GMRES)
 SPARSH_KRYLOV_ENTRY(Solver_PGMRES_1, SPARSH_PGMRES)
+SPARSH_KRYLOV_ENTRY(Solver_FCG_1, SPARSH_FCG)
 
 // ------------------------------------------------------------------------------ solver objects
 // AMG_solver / AMG_GPU1_solver / AMG_GPU_solver (include/AMG_phases.hpp, AMG_gpu_phases*.hpp of the

@@ -91,6 +91,11 @@ struct DBuf {
         ((h)->eng->distributed() || ((h)->eng->comm() && (h)->eng->comm()->size > 1)))                                             \
     return fail(SPARSH_EINVAL, "GMRES is not available on a partitioned (multi-GPU) handle: its j + 2 sums per step need a wider all-reduce")
 
+// likewise: a method the handle's cycle cannot serve (the K-cycle under a Krylov method that needs a fixed operator, W or K on a
+// partitioned handle or with the fp32 preconditioner, more level visits than the cap)
+#define REQUIRE_CYCLE_FITS(h, method) \
+    if ((h) && (h)->eng && (h)->eng->cycle_check(method) != SPARSH_OK) return fail(SPARSH_EINVAL, (h)->eng->error)
+
 #define REQUIRE_HOST(h)                                               \
     if (!(h) || !(h)->eng) return fail(SPARSH_EINVAL, "null handle"); \
     if (!(h)->eng->host_ready()) return fail(SPARSH_ESTATE, "sparsh_setup / sparsh_setup_host has not been called (or failed)")
@@ -821,6 +826,7 @@ double sparsh_setup_seconds(sparsh_handle h) { return (h && h->eng) ? h->eng->se
 
 int sparsh_vcycle(sparsh_handle h, const double *b, double *x, int iterations, double *hist, int hist_cap, int *ncycles)
 {
+    REQUIRE_CYCLE_FITS(h, SPARSH_AMG);
     REQUIRE_READY(h);
     Engine &E = *h->eng;
     const size_t n = (size_t)E.local_n0();  // multi-GPU: this rank's block of level 0
@@ -834,6 +840,7 @@ int sparsh_vcycle(sparsh_handle h, const double *b, double *x, int iterations, d
 
 int sparsh_vcycle_dev(sparsh_handle h, const double *b_dev, double *x_dev, int iterations, double *hist, int hist_cap, int *ncycles)
 {
+    REQUIRE_CYCLE_FITS(h, SPARSH_AMG);
     REQUIRE_READY(h);
     int rc = h->eng->amg_solve_dev(b_dev, x_dev, iterations, hist, hist_cap, ncycles);
     if (rc != SPARSH_OK) return fail(rc, h->eng->error);
@@ -843,6 +850,7 @@ int sparsh_vcycle_dev(sparsh_handle h, const double *b_dev, double *x_dev, int i
 int sparsh_solve(sparsh_handle h, int method, const double *b, double *x, double *hist, int hist_cap, int *iters)
 {
     REQUIRE_SMOOTHER_FITS(h, method);
+    REQUIRE_CYCLE_FITS(h, method);
     REQUIRE_GMRES_FITS(h, method);
     REQUIRE_READY(h);
     Engine &E = *h->eng;
@@ -859,6 +867,7 @@ int sparsh_solve_dev(sparsh_handle h, int method, const double *b_dev, double *x
                      int *iters, double *seconds)
 {
     REQUIRE_SMOOTHER_FITS(h, method);
+    REQUIRE_CYCLE_FITS(h, method);
     REQUIRE_GMRES_FITS(h, method);
     REQUIRE_READY(h);
     int rc = h->eng->solve_dev(method, b_dev, x_dev, max_iters, hist, hist_cap, iters, seconds);
@@ -1159,6 +1168,7 @@ int sparsh_dist_deep_op_get(sparsh_handle h, int *rowptr, int *col, double *val,
 int sparsh_krylov_init_dev(sparsh_handle h, int method, const double *b_dev, double *x_dev)
 {
     REQUIRE_SMOOTHER_FITS(h, method);
+    REQUIRE_CYCLE_FITS(h, method);
     REQUIRE_READY(h);
     if (method != SPARSH_CG && method != SPARSH_PCG) return fail(SPARSH_EINVAL, "stepwise interface covers SPARSH_CG and SPARSH_PCG");
     int rc = h->eng->pcg_init(b_dev, x_dev, method == SPARSH_PCG);
@@ -1362,6 +1372,7 @@ int sparsh_op_precond_f32(sparsh_handle h, const double *r, double *z)
 
 int sparsh_op_precond(sparsh_handle h, const double *r, double *z)
 {
+    REQUIRE_CYCLE_FITS(h, SPARSH_AMG);
     REQUIRE_READY(h);
     REQUIRE_SINGLE(h);
     Engine &E = *h->eng;
@@ -1370,6 +1381,52 @@ int sparsh_op_precond(sparsh_handle h, const double *r, double *z)
     if (!dr.p || !dz.p) return fail(SPARSH_ENODEV, E.error);
     if (int rc = E.op_precond(dr.p, dz.p); rc != SPARSH_OK) return fail(rc, E.error);
     return done(E, dz.get(z));
+}
+
+int sparsh_set_cycle(sparsh_handle h, int kind, int stride)
+{
+    if (!h || !h->eng) return fail(SPARSH_EINVAL, "null handle");
+    if (kind != SPARSH_CYCLE_V && kind != SPARSH_CYCLE_W && kind != SPARSH_CYCLE_K)
+        return fail(SPARSH_EINVAL, "kind must be SPARSH_CYCLE_V (0), SPARSH_CYCLE_W (1) or SPARSH_CYCLE_K (2)");
+    if (stride < 0 || stride > 8) return fail(SPARSH_EINVAL, "stride must be 1..8 (0: the default of 3)");
+    h->eng->set_cycle(kind, stride == 0 ? Engine::kCycleDefaultStride : stride);
+    return SPARSH_OK;
+}
+
+int sparsh_cycle_info(sparsh_handle h, int *kind, int *stride, int *nlevels_wk, long *level_visits, long *bytes)
+{
+    if (!h || !h->eng) return fail(SPARSH_EINVAL, "null handle");
+    const Engine &E = *h->eng;
+    if (kind) *kind = E.cycle_kind();
+    if (stride) *stride = E.cycle_stride();
+    if (nlevels_wk) *nlevels_wk = E.host_ready() ? E.wk_level_count() : 0;
+    if (level_visits) *level_visits = E.host_ready() ? E.cycle_visits() : 0;
+    if (bytes) *bytes = (long)E.wk_bytes();
+    return SPARSH_OK;
+}
+
+int sparsh_level_cycle(sparsh_handle h, int level, int *is_wk, long *visits)
+{
+    REQUIRE_HOST(h);
+    REQUIRE_LEVEL(h, level);
+    if (is_wk) *is_wk = h->eng->wk_level(level) ? 1 : 0;
+    if (visits) *visits = h->eng->level_visits(level);
+    return SPARSH_OK;
+}
+
+int sparsh_op_kstep(sparsh_handle h, int level, const double *b, const double *c, const double *d, double *r, double *x, double *scal8)
+{
+    if (!b || !c || !d || !r || !x || !scal8) return fail(SPARSH_EINVAL, "null array");
+    REQUIRE_READY(h);
+    REQUIRE_SINGLE(h);
+    REQUIRE_LEVEL(h, level);
+    Engine &E = *h->eng;
+    const size_t n = (size_t)E.level(level).n;
+    DBuf db(E, n, b), dc(E, n, c), dd(E, n, d), dr(E, n), dx(E, n), ds(E, 8);
+    if (!db.p || !dc.p || !dd.p || !dr.p || !dx.p || !ds.p) return fail(SPARSH_ENODEV, E.error);
+    if (int rc = E.op_kstep(level, db.p, dc.p, dd.p, dr.p, dx.p, ds.p); rc != SPARSH_OK) return fail(rc, E.error);
+    const bool ok = dr.get(r) && dx.get(x) && ds.get(scal8);
+    return done(E, ok);
 }
 
 int sparsh_set_gmres(sparsh_handle h, int restart)

@@ -1203,6 +1203,9 @@ int Engine::setup(const sparsh_params &p)
     multi_forget();  // (the block vectors too: the next block call reallocates them)
     sor_.clear();
     cheb_.clear();  // (the d vectors are freed with the rest)
+    wk_.clear();    // (so are the extra vectors of the W- and K-cycles)
+    kc_part_ = kc_scal_ = nullptr;
+    wk_bytes_ = 0;
     coarse_.release();
     if (!comm_) comm_ = make_self_comm();
     const int G = comm_->size, me = comm_->rank;
@@ -2250,16 +2253,16 @@ void Engine::cheby_bench_step(int l)
 
 // One smoothing leg of vcycle_plain.  SOR: colours 1..C before the coarse correction, C..1 after it under the symmetric order; the zero
 // guess is a fill and the dot a launch of its own.  Chebyshev: the zero guess is the leg's first launch and the dot rides in its last.
-void Engine::plain_leg(int l, bool x_zero, bool post, double *dot_partial, int *dot_nblk)
+void Engine::plain_leg(int l, const double *b, bool x_zero, bool post, double *dot_partial, int *dot_nblk)
 {
     DevLevel &L = lev_[l];
     if (cheby_on()) {
-        cheby_leg(l, L.b, x_zero, cheby_degree(), dot_partial, dot_nblk);
+        cheby_leg(l, b, x_zero, cheby_degree(), dot_partial, dot_nblk);
         return;
     }
     if (x_zero) launch_fill(L.n, 0.0, L.x, st_);  // fill(Xv[l1+1], ..., 0.0)
-    sor_leg(l, L.b, L.x, sor_sweeps(), post && sor_order_ == SPARSH_SOR_SYMMETRIC);
-    if (dot_partial) launch_dot(L.n, L.x, L.b, dot_partial, dot_nblk, st_);
+    sor_leg(l, b, L.x, sor_sweeps(), post && sor_order_ == SPARSH_SOR_SYMMETRIC);
+    if (dot_partial) launch_dot(L.n, L.x, b, dot_partial, dot_nblk, st_);
 }
 
 // AMG_solve_SOR (src/AMG_phases.cpp:234-306): the Jacobi cycle's hierarchy and order of operations, with plain residual,
@@ -2276,20 +2279,210 @@ void Engine::vcycle_plain(const double *b0, bool x0_zero, double *dot_partial, i
     }
     for (int l = 0; l < last; ++l) {
         DevLevel &L = lev_[l];
-        plain_leg(l, l > 0 || x0_zero, false, nullptr, nullptr);  // pre-smoothing; coarse levels start from x = 0
+        plain_leg(l, L.b, l > 0 || x0_zero, false, nullptr, nullptr);  // pre-smoothing; coarse levels start from x = 0
         op_residual(l, L.b, L.x, L.r);                            // store_residual
         op_restrict(l, L.r, lev_[l + 1].b, false);                // transfer_residual
     }
     op_coarse(lev_[last].b, lev_[last].x);  // Direct_Solver_Pardiso_solve
     for (int l = last; l > 0; --l) {
         op_prolong(l - 1, lev_[l].x, lev_[l - 1].x);  // transfer_solution
-        plain_leg(l - 1, false, true, l == 1 ? dot_partial : nullptr, dot_nblk);
+        plain_leg(l - 1, lev_[l - 1].b, false, true, l == 1 ? dot_partial : nullptr, dot_nblk);
     }
+}
+
+// ---------------------------------------------------------------------------- W- and K-cycles at chosen levels
+
+long Engine::level_visits_for(int l, int stride) const
+{
+    long v = 1;
+    for (int k = 1; k <= l; ++k)
+        if (wk_level_for(k, stride)) v = std::min(v * 2, 1L << 40);
+    return v;
+}
+
+long Engine::cycle_visits_for(int stride) const
+{
+    long total = 0;
+    for (int l = 0; l < (int)H_.levels.size(); ++l) total += level_visits_for(l, stride);
+    return total;
+}
+
+int Engine::wk_level_count() const
+{
+    int c = 0;
+    for (int l = 0; l < (int)H_.levels.size(); ++l) c += wk_level(l) ? 1 : 0;
+    return c;
+}
+
+int Engine::cycle_check(int method)
+{
+    if (cycle_kind_ == SPARSH_CYCLE_V) return SPARSH_OK;
+    if (method == SPARSH_CG || method == SPARSH_BICG || method == SPARSH_GMRES) return SPARSH_OK;  // no preconditioner
+    const char *name = cycle_kind_ == SPARSH_CYCLE_W ? "W" : "K";
+    if (cycle_kind_ == SPARSH_CYCLE_K && (method == SPARSH_PCG || method == SPARSH_PBICG || method == SPARSH_PGMRES)) {
+        error = "the K-cycle is not a fixed linear operator: SPARSH_PCG, SPARSH_PBICG and SPARSH_PGMRES cannot take it; use SPARSH_FCG (or the W-cycle)";
+        return SPARSH_EINVAL;
+    }
+    if (dist_ || (comm_ && comm_->size > 1)) {
+        error = std::string("the ") + name + "-cycle is not available on a partitioned (multi-GPU) handle";
+        return SPARSH_EINVAL;
+    }
+    if ((host_ready_ || ready_) && prm_.precond_fp32) {
+        error = std::string("the ") + name + "-cycle has no fp32 hierarchy: unset params.precond_fp32";
+        return SPARSH_EINVAL;
+    }
+    if (host_ready_ && cycle_visits() > kCycleMaxVisits) {
+        int smallest = 0, largest = 0;
+        for (int s = 1; s <= 8; ++s)
+            if (cycle_visits_for(s) <= kCycleMaxVisits) {
+                if (!smallest) smallest = s;
+                largest = s;
+            }
+        error = std::string("the ") + name + "-cycle with stride " + std::to_string(cycle_stride_) + " visits " + std::to_string(cycle_visits()) + " levels per cycle on " +
+                std::to_string(H_.levels.size()) + " levels; the cap is " + std::to_string(kCycleMaxVisits) + ": " +
+                (largest ? "the largest stride that fits is " + std::to_string(largest) + ", the smallest " + std::to_string(smallest) : std::string("no stride fits"));
+        return SPARSH_EINVAL;
+    }
+    return SPARSH_OK;
+}
+
+bool Engine::kc_scratch()
+{
+    if (kc_part_ && kc_scal_) return true;
+    const size_t pb = (size_t)kKcPartialDoubles * 8, sb = (size_t)kKcScalDoubles * 8 * (lev_.size() + 1);
+    kc_part_ = static_cast<double *>(dalloc(pb));
+    kc_scal_ = static_cast<double *>(dalloc(sb));
+    if (!kc_part_ || !kc_scal_) return false;
+    if (!check(hipMemsetAsync(kc_part_, 0, pb, st_), "hipMemsetAsync") || !check(hipMemsetAsync(kc_scal_, 0, sb, st_), "hipMemsetAsync")) return false;
+    wk_bytes_ += pb + sb;
+    return true;
+}
+
+int Engine::cycle_prepare(int method)
+{
+    if (int rc = cycle_check(method); rc != SPARSH_OK) return rc;
+    if (cycle_kind_ == SPARSH_CYCLE_V || method == SPARSH_CG || method == SPARSH_BICG || method == SPARSH_GMRES) return SPARSH_OK;
+    if (wk_.size() != lev_.size()) wk_.assign(lev_.size(), WkLevel());
+    const bool k = cycle_kind_ == SPARSH_CYCLE_K;
+    if (k && !kc_scratch()) return fault_ != SPARSH_OK ? fault_ : SPARSH_ENODEV;
+    for (int l = 1; l + 1 < (int)lev_.size(); ++l) {
+        if (!wk_level(l)) continue;
+        const size_t bytes = (size_t)std::max(lev_[l].n, 1) * 8;
+        for (double **slot : {&wk_[l].c, &wk_[l].r, k ? &wk_[l].v : (double **)nullptr}) {
+            if (!slot || *slot) continue;
+            double *p = static_cast<double *>(dalloc(bytes));
+            if (!p || !check(hipMemsetAsync(p, 0, bytes, st_), "hipMemsetAsync")) return fault_ != SPARSH_OK ? fault_ : SPARSH_ENODEV;
+            *slot = p;
+            wk_bytes_ += bytes;
+        }
+    }
+    return SPARSH_OK;
+}
+
+// One smoothing leg of the recursive cycle: the handle's smoother on right-hand side b, nothing fused with a neighbouring launch
+// (Jacobi: what op_jacobi runs).
+void Engine::wk_leg(int l, const double *b, bool x_zero, bool post, double *dot_partial, int *dot_nblk)
+{
+    if (!jacobi_on()) {
+        plain_leg(l, b, x_zero, post, dot_partial, dot_nblk);
+        return;
+    }
+    DevLevel &L = lev_[l];
+    if (x_zero && prm_.sweeps <= 0) launch_fill(L.n, 0.0, L.x, st_);
+    smooth(L, b, prm_.sweeps, x_zero, dot_partial, dot_nblk);
+}
+
+void Engine::cycle_wk(int l, const double *b, bool x_zero, double *dot_partial, int *dot_nblk)
+{
+    const int last = (int)lev_.size() - 1;
+    if (l == last) {
+        op_coarse(b, lev_[l].x);  // Direct_Solver_Pardiso_solve
+        if (dot_partial) launch_dot(lev_[l].n, lev_[l].x, b, dot_partial, dot_nblk, st_);
+        return;
+    }
+    wk_leg(l, b, x_zero, false, nullptr, nullptr);          // pre-smoothing
+    op_residual(l, b, lev_[l].x, lev_[l].r);                // store_residual
+    op_restrict(l, lev_[l].r, lev_[l + 1].b, false);        // transfer_residual
+    solve_coarse_wk(l + 1);
+    op_prolong(l, lev_[l + 1].x, lev_[l].x);                // transfer_solution
+    wk_leg(l, b, false, true, dot_partial, dot_nblk);       // post-smoothing
+}
+
+void Engine::kstep_first(int l, const double *b, const double *c, double *v, double *r, double *s)
+{
+    const int n = lev_[l].n;
+    op_spmv(l, c, v);                                           // v = A c
+    const int nb = launch_kc_dot2(n, c, v, b, kc_part_, st_);  // c.v ; c.b
+    launch_kc_scal1(kc_part_, nb, s, st_);                      // rho1, alpha1, q
+    launch_kc_resid(n, s, b, v, r, st_);                        // r = b - q v
+}
+
+void Engine::kstep_second(int l, const double *c, const double *d, const double *v, double *w, const double *r, double *x, double *s)
+{
+    const int n = lev_[l].n;
+    op_spmv(l, d, w);                                              // w = A d
+    const int nb = launch_kc_dot3(n, d, v, w, r, kc_part_, st_);  // d.v ; d.w ; d.r
+    launch_kc_scal2(kc_part_, nb, s, st_);                         // gamma, beta, alpha2, rho2, k1, k2
+    launch_kc_combine(n, s, c, d, x, st_);                         // x = k1 c + k2 d
+}
+
+void Engine::solve_coarse_wk(int l)
+{
+    const double *b = lev_[l].b;
+    if (!wk_level(l) || l >= (int)wk_.size() || !wk_[l].c) {
+        cycle_wk(l, b, true, nullptr, nullptr);
+        return;
+    }
+    WkLevel &K = wk_[l];
+    if (!K.r || (cycle_kind_ == SPARSH_CYCLE_K && (!K.v || !kc_part_ || !kc_scal_))) {
+        // every caller reserves the vectors first (cycle_prepare): nothing may run on a missing one
+        error = "recursive cycle on level " + std::to_string(l) + " without its extra vectors";
+        if (fault_ == SPARSH_OK) fault_ = SPARSH_ESTATE;
+        return;
+    }
+    const int n = lev_[l].n;
+    cycle_wk(l, b, true, nullptr, nullptr);
+    std::swap(lev_[l].x, K.c);  // c stays where the cycle left it: the level goes on with the other buffer (equal size)
+    if (cycle_kind_ == SPARSH_CYCLE_W) {
+        op_residual(l, b, K.c, K.r);                  // r = b - A c
+        cycle_wk(l, K.r, true, nullptr, nullptr);      // d
+        launch_axpby(n, 1.0, K.c, 1.0, lev_[l].x, st_);  // x = c + d
+        return;
+    }
+    double *s = kc_scal_ + (size_t)kKcScalDoubles * l;
+    kstep_first(l, b, K.c, K.v, K.r, s);
+    cycle_wk(l, K.r, true, nullptr, nullptr);  // d in lev_[l].x ; lev_[l].r is free again and takes w = A d
+    kstep_second(l, K.c, lev_[l].x, K.v, lev_[l].r, K.r, lev_[l].x, s);
+}
+
+int Engine::op_kstep(int l, const double *b, const double *c, const double *d, double *r, double *x, double *scal8)
+{
+    if (!kc_scratch()) return fault_ != SPARSH_OK ? fault_ : SPARSH_ENODEV;
+    const size_t bytes = (size_t)std::max(lev_[l].n, 1) * 8;
+    double *v = static_cast<double *>(dalloc(bytes)), *w = static_cast<double *>(dalloc(bytes));
+    if (!v || !w) {
+        dfree(v);
+        dfree(w);
+        return SPARSH_ENODEV;
+    }
+    double *s = kc_scal_ + (size_t)kKcScalDoubles * lev_.size();
+    kstep_first(l, b, c, v, r, s);
+    kstep_second(l, c, d, v, w, r, x, s);
+    HIPCHK(hipMemcpyAsync(scal8, s, 8 * sizeof(double), hipMemcpyDeviceToDevice, st_));
+    HIPCHK(hipStreamSynchronize(st_));
+    dfree(v);
+    dfree(w);
+    return fault_;
 }
 
 // One V(nu,nu) cycle (body of the while loops in AMG_solve_jacobi, src/AMG_phases.cpp:198-216).
 void Engine::vcycle(const double *b0, bool x0_zero, double *dot_partial, int *dot_nblk, bool zero_done0)
 {
+    if (cycle_kind_ != SPARSH_CYCLE_V) {
+        lev_[0].b = const_cast<double *>(b0);
+        cycle_wk(0, b0, x0_zero, dot_partial, dot_nblk);
+        return;
+    }
     if (!jacobi_on()) {
         vcycle_plain(b0, x0_zero, dot_partial, dot_nblk);
         return;
@@ -2367,6 +2560,7 @@ int Engine::amg_solve_dev(const double *b, double *x, int iterations, double *hi
 {
     if (!ready_) return SPARSH_ESTATE;
     if (int rc = smoother_prepare(); rc != SPARSH_OK) return rc;
+    if (int rc = cycle_prepare(SPARSH_AMG); rc != SPARSH_OK) return rc;
     DevLevel &L0 = lev_[0];
     const int n = L0.n;
     HIPCHK(hipMemcpyAsync(L0.x, x, (size_t)n * 8, hipMemcpyDeviceToDevice, st_));
@@ -2429,7 +2623,8 @@ int Engine::pcg_smoother_check()
         error = "SPARSH_PCG needs a symmetric preconditioner: the SOR smoother must use SPARSH_SOR_SYMMETRIC";
         return SPARSH_EINVAL;
     }
-    return smoother_prepare();
+    if (int rc = smoother_prepare(); rc != SPARSH_OK) return rc;
+    return cycle_prepare(SPARSH_PCG);
 }
 
 int Engine::pcg_init(const double *b, double *x, bool precond)
@@ -2482,7 +2677,7 @@ void Engine::pcg_body(bool precond, int slot)
     // are reduced together with z.r after the V-cycle: one finalize launch (one all-reduce) less
     // with the fp64 V-cycle behind it the update also writes the cycle's zero-guess sweep of level 0 (z0 = omega r / d)
     // (... unless the cycle's first launch on level 0 is the three-sweep one, which reads r alone)
-    const bool fuse_zero = cfg_.fuse_cg_zero && precond && !f32_ready_ && jacobi_on() && lev_.size() > 1 && !lev_[0].deep && prm_.sweeps > 0 &&
+    const bool fuse_zero = cfg_.fuse_cg_zero && precond && !f32_ready_ && jacobi_on() && cycle_kind_ == SPARSH_CYCLE_V && lev_.size() > 1 && !lev_[0].deep && prm_.sweeps > 0 &&
                            !(prm_.sweeps >= 3 && zero_start(lev_[0]));
     // with the fp64 V-cycle behind it x += alpha p waits for the direction update at the end of this iteration (one read of p for both)
     const bool defer_x = cfg_.defer_x && precond && !f32_ready_;
@@ -2549,7 +2744,8 @@ int Engine::pcg_steps(int nsteps, int *done)
     int did = 0;
     const int check_every = std::max(1, prm_.check_every);
     // hipGraph replay: single GPU, no per-launch profiling events
-    bool use_graph = prm_.use_graph && !dist_ && !prof.enabled && (int)lev_.size() > 1;
+    // (the W-cycle launches eagerly: its WK levels exchange their buffers from one inner cycle to the next)
+    bool use_graph = prm_.use_graph && !dist_ && !prof.enabled && (int)lev_.size() > 1 && (!precond || cycle_kind_ == SPARSH_CYCLE_V);
     if (use_graph && !(graph_.exec && graph_.x == ks_.x && graph_.precond == precond)) use_graph = capture_graph(precond);
     if (use_graph) HIPCHK(hipMemcpyAsync(iter_ctr_, &ks_.count, sizeof(int), hipMemcpyHostToDevice, st_));
     while (ks_.count < lev_[0].nglob && ks_.r1 > prm_.tol && did < nsteps && fault_ == SPARSH_OK) {
@@ -2598,8 +2794,10 @@ int Engine::pcg(const double *b, double *x, int max_iters, double *hist, int his
 // Solver_BiCG_1 (precond = false) / Solver_PBiCG_1 (precond = true).
 int Engine::bicg(const double *b, double *x, int max_iters, double *hist, int hist_cap, int *iters, bool precond)
 {
-    if (precond)
+    if (precond) {
         if (int rc = smoother_prepare(); rc != SPARSH_OK) return rc;
+        if (int rc = cycle_prepare(SPARSH_PBICG); rc != SPARSH_OK) return rc;
+    }
     const int n = lev_[0].n;
     double *r0 = work_[0], *r = work_[1], *p = work_[2], *Ap = work_[3], *s = work_[4], *As = work_[5], *p1buf = work_[6];
     int nb = 0;
@@ -2661,10 +2859,79 @@ int Engine::bicg(const double *b, double *x, int max_iters, double *hist, int hi
     return fault_ != SPARSH_OK ? fault_ : rc;
 }
 
+// Flexible CG, Notay's FCG(1): PCG whose new direction is made A-orthogonal to the previous one explicitly (beta = -z.Ap / p.Ap), so
+// the preconditioner may change from one application to the next (the K-cycle).  With a fixed symmetric M it is PCG in exact arithmetic.
+int Engine::fcg(const double *b, double *x, int max_iters, double *hist, int hist_cap, int *iters)
+{
+    if (dist_ || (comm_ && comm_->size > 1)) {
+        error = "SPARSH_FCG is not available on a partitioned (multi-GPU) handle";
+        return SPARSH_EINVAL;
+    }
+    if (sor_on() && sor_order_ != SPARSH_SOR_SYMMETRIC) {
+        error = "SPARSH_FCG needs a symmetric preconditioner: the SOR smoother must use SPARSH_SOR_SYMMETRIC";
+        return SPARSH_EINVAL;
+    }
+    if (int rc = smoother_prepare(); rc != SPARSH_OK) return rc;
+    if (int rc = cycle_prepare(SPARSH_FCG); rc != SPARSH_OK) return rc;
+    const int n = lev_[0].n;
+    double *r = work_[0], *p = work_[1], *Ap = work_[2];
+    int nb = 0;
+    op_residual(0, b, x, r);  // r0 = b - A x
+    launch_dot(n, r, r, part0_, &nb, st_);
+    finalize(FIN_SQRT, part0_, nullptr, nb, S_RES, nullptr, 0);
+    double res = read_scalar(S_RES);
+    int count = 0;
+    int rc = SPARSH_OK;
+    const int check_every = std::max(1, prm_.check_every);
+    if (res > prm_.tol) {
+        const double *z = precondition(r, work_[4]);  // z0 = M r0
+        launch_dot(n, z, r, part0_, &nb, st_);
+        finalize(FIN_STORE, part0_, nullptr, nb, S_RZ, nullptr, 0);  // rho = z0.r0
+        launch_copy(n, z, p, st_);
+    }
+    while (res > prm_.tol) {
+        if (fault_ != SPARSH_OK) break;
+        if (count >= max_iters) {
+            rc = SPARSH_ENOCONV;
+            break;
+        }
+        CsrArgs a;
+        a.x = p;
+        a.y = Ap;
+        a.partial = part0_;
+        const int np = apply_A(lev_[0], OP_SPMV_DOT, a);  // q = A p ; sigma = p.q
+        finalize(FIN_PCG_ALPHA, part0_, nullptr, np, 0, nullptr, 0);  // alpha = rho / sigma
+        launch_cg_update(n, scal_, p, Ap, x, r, part1_, &nb, st_);   // x += alpha p ; r -= alpha q ; r.r
+        const int slot = std::min(count, hist_cap_dev_ - 1);
+        finalize(FIN_SQRT, part1_, nullptr, nb, S_RES, hist_dev_, slot);
+        const double *z = precondition(r, work_[4]);                // z = M r
+        launch_dot2(n, z, r, z, Ap, part0_, part1_, &nb, st_);       // rho = z.r ; tau = z.q
+        finalize(FIN_FCG_BETA, part0_, part1_, nb, 0, nullptr, 0);  // beta = -tau / sigma
+        launch_p_update(n, scal_, z, p, st_);                        // p = z + beta p
+        ++count;
+        if (count % check_every == 0 || count >= max_iters) {
+            res = read_hist(slot);
+            if (prm_.print_solve) std::printf("%d\t%g\n", count, res);
+            if (!(res == res)) {
+                rc = SPARSH_ENUMERIC;
+                break;
+            }
+        }
+    }
+    HIPCHK(hipStreamSynchronize(st_));
+    if (hist) {
+        const int m = std::min(std::min(count, hist_cap), hist_cap_dev_);
+        if (m > 0) HIPCHK(hipMemcpy(hist, hist_dev_, (size_t)m * 8, hipMemcpyDeviceToHost));
+    }
+    if (iters) *iters = count;
+    return fault_ != SPARSH_OK ? fault_ : rc;
+}
+
 // z = M r, the preconditioner of SPARSH_PBICG / SPARSH_PGMRES: one V-cycle of the current smoother from a zero guess, or the fp32 cycle.
 int Engine::op_precond(const double *r, double *z)
 {
     if (int rc = smoother_prepare(); rc != SPARSH_OK) return rc;
+    if (int rc = cycle_prepare(SPARSH_AMG); rc != SPARSH_OK) return rc;
     const double *zc = precondition(r, z);
     if (zc != z) launch_copy(lev_[0].n, zc, z, st_);
     return fault_;
@@ -2801,6 +3068,8 @@ int Engine::gmres(const double *b, double *x, int max_iters, double *hist, int h
     }
     if (precond)
         if (int rc = smoother_prepare(); rc != SPARSH_OK) return rc;
+    if (precond)
+        if (int rc = cycle_prepare(SPARSH_PGMRES); rc != SPARSH_OK) return rc;
     if (int rc = gmres_reserve(); rc != SPARSH_OK) return rc;
     const int n = lev_[0].n, m = gm_restart_;
     const bool f32b = gm_prec_ == SPARSH_BASIS_FP32;
@@ -2965,6 +3234,7 @@ int Engine::solve_dev(int method, const double *b, double *x, int max_iters, dou
     case SPARSH_PBICG: rc = bicg(b, x, max_iters, hist, hist_cap, iters, true); break;
     case SPARSH_GMRES: rc = gmres(b, x, max_iters, hist, hist_cap, iters, false); break;
     case SPARSH_PGMRES: rc = gmres(b, x, max_iters, hist, hist_cap, iters, true); break;
+    case SPARSH_FCG: rc = fcg(b, x, max_iters, hist, hist_cap, iters); break;
     default: error = "unknown method"; return SPARSH_EINVAL;
     }
     if (seconds) {

@@ -74,6 +74,12 @@ struct ChebyLevel {
     double lmax() const { return forced > 0.0 ? forced : est.lmax; }
 };
 
+// Extra vectors of one WK level (a level where the W- or the K-cycle recurses twice): the first inner cycle's result c, v = A_l c (K
+// only) and the right-hand side r of the second inner cycle.  Allocated at the first cycle that needs them.
+struct WkLevel {
+    double *c = nullptr, *v = nullptr, *r = nullptr;
+};
+
 struct KrylovState {
     bool active = false, precond = false;
     const double *b = nullptr;
@@ -165,6 +171,33 @@ public:
     bool op_cheby(int l, const double *b, double *x, double *tmp, int degree, bool x_is_zero);
     // bench: one step of the k >= 1 form on the level's resident buffers (x, x2, d; r as the right-hand side)
     void cheby_bench_step(int l);
+    // ---- W- and K-cycles at chosen levels.  Level l is a WK level when 1 <= l < last and l % stride == 0; there
+    // the coarse problem is solved by two inner cycles (W: the second on the residual of the first; K: two flexible-CG steps).
+    static constexpr int kCycleDefaultStride = 3;
+    static constexpr long kCycleMaxVisits = 1024;  // level visits of one cycle, all levels together
+    void set_cycle(int kind, int stride)
+    {
+        cycle_kind_ = kind;
+        cycle_stride_ = stride;
+        config_changed();
+    }
+    int cycle_kind() const { return cycle_kind_; }
+    int cycle_stride() const { return cycle_stride_; }
+    // host-side counts of the hierarchy built by setup_host, under the current kind and stride (kind V: no WK level, one visit each)
+    bool wk_level(int l) const { return wk_level_for(l, cycle_stride_); }
+    long level_visits(int l) const { return level_visits_for(l, cycle_stride_); }
+    long cycle_visits() const { return cycle_visits_for(cycle_stride_); }
+    int wk_level_count() const;
+    size_t wk_bytes() const { return wk_bytes_; }
+    // whether `method` can run under the current cycle on this handle: SPARSH_OK, or SPARSH_EINVAL with the reason in error.  Needs no
+    // device; the visit cap is checked once the hierarchy exists.  SPARSH_AMG stands for every caller that takes a preconditioner
+    // which changes from one application to the next (the stand-alone iteration, op_precond)
+    int cycle_check(int method);
+    // cycle_check and the extra vectors of the WK levels (every solver entry calls it next to smoother_prepare)
+    int cycle_prepare(int method);
+    // test hook: the K step's own launches on caller vectors of level l (device): v = A c, the two sums, q, r = b - q v; w = A d, the
+    // three sums, the scalars, x = k1 c + k2 d; scal8 = {rho1, alpha1, gamma, beta, alpha2, rho2, k1, k2}
+    int op_kstep(int l, const double *b, const double *c, const double *d, double *r, double *x, double *scal8);
     // SOR layouts / Chebyshev bounds and d vectors of the smoothed levels (all but the coarsest) ready for a solve on this handle, built
     // now if the smoother was chosen after setup; SPARSH_* code (every solver entry calls it)
     int smoother_prepare();
@@ -384,7 +417,31 @@ private:
     void vcycle_plain(const double *b0, bool x0_zero, double *dot_partial, int *dot_nblk);
     // one smoothing leg of that cycle on level l, iterate in lev_[l].x (x_zero: taken as 0); post: after the coarse correction;
     // dot_partial: the leg also leaves the partial sums of x.b there (Chebyshev: fused into its last step, OP_CHEBY_DOT)
-    void plain_leg(int l, bool x_zero, bool post, double *dot_partial, int *dot_nblk);
+    // b: the leg's right-hand side (lev_[l].b in the V-cycle; the W- and K-cycles also run a level on a residual of their own)
+    void plain_leg(int l, const double *b, bool x_zero, bool post, double *dot_partial, int *dot_nblk);
+    // ---- the recursive cycle (kind W or K), reached from vcycle() when the kind is not V
+    // cycle(l, b): the plain V-cycle body of level l from a zero guess (level 0: from lev_[0].x unless x_zero), result in lev_[l].x;
+    // below level l the coarse problems go through solve_coarse_wk.  Legs are the handle's smoother with nothing fused across launches
+    void cycle_wk(int l, const double *b, bool x_zero, double *dot_partial, int *dot_nblk);
+    // x_l = solve_coarse(l, lev_[l].b) in lev_[l].x: cycle(l, b) on a plain level, the W or the K step around two of them on a WK level
+    void solve_coarse_wk(int l);
+    void wk_leg(int l, const double *b, bool x_zero, bool post, double *dot_partial, int *dot_nblk);
+    // the two halves of a K step around the second inner cycle; s: the level's scalar block
+    void kstep_first(int l, const double *b, const double *c, double *v, double *r, double *s);
+    void kstep_second(int l, const double *c, const double *d, const double *v, double *w, const double *r, double *x, double *s);
+    bool wk_level_for(int l, int stride) const
+    {
+        const int last = (int)H_.levels.size() - 1;
+        return cycle_kind_ != SPARSH_CYCLE_V && l >= 1 && l < last && l % stride == 0;
+    }
+    long level_visits_for(int l, int stride) const;
+    long cycle_visits_for(int stride) const;
+    bool kc_scratch();  // partial sums and scalar blocks of the K step (no-op once held)
+    int fcg(const double *b, double *x, int max_iters, double *hist, int hist_cap, int *iters);
+    int cycle_kind_ = SPARSH_CYCLE_V, cycle_stride_ = kCycleDefaultStride;
+    std::vector<WkLevel> wk_;  // per level (empty until first use)
+    double *kc_part_ = nullptr, *kc_scal_ = nullptr;  // kKcPartialDoubles ; kKcScalDoubles per level and one block more for op_kstep
+    size_t wk_bytes_ = 0;
     // run fn with lev_[l]'s ping-pong slots pointing at the caller's x / tmp; the result ends in x
     template <class Fn> void with_borrowed_slots(int l, double *x, double *tmp, Fn fn);
     std::vector<ChebyLevel> cheb_;  // per level (empty until first use)

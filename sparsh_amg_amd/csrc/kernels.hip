@@ -2595,6 +2595,11 @@ __global__ __launch_bounds__(kFinBlock) void finalize_kernel(int code, int mode,
         scal[S_RES] = res;
         if (hist) hist[hslot] = res;
     } break;
+    case FIN_FCG_BETA: {
+        scal[S_ZR] = s0;
+        scal[S_RZ] = s0;
+        scal[S_BETA] = -s1 / scal[S_PAP];
+    } break;
     default: break;
     }
 }

@@ -310,7 +310,8 @@ enum Fin : int {
     FIN_BICG_ALPHA = 6,// alpha1 = sum0 (r.r0) ; apr0 = sum1 (Ap.r0) ; alpha = alpha1/apr0
     FIN_BICG_OMEGA = 7,// ass = sum0 (As.s) ; asas = sum1 (As.As) ; omega1 = ass/asas
     FIN_BICG_BETA = 8, // rr0 = sum0 (r.r0) ; rr = sum1 (r.r) ; beta = rr0/alpha1*(alpha/omega1) ; res = sqrt(rr) ; hist
-    FIN_PCG_BETA_RES = 9  // FIN_PCG_BETA on sum0 (z.r) and res = sqrt(sum1) (r.r) ; hist
+    FIN_PCG_BETA_RES = 9, // FIN_PCG_BETA on sum0 (z.r) and res = sqrt(sum1) (r.r) ; hist
+    FIN_FCG_BETA = 10     // flexible CG: rz = sum0 (z.r) ; beta = -sum1 (z.Ap) / pAp
 };
 // it >= 0: residual-history slot; it < 0: take the slot from the device counter *iter_ctr (graph replays).
 // mode 0: reduce the partials and apply `code` (single GPU); mode 1: reduce only, local sums to
@@ -344,6 +345,25 @@ void launch_bicg_xr(int n, const double *scal, const double *p1, const double *s
                     const double *r0, double *x, double *r, double *partial0, double *partial1, int *nblk, hipStream_t st);
 // BiCGStab: p = r + beta*(p - omega1*Ap)
 void launch_bicg_p(int n, const double *scal, const double *r, const double *Ap, double *p, hipStream_t st);
+
+// ---- K step of the K-cycle (kcycle_kernels.hip): two flexible-CG steps on a coarse level with everything but the
+// two inner cycles and the two SpMVs done here, scalars in device memory.  Slots of the scalar block s (kKcScalDoubles doubles):
+enum KcSlot : int { KC_RHO1 = 0, KC_ALPHA1, KC_GAMMA, KC_BETA, KC_ALPHA2, KC_RHO2, KC_K1, KC_K2, KC_Q };
+constexpr int kKcScalDoubles = 16;
+constexpr int kKcMaxGrid = 512;                      // workgroups of a reducing launch: one per 2048 rows, capped
+constexpr int kKcPartialDoubles = 3 * kKcMaxGrid;   // sum k of a launch at partial[k * kKcMaxGrid + workgroup]
+int kc_grid(int n);
+// partial sums of c.v and c.b (dot2) / of d.v, d.w and d.r (dot3), the first vector read once; return the number of partials per sum
+int launch_kc_dot2(int n, const double *c, const double *v, const double *b, double *partial, hipStream_t st);
+int launch_kc_dot3(int n, const double *d, const double *v, const double *w, const double *r, double *partial, hipStream_t st);
+// one workgroup adds the partials in a fixed order; scal1: rho1, alpha1, q (1 when rho1 is not finite and > 0); scal2: gamma, beta,
+// alpha2, rho2 = beta - gamma^2 / rho1, k1 = q - gamma alpha2 / (rho1 rho2), k2 = alpha2 / rho2 -- with rho1 unusable rho2 = 0 and
+// k1 = k2 = 1, else with rho2 not finite and > 0 k1 = q and k2 = 0
+void launch_kc_scal1(const double *partial, int nblk, double *s, hipStream_t st);
+void launch_kc_scal2(const double *partial, int nblk, double *s, hipStream_t st);
+// r = b - q v and x = k1 c + k2 d (x may be d), coefficients read from s; every product and sum rounded on its own
+void launch_kc_resid(int n, const double *s, const double *b, const double *v, double *r, hipStream_t st);
+void launch_kc_combine(int n, const double *s, const double *c, const double *d, double *x, hipStream_t st);
 
 // ---- restarted GMRES (krylov_kernels.hip): block Gram-Schmidt against the basis v_k = V + k * stride and the device-resident
 // small problem.  Partial sums are per workgroup, gs_grid(n) of them per sum: sum k at partial[k * gs_grid(n) + workgroup].
