@@ -338,6 +338,11 @@ int sparsh_set_coarse_form(sparsh_handle h, int form, int leaf, int merge_rows);
  * dependent launches per solve whatever it holds. */
 int sparsh_set_coarse_top_merge(sparsh_handle h, int top_merge_rows);
 int sparsh_coarse_nd_info(sparsh_handle h, int *info6);
+/* Pivoting of the device factorisation, counted by the inversion kernels during sparsh_setup: out4 = {pivot steps, steps whose
+ * pivot row was not the diagonal row} of the one-workgroup LDS inversions (nested dissection, pivot blocks of at most 80 rows), then
+ * the same pair for the one-launch-per-step inversions (nested dissection: larger pivot blocks; block tridiagonal: every diagonal
+ * block).  All zero for the dense form and before sparsh_setup. */
+int sparsh_coarse_pivot_info(sparsh_handle h, int *out4);
 /* Interface form of the block-tridiagonal solve: where the RCM band is narrow against the block (2 * window <= block,
  * window = bandwidth rounded up to 64) only the first / last `window` rows of a block couple to its neighbours, so the
  * chain of dependent steps runs on those rows alone (products S_i^-1 A[i,neighbour] kept in HBM) and everything else is

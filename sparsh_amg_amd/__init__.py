@@ -154,6 +154,7 @@ def _load():
         "sparsh_set_coarse_block": (C.c_int, [H, C.c_int]),
         "sparsh_set_coarse_form": (C.c_int, [H, C.c_int, C.c_int, C.c_int]),
         "sparsh_coarse_nd_info": (C.c_int, [H, c_int_p]),
+        "sparsh_coarse_pivot_info": (C.c_int, [H, c_int_p]),
         "sparsh_set_coarse_top_merge": (C.c_int, [H, C.c_int]),
         "sparsh_setup_seconds": (C.c_double, [H]),
         "sparsh_vcycle": (C.c_int, [H, c_dbl_p, c_dbl_p, C.c_int, c_dbl_p, C.c_int, c_int_p]),
@@ -732,10 +733,13 @@ class sp_matrix_mg:
         _check(lib.sparsh_coarse_window(self._h, C.byref(win)))
         nd = (C.c_int * 6)()
         _check(lib.sparsh_coarse_nd_info(self._h, nd))
+        piv = (C.c_int * 4)()
+        _check(lib.sparsh_coarse_pivot_info(self._h, piv))
         form = "dense" if info[1] else ("nested_dissection" if nd[0] else ("block_tridiagonal" if info[3] else "not factored yet"))
         return {"rows": info[0], "dense": bool(info[1]), "form": form, "block": info[2], "nblocks": info[3], "bandwidth": info[4],
                 "extended": bool(info[5]), "bytes": nbytes.value, "window": win.value,
-                "nd_nodes": nd[1], "nd_levels": nd[2], "nd_max_pivot": nd[3], "nd_launches_per_solve": nd[4], "nd_leaf": nd[5]}
+                "nd_nodes": nd[1], "nd_levels": nd[2], "nd_max_pivot": nd[3], "nd_launches_per_solve": nd[4], "nd_leaf": nd[5],
+                "pivot_steps_lds": piv[0], "row_swaps_lds": piv[1], "pivot_steps_chip": piv[2], "row_swaps_chip": piv[3]}
 
     def set_coarse_form(self, form="nd", leaf=0, merge_rows=-1, top_merge_rows=-1):
         """Direct solver of a coarsest level above dense_limit rows: "nd" (nested-dissection multifrontal, default) or "bt"

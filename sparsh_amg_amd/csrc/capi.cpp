@@ -806,6 +806,14 @@ int sparsh_coarse_nd_info(sparsh_handle h, int *info6)
     return SPARSH_OK;
 }
 
+int sparsh_coarse_pivot_info(sparsh_handle h, int *out4)
+{
+    REQUIRE_HOST(h);
+    if (!out4) return fail(SPARSH_EINVAL, "null output");
+    h->eng->coarse().pivot_counts(out4);
+    return SPARSH_OK;
+}
+
 int sparsh_set_coarse_block(sparsh_handle h, int rows)
 {
     if (!h || !h->eng) return fail(SPARSH_EINVAL, "null handle");

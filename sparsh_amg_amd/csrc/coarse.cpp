@@ -110,6 +110,7 @@ void CoarseSolver::release()
     out_ = in_ = BtDevCsr();
     out_ell_ = in_ell_ = BtDevEll();
     steps_.clear();
+    bt_counts_[0] = bt_counts_[1] = 0;
     n_ = 0;
 }
 
@@ -217,7 +218,7 @@ bool CoarseSolver::setup_bt(const HostCsr &A, hipStream_t st, std::string &err, 
     double *c1 = ok ? dev_alloc<double>(tmp, (size_t)B, err) : nullptr;
     int *piv = ok ? dev_alloc<int>(tmp, (size_t)B, err) : nullptr;
     int *cmap = ok ? dev_alloc<int>(tmp, (size_t)B, err) : nullptr;
-    int *sing = ok ? dev_alloc<int>(tmp, 1, err) : nullptr;
+    int *sing = ok ? dev_alloc<int>(tmp, 3, err) : nullptr;  // the singular flag, then {pivot steps, row interchanges}
     if (!(ok && perm_ && z_ && sinv_ && S && S2 && c0 && c1 && piv && cmap && sing)) {
         drop_tmp();
         release();
@@ -225,14 +226,14 @@ bool CoarseSolver::setup_bt(const HostCsr &A, hipStream_t st, std::string &err, 
     }
     (void)hipMemsetAsync(sinv_, 0, (size_t)nb * B * B * sizeof(double), st);
     (void)hipMemsetAsync(z_, 0, (size_t)n * sizeof(double), st);
-    (void)hipMemsetAsync(sing, 0, sizeof(int), st);
+    (void)hipMemsetAsync(sing, 0, 3 * sizeof(int), st);
     const size_t bstride = (size_t)B * B;
     auto factor_block = [&](int i, int o1, int o2) {
         const int r0 = i * B, bs = P.block_rows(i);
         bt_launch_diag(r0, bs, B, diag.rp, diag.ci, diag.v, S, st);
         for (int o : {o1, o2})
             if (o >= 0 && o < nb) bt_launch_schur(r0, bs, o * B, P.block_rows(o), B, out_, inT, sinv_ + (size_t)o * bstride, S, st);
-        bt_launch_invert(bs, B, S, S2, c0, c1, piv, cmap, sing, sinv_ + (size_t)i * bstride, st);
+        bt_launch_invert(bs, B, S, S2, c0, c1, piv, cmap, sing, sing + 1, sinv_ + (size_t)i * bstride, st);
     };
     for (int i = 0; i < mid; ++i) factor_block(i, i - 1, -1);          // top chain
     for (int i = nb - 1; i > mid; --i) factor_block(i, i + 1, -1);     // bottom chain
@@ -355,8 +356,8 @@ bool CoarseSolver::setup_bt(const HostCsr &A, hipStream_t st, std::string &err, 
             tri_bytes_ = tri;
         }
     }
-    int sing_h = 0;
-    const bool copied = hipMemcpyAsync(&sing_h, sing, sizeof(int), hipMemcpyDeviceToHost, st) == hipSuccess;
+    int stat_h[3] = {0, 0, 0};
+    const bool copied = hipMemcpyAsync(stat_h, sing, sizeof(stat_h), hipMemcpyDeviceToHost, st) == hipSuccess;
     const hipError_t e = hipStreamSynchronize(st);
     drop_tmp();
     if (!copied || e != hipSuccess) {
@@ -364,7 +365,7 @@ bool CoarseSolver::setup_bt(const HostCsr &A, hipStream_t st, std::string &err, 
         release();
         return false;
     }
-    if (sing_h) {
+    if (stat_h[0]) {
         why = 2;
         err = "coarsest-level matrix is singular (zero pivot in a diagonal block of the block-tridiagonal factorisation)";
         release();
@@ -402,6 +403,8 @@ bool CoarseSolver::setup_bt(const HostCsr &A, hipStream_t st, std::string &err, 
     }
     // the host pieces are no longer needed (sizes stay in plan_)
     plan_.diag = plan_.out = plan_.in = plan_.inT = HostCsr();
+    bt_counts_[0] = stat_h[1];
+    bt_counts_[1] = stat_h[2];
     n_ = n;
     dense_ = false;
     why = 0;

@@ -107,6 +107,13 @@ public:
         return dense_ ? (size_t)n_ * n_ * 8 : plan_.sinv_bytes() + (windowed_ ? (size_t)2 * plan_.nb * plan_.B * win_ * 8 : 0) + tri_bytes_;
     }
     double factor_seconds = 0.0;
+    // pivot steps and row interchanges (pivot row != diagonal row) of the device factorisation, counted by the inversion kernels:
+    // out4 = {steps, interchanges} of the one-workgroup LDS inversions, {steps, interchanges} of the one-launch-per-step inversions
+    // (nested dissection: pivot blocks above kNdTinyPivot rows; block tridiagonal: every diagonal block).  Zeros for the dense form.
+    void pivot_counts(int out4[4]) const
+    {
+        for (int q = 0; q < 4; ++q) out4[q] = nd_.ready() ? nd_.pivot_counts()[q] : (q >= 2 && n_ > 0 && !dense_ ? bt_counts_[q - 2] : 0);
+    }
 
 private:
     NdSolver nd_;
@@ -115,6 +122,7 @@ private:
     bool allow_windowed_ = true, unroll_chain_ = true;
     int block_hint_ = 0;
     int n_ = 0;
+    int bt_counts_[2] = {0, 0};
     bool dense_ = true;
     double *inv_ = nullptr;  // dense form
     BtPlan plan_;            // (pieces dropped after upload; sizes kept)
@@ -147,8 +155,9 @@ private:
 void bt_launch_diag(int r0, int bs, int ld, const int *rp, const int *ci, const double *v, double *S, hipStream_t st);
 void bt_launch_schur(int r0, int bs, int o0, int obs, int ld, const BtDevCsr &out, const BtDevCsr &inT, const double *SinvO, double *S,
                      hipStream_t st);
+// counts: {pivot steps, row interchanges}, added to by the thread that records a step's pivot
 void bt_launch_invert(int bs, int ld, double *S, double *S2, double *col0, double *col1, int *pivots, int *colmap, int *singular,
-                      double *out, hipStream_t st);
+                      int *counts, double *out, hipStream_t st);
 void bt_launch_solve_step(const int r0[2], const int bs[2], const int blk[2], int nblk, int mode, int final_, int ld, size_t blk_stride,
                           const double *sinv, const int *perm, const BtDevCsr &A, const BtDevEll &E, int n, const double *b, double *z, double *x,
                           hipStream_t st);

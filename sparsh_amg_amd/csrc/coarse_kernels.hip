@@ -100,7 +100,7 @@ constexpr int kGjRows = 8;  // rows per workgroup
 
 __global__ __launch_bounds__(kCB) void bt_gj_kernel(int k, int bs, int ld, const double *__restrict__ src, double *__restrict__ dst,
                                                     const double *__restrict__ colcur, double *__restrict__ colnext,
-                                                    int *__restrict__ pivots, int *__restrict__ singular)
+                                                    int *__restrict__ pivots, int *__restrict__ singular, int *__restrict__ counts)
 {
     extern __shared__ double prow[];  // bs doubles: the scaled pivot row
     __shared__ double smax[kCB / 64];
@@ -143,6 +143,8 @@ __global__ __launch_bounds__(kCB) void bt_gj_kernel(int k, int bs, int ld, const
         if (blockIdx.x == 0) {
             pivots[k] = ix;
             if (!(b > 0.0)) *singular = 1;
+            atomicAdd(&counts[0], 1);  // pivot steps and row interchanges of the factorisation (integers)
+            if (ix != k) atomicAdd(&counts[1], 1);
         }
     }
     __syncthreads();
@@ -634,13 +636,13 @@ void bt_launch_schur(int r0, int bs, int o0, int obs, int ld, const BtDevCsr &ou
 
 // inverts S (bs x bs, ld) into out; S and S2 are scratch.  Enqueues bs + 3 launches.
 void bt_launch_invert(int bs, int ld, double *S, double *S2, double *col0, double *col1, int *pivots, int *colmap, int *singular,
-                      double *out, hipStream_t st)
+                      int *counts, double *out, hipStream_t st)
 {
     hipLaunchKernelGGL(bt_col0_kernel, dim3((bs + kCB - 1) / kCB), dim3(kCB), 0, st, bs, ld, S, col0);
     const int grid = (bs + kGjRows - 1) / kGjRows;
     double *src = S, *dst = S2, *cc = col0, *cn = col1;
     for (int k = 0; k < bs; ++k) {
-        hipLaunchKernelGGL(bt_gj_kernel, dim3(grid), dim3(kCB), (size_t)bs * sizeof(double), st, k, bs, ld, src, dst, cc, cn, pivots, singular);
+        hipLaunchKernelGGL(bt_gj_kernel, dim3(grid), dim3(kCB), (size_t)bs * sizeof(double), st, k, bs, ld, src, dst, cc, cn, pivots, singular, counts);
         double *t = src;
         src = dst;
         dst = t;

@@ -57,7 +57,8 @@ __global__ __launch_bounds__(kNB) void nd_extend_add_kernel(const NdDevNode *__r
 constexpr int kInvThreads = 256;
 
 __global__ __launch_bounds__(kInvThreads) void nd_invert_kernel(const NdDevNode *__restrict__ nodes, const int *__restrict__ list,
-                                                               const double *__restrict__ fronts, double *__restrict__ Bm, int *__restrict__ singular)
+                                                               const double *__restrict__ fronts, double *__restrict__ Bm, int *__restrict__ singular,
+                                                               int *__restrict__ counts)
 {
     __shared__ double M[kNdTinyPivot * (kNdTinyPivot + 1)];
     __shared__ double prow[kNdTinyPivot], fcol[kNdTinyPivot];
@@ -133,13 +134,18 @@ __global__ __launch_bounds__(kInvThreads) void nd_invert_kernel(const NdDevNode 
     }
     for (int j = tid; j < p; j += kInvThreads) cm[j] = j;
     __syncthreads();
-    if (tid == 0)
+    if (tid == 0) {
+        int swaps = 0;
         for (int k = p - 1; k >= 0; --k) {
             const int q = pivs[k];
             const int t = cm[k];
             cm[k] = cm[q];
             cm[q] = t;
+            swaps += (q != k);
         }
+        atomicAdd(&counts[0], p);  // pivot steps and row interchanges of this block (integers: the totals do not depend on the order)
+        atomicAdd(&counts[1], swaps);
+    }
     __syncthreads();
     double *__restrict__ out = Bm + nd.boff;
     for (int e = tid; e < p * p; e += kInvThreads) out[(size_t)(e / p) * ld + e % p] = M[(e / p) * lm + cm[e % p]];
@@ -164,7 +170,7 @@ __global__ __launch_bounds__(kNB) void nd_gj_col0_kernel(const NdGjNode *__restr
 }
 
 __global__ __launch_bounds__(kNB) void nd_gj_step_kernel(const NdGjNode *__restrict__ nodes, const int *__restrict__ wg_node, int k,
-                                                         int *__restrict__ singular)
+                                                         int *__restrict__ singular, int *__restrict__ counts)
 {
     extern __shared__ double prow[];
     __shared__ double smax[kNB / 64];
@@ -215,6 +221,8 @@ __global__ __launch_bounds__(kNB) void nd_gj_step_kernel(const NdGjNode *__restr
         if ((int)blockIdx.x == nd.wg0) {
             nd.piv[k] = ix;
             if (!(b > 0.0)) *singular = 1;
+            atomicAdd(&counts[0], 1);
+            if (ix != k) atomicAdd(&counts[1], 1);
         }
     }
     __syncthreads();
@@ -430,17 +438,17 @@ void nd_launch_extend_add(const NdDevNode *nodes, const int *children, int nchil
     hipLaunchKernelGGL(nd_extend_add_kernel, dim3(nchildren, (max_nu + kNB / 64 - 1) / (kNB / 64)), dim3(kNB), 0, st, nodes, children, rel_idx, fronts);
 }
 
-void nd_launch_invert(const NdDevNode *nodes, const int *list, int count, const double *fronts, double *Bm, int *singular, hipStream_t st)
+void nd_launch_invert(const NdDevNode *nodes, const int *list, int count, const double *fronts, double *Bm, int *singular, int *counts, hipStream_t st)
 {
     if (count <= 0) return;
-    hipLaunchKernelGGL(nd_invert_kernel, dim3(count), dim3(kInvThreads), 0, st, nodes, list, fronts, Bm, singular);
+    hipLaunchKernelGGL(nd_invert_kernel, dim3(count), dim3(kInvThreads), 0, st, nodes, list, fronts, Bm, singular, counts);
 }
 
-void nd_launch_gj_batched(const NdGjNode *nodes, int nnodes, const int *wg_node, int nwg, int max_p, int *singular, hipStream_t st)
+void nd_launch_gj_batched(const NdGjNode *nodes, int nnodes, const int *wg_node, int nwg, int max_p, int *singular, int *counts, hipStream_t st)
 {
     if (nnodes <= 0 || nwg <= 0) return;
     hipLaunchKernelGGL(nd_gj_col0_kernel, dim3(nwg), dim3(kNB), 0, st, nodes, wg_node);
-    for (int k = 0; k < max_p; ++k) hipLaunchKernelGGL(nd_gj_step_kernel, dim3(nwg), dim3(kNB), (size_t)max_p * sizeof(double), st, nodes, wg_node, k, singular);
+    for (int k = 0; k < max_p; ++k) hipLaunchKernelGGL(nd_gj_step_kernel, dim3(nwg), dim3(kNB), (size_t)max_p * sizeof(double), st, nodes, wg_node, k, singular, counts);
     hipLaunchKernelGGL(nd_gj_colmap_kernel, dim3(nnodes), dim3(kNB), 0, st, nodes);
     hipLaunchKernelGGL(nd_gj_unscramble_kernel, dim3(nwg), dim3(kNB), 0, st, nodes, wg_node);
 }

@@ -51,6 +51,7 @@ void NdSolver::release()
     bwd_.clear();
     n_ = nlevels_ = nnodes_ = leaf_ = max_np_ = launches_ = 0;
     factor_bytes_ = 0;
+    for (int &c : pivot_counts_) c = 0;
 }
 
 bool NdSolver::plan(const HostCsr &A, const NdParams &prm, std::string &err)
@@ -123,10 +124,10 @@ bool NdSolver::setup(const HostCsr &A, const NdParams &prm, hipStream_t st, std:
     long long *a_dst = nd_upload(tmp, P.a_dst, err);
     double *a_val = nd_upload(tmp, P.a_val, err);
     int *rel = nd_upload(tmp, P.rel_idx, err);
-    int *sing = nd_alloc<int>(tmp, 1, err);
+    int *sing = nd_alloc<int>(tmp, 5, err);  // the singular flag, then {pivot steps, row interchanges} of the two inverters
     if (!(fronts && a_dst && a_val && rel && sing)) return fail();
     (void)hipMemsetAsync(fronts, 0, P.front_doubles * sizeof(double), st);
-    (void)hipMemsetAsync(sing, 0, sizeof(int), st);
+    (void)hipMemsetAsync(sing, 0, 5 * sizeof(int), st);
     nd_launch_scatter((long long)P.a_dst.size(), a_dst, a_val, fronts, st);
     // scratch of the batched whole-chip inversion (pivot blocks above kNdTinyPivot rows): per level the second buffers of its blocks
     size_t gj_doubles = 0, gj_rows = 0;
@@ -218,7 +219,7 @@ bool NdSolver::setup(const HostCsr &A, const NdParams &prm, hipStream_t st, std:
         if (!small.empty()) {
             int *sl = nd_upload(tmp, small, err);
             if (!sl) return fail();
-            nd_launch_invert(nodes_, sl, (int)small.size(), fronts, Bm_, sing, st);
+            nd_launch_invert(nodes_, sl, (int)small.size(), fronts, Bm_, sing, sing + 1, st);
         }
         lap(t_inv);
         if (!big.empty()) {
@@ -227,7 +228,7 @@ bool NdSolver::setup(const HostCsr &A, const NdParams &prm, hipStream_t st, std:
             NdGjNode *bd = nd_upload(tmp, big, err);
             int *wd = nd_upload(tmp, wg_node, err);
             if (!bd || !wd) return fail();
-            nd_launch_gj_batched(bd, (int)big.size(), wd, (int)wg_node.size(), max_p, sing, st);
+            nd_launch_gj_batched(bd, (int)big.size(), wd, (int)wg_node.size(), max_p, sing, sing + 3, st);
         }
         lap(t_big);
         // -D^-1 F12 -> B_k[:, np:], F21 D^-1 -> Lh_k ; then F22 += F21 (-D^-1 F12)
@@ -264,8 +265,8 @@ bool NdSolver::setup(const HostCsr &A, const NdParams &prm, hipStream_t st, std:
     }
     if (timing) std::printf("nd timing: extend-add %.3f s, one-workgroup inversions %.3f s, whole-chip inversions %.3f s, products %.3f s\n", t_ext, t_inv, t_big, t_gemm);
     nd_launch_repack((long long)P.segs.size(), segs_d, Lm_, Lf_, st);
-    int sing_h = 0;
-    const bool copied = hipMemcpyAsync(&sing_h, sing, sizeof(int), hipMemcpyDeviceToHost, st) == hipSuccess;
+    int stat_h[5] = {0, 0, 0, 0, 0};
+    const bool copied = hipMemcpyAsync(stat_h, sing, sizeof(stat_h), hipMemcpyDeviceToHost, st) == hipSuccess;
     const hipError_t e = hipStreamSynchronize(st);
     for (void *p : tmp) (void)hipFree(p);
     tmp.clear();
@@ -274,7 +275,7 @@ bool NdSolver::setup(const HostCsr &A, const NdParams &prm, hipStream_t st, std:
         release();
         return false;
     }
-    if (sing_h) {
+    if (stat_h[0]) {
         why = 2;
         err = "coarsest-level matrix is singular (zero pivot in a pivot block of the multifrontal factorisation)";
         release();
@@ -285,6 +286,7 @@ bool NdSolver::setup(const HostCsr &A, const NdParams &prm, hipStream_t st, std:
     nnodes_ = nn;
     leaf_ = P.leaf;
     max_np_ = P.max_np;
+    for (int q = 0; q < 4; ++q) pivot_counts_[q] = stat_h[1 + q];
     // everything a solve streams: the factor rows, their gather indices (one int32 per forward element, one list per node for the
     // backward pass) and the row records
     factor_bytes_ = P.factor_bytes() + (P.fidx.size() + P.bidx.size()) * sizeof(int) + (size_t)2 * n * sizeof(NdRow);

@@ -65,6 +65,9 @@ public:
     int max_pivot_rows() const { return max_np_; }
     int launches_per_solve() const { return launches_; }
     size_t bytes() const { return factor_bytes_; }
+    // pivot steps and row interchanges (pivot row != diagonal row) of the last factorisation, counted by the kernels:
+    // {steps, interchanges} of the one-workgroup inversions, then of the whole-chip inversions
+    const int *pivot_counts() const { return pivot_counts_; }
     double factor_seconds = 0.0, plan_seconds = 0.0;
 
 private:
@@ -72,6 +75,7 @@ private:
     const void *pending_key_ = nullptr;
     int n_ = 0, nlevels_ = 0, nnodes_ = 0, leaf_ = 0, max_np_ = 0, launches_ = 0;
     size_t factor_bytes_ = 0;
+    int pivot_counts_[4] = {0, 0, 0, 0};
     std::vector<void *> allocs_;
     double *Bm_ = nullptr, *Lf_ = nullptr, *w_ = nullptr;  // backward rows, forward rows (per target row), [c | x] in the new numbering
     int *bidx_ = nullptr, *fidx_ = nullptr;
@@ -82,11 +86,11 @@ private:
     std::vector<Pass> fwd_, bwd_;  // per tree level
 };
 
-// launchers of nd_kernels.hip
+// launchers of nd_kernels.hip (counts: {pivot steps, row interchanges} of the kernel family, added to by the thread that records a pivot)
 void nd_launch_scatter(long long cnt, const long long *dst, const double *val, double *fronts, hipStream_t st);
 void nd_launch_extend_add(const NdDevNode *nodes, const int *children, int nchildren, int max_nu, const int *rel_idx, double *fronts, hipStream_t st);
-void nd_launch_invert(const NdDevNode *nodes, const int *list, int count, const double *fronts, double *Bm, int *singular, hipStream_t st);
-void nd_launch_gj_batched(const NdGjNode *nodes, int nnodes, const int *wg_node, int nwg, int max_p, int *singular, hipStream_t st);
+void nd_launch_invert(const NdDevNode *nodes, const int *list, int count, const double *fronts, double *Bm, int *singular, int *counts, hipStream_t st);
+void nd_launch_gj_batched(const NdGjNode *nodes, int nnodes, const int *wg_node, int nwg, int max_p, int *singular, int *counts, hipStream_t st);
 void nd_launch_gemm(const NdGemm *problems, const int *tiles, int ntiles, hipStream_t st);
 void nd_launch_repack(long long nseg, const NdSegment *segs, const double *Lh, double *Lf, hipStream_t st);
 void nd_launch_pass(bool forward, const NdRow *rows, int nrows, int nwide, int n, const double *M, const int *idx, double *w, const double *b, double *x,

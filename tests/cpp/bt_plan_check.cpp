@@ -2,17 +2,22 @@
 // pieces (diag / out / in / inT), the block partition and the inward/outward schedule are run
 // through a plain dense host emulation of what the device kernels do (Schur assembly from `out` and
 // `inT`, explicit block inverses, twisted solve) and the result is checked against A x = b.
-// No GPU needed.  argv: n_side dim(2|3) [target_blocks]
+// No GPU needed.  argv: n_side dim(2|3) [target_blocks [row_scale]]
+// row_scale (8): a seeded third of the rows is multiplied by it, so the pivot of a diagonal block is often not the diagonal row (the
+// plain grid never interchanges rows: it is diagonally dominant).  The output line counts pivot steps and interchanges.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <random>
 #include <string>
 #include <vector>
 
 #include "coarse.hpp"
 
 using namespace sparsh;
+
+static long long g_steps, g_swaps;  // pivot steps, and those whose pivot row was not the diagonal row
 
 static void invert(std::vector<double> &M, int n)  // Gauss-Jordan with partial pivoting, in place
 {
@@ -22,6 +27,8 @@ static void invert(std::vector<double> &M, int n)  // Gauss-Jordan with partial 
         for (int i = k + 1; i < n; ++i)
             if (std::fabs(M[(size_t)i * n + k]) > std::fabs(M[(size_t)p * n + k])) p = i;
         piv[k] = p;
+        ++g_steps;
+        g_swaps += p != k;
         if (p != k)
             for (int j = 0; j < n; ++j) std::swap(M[(size_t)k * n + j], M[(size_t)p * n + j]);
         const double rp = 1.0 / M[(size_t)k * n + k];
@@ -42,6 +49,7 @@ int main(int argc, char **argv)
     const int m = argc > 1 ? std::atoi(argv[1]) : 12;
     const int dim = argc > 2 ? std::atoi(argv[2]) : 3;
     const int target = argc > 3 ? std::atoi(argv[3]) : 8;
+    const double row_scale = argc > 4 ? std::atof(argv[4]) : 1.0;
     // grid Laplacian with a mild nonsymmetric perturbation (the reference factors with mtype 11, general)
     const int n = dim == 3 ? m * m * m : m * m;
     std::vector<int> rp(1, 0), ci;
@@ -65,6 +73,12 @@ int main(int argc, char **argv)
                 }
                 rp.push_back((int)ci.size());
             }
+    if (row_scale != 1.0) {
+        std::mt19937 rng(777);
+        for (int i = 0; i < n; ++i)
+            if (rng() % 3 == 0)
+                for (int j = rp[i]; j < rp[i + 1]; ++j) v[j] *= row_scale;
+    }
     HostCsr A = HostCsr::alias(n, n, rp.data(), ci.data(), v.data());
     BtPlan P;
     std::string err;
@@ -148,6 +162,6 @@ int main(int argc, char **argv)
         err2 += (x[i] - xref[i]) * (x[i] - xref[i]);
         ref2 += xref[i] * xref[i];
     }
-    std::printf("BT n %d bw %d B %d nb %d mid %d relerr %.3e\n", n, P.bw, B, nb, mid, std::sqrt(err2 / ref2));
+    std::printf("BT n %d bw %d B %d nb %d mid %d relerr %.3e steps %lld swaps %lld\n", n, P.bw, B, nb, mid, std::sqrt(err2 / ref2), g_steps, g_swaps);
     return std::sqrt(err2 / ref2) < 1e-10 ? 0 : 4;
 }

@@ -3,8 +3,17 @@
 // emulation of what the device kernels of csrc/nd_kernels.hip do (scatter, extend-add by child slot, Gauss-Jordan
 // inverse of the pivot block with partial pivoting, the three products, forward pull, backward product) and the
 // result is checked against A x = b.  No GPU needed.
-//   argv: kind(grid2|grid3|box|rand|blocks|arrow|diag) size leaf [merge_rows [top_merge_rows]]      (box: size = nx * 1000000 + ny * 1000 + nz)
+//   argv: kind(grid2|grid3|box|rand|blocks|arrow|diag|grid2x8|grid3x8|cliques|hadamard|singular) size leaf [merge_rows [top_merge_rows]]
+//         (box: size = nx * 1000000 + ny * 1000 + nz)
 //   env ND_PLAN_ONLY=1: statistics of the plan only (large cases)
+// The grid, box and random kinds are diagonally dominant: their pivot is always the diagonal row.  The kinds that make the
+// inversion interchange rows (the output line counts them, per size class of the device's two inverters):
+//   grid2x8 / grid3x8  the grid with a seeded third of its rows multiplied by 8
+//   cliques            dense diagonal blocks of 1, 2, 63, 64, 65, 79, 80, 81, 82, 128, 129 and 257 rows, entries random integers in
+//                      [-9, 9] (0 -> 1), b = A x_true with integer x_true; every block is one tree node (size is ignored)
+//   hadamard           Sylvester Hadamard blocks of 64, 128 and 256 rows with shuffled rows (size is ignored)
+//   singular           healthy cliques and one of `size` rows that is all ones, 2 on the diagonal, row 1 a copy of row 0: the last
+//                      pivot is exactly 0 and the emulation must stop with exit code 4
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -18,8 +27,12 @@
 
 using namespace sparsh;
 
+static const int kTinyPivot = 80;              // csrc/nd_solver.hpp kNdTinyPivot: one workgroup in LDS up to here, the whole chip above
+static long long g_steps[2], g_swaps[2];       // pivot steps and row interchanges: [0] blocks <= kTinyPivot rows, [1] larger blocks
+
 static bool invert(double *M, int n, int ld, double *out)  // as nd_invert_kernel
 {
+    const int cls = n > kTinyPivot;
     std::vector<int> piv((size_t)n);
     for (int k = 0; k < n; ++k) {
         int p = k;
@@ -27,6 +40,8 @@ static bool invert(double *M, int n, int ld, double *out)  // as nd_invert_kerne
             if (std::fabs(M[(size_t)i * ld + k]) > std::fabs(M[(size_t)p * ld + k])) p = i;
         piv[k] = p;
         if (!(std::fabs(M[(size_t)p * ld + k]) > 0.0)) return false;
+        ++g_steps[cls];
+        g_swaps[cls] += p != k;
         if (p != k)
             for (int j = 0; j < n; ++j) std::swap(M[(size_t)k * ld + j], M[(size_t)p * ld + j]);
         const double rp = 1.0 / M[(size_t)k * ld + k];
@@ -66,8 +81,40 @@ int main(int argc, char **argv)
     std::vector<int> rp(1, 0), ci;
     std::vector<double> v;
     int n = 0;
-    if (kind == "grid2" || kind == "grid3" || kind == "box") {
-        const int dim = kind == "grid2" ? 2 : 3;
+    bool exact_rhs = false;  // b = A x_true with small integers (exact in fp64) instead of the fixed pattern below
+    if (kind == "cliques" || kind == "hadamard" || kind == "singular") {
+        std::vector<int> sizes;
+        if (kind == "cliques") sizes = {1, 2, 63, 64, 65, 79, 80, 81, 82, 128, 129, 257};
+        if (kind == "hadamard") sizes = {64, 128, 256};
+        if (kind == "singular") sizes = {5, m, 70, 100};
+        std::mt19937 rng(2024);
+        exact_rhs = kind != "singular";
+        for (size_t q = 0; q < sizes.size(); ++q) {
+            const int s = sizes[q], r0 = n;
+            std::vector<int> order((size_t)s);
+            for (int i = 0; i < s; ++i) order[i] = i;
+            if (kind == "hadamard")
+                for (int i = s - 1; i > 0; --i) std::swap(order[i], order[rng() % (unsigned)(i + 1)]);
+            for (int i = 0; i < s; ++i) {
+                for (int j = 0; j < s; ++j) {
+                    double a;
+                    if (kind == "hadamard")
+                        a = (__builtin_popcount((unsigned)(order[i] & j)) & 1) ? -1.0 : 1.0;
+                    else if (kind == "singular" && q == 1)
+                        a = (i <= 1 ? 0 : i) == j ? 2.0 : 1.0;  // row 1 repeats row 0
+                    else {
+                        a = (double)((int)(rng() % 19) - 9);
+                        if (a == 0.0) a = 1.0;
+                    }
+                    ci.push_back(r0 + j);
+                    v.push_back(a);
+                }
+                rp.push_back((int)ci.size());
+            }
+            n += s;
+        }
+    } else if (kind == "grid2" || kind == "grid3" || kind == "box" || kind == "grid2x8" || kind == "grid3x8") {
+        const int dim = kind.compare(0, 5, "grid2") == 0 ? 2 : 3;
         const int nx = kind == "box" ? m / 1000000 : m, ny = kind == "box" ? (m / 1000) % 1000 : m, nz = kind == "box" ? m % 1000 : (dim == 3 ? m : 1);
         n = nx * ny * nz;
         auto idx = [&](int x, int y, int z) { return (z * ny + y) * nx + x; };
@@ -89,6 +136,12 @@ int main(int argc, char **argv)
                     }
                     rp.push_back((int)ci.size());
                 }
+        if (kind == "grid2x8" || kind == "grid3x8") {  // a power of two: the scaled entries stay exact
+            std::mt19937 rng(777);
+            for (int i = 0; i < n; ++i)
+                if (rng() % 3 == 0)
+                    for (int j = rp[i]; j < rp[i + 1]; ++j) v[j] *= 8.0;
+        }
     } else {
         // rand: random sparse pattern, structurally nonsymmetric, diagonally dominant; blocks: the same but in 3 disconnected
         // pieces of different size (one of them a single row) -- several roots, components inside the dissection
@@ -216,6 +269,11 @@ int main(int argc, char **argv)
         for (int t = 0; t < g.p; ++t) Lf[(size_t)g.dst + t] = Lm[(size_t)g.moff + t];
     std::vector<double> b((size_t)n), x((size_t)n, 0.0), w((size_t)2 * n, std::nan(""));
     for (int i = 0; i < n; ++i) b[i] = 1.0 + 0.37 * ((i * 31) % 17);
+    if (exact_rhs)
+        for (int i = 0; i < n; ++i) {
+            b[i] = 0.0;
+            for (int j = rp[i]; j < rp[i + 1]; ++j) b[i] += v[j] * (double)(1 + (ci[j] * 7) % 5);
+        }
     auto vec = [&](int g) { return g < 2 * n ? w[g] : b[g - 2 * n]; };
     auto gdot = [&](const NdRow &R, const std::vector<double> &M, const std::vector<int> &idx) {
         double acc = 0.0;
@@ -248,5 +306,10 @@ int main(int argc, char **argv)
     for (const NdSegment &g : P.segs) seg_len += g.p;
     std::printf("n %d nodes %d levels %d max_pivot %d max_children %d factor_MB %.2f front_MB %.2f relerr %.3e\n", n, nn, P.nlevels, P.max_np,
                 P.max_children, P.factor_bytes() / 1e6, P.front_bytes() / 1e6, rel);
+    std::printf("pivoting: rows<=%d steps %lld swaps %lld ; rows>%d steps %lld swaps %lld\n", kTinyPivot, g_steps[0], g_swaps[0], kTinyPivot, g_steps[1], g_swaps[1]);
+    std::printf("pivot_rows");
+    if (nn <= 64)
+        for (int k = 0; k < nn; ++k) std::printf(" %d", P.nodes[k].np);
+    std::printf("\n");
     return rel < 1e-12 ? 0 : 1;
 }

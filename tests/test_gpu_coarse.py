@@ -56,8 +56,8 @@ def _nonsym2d(m):
     ("p2d_100_chain_step_by_step", lambda: problems.poisson2d(100), 2),       # the same, one launch per chain step
     ("nonsym2d_60_window64_short_last_block", lambda: _nonsym2d(60), True),   # window 64, last block (16 rows) shorter than a window
     ("nonsym2d_170", lambda: _nonsym2d(170), True),
-    ("nonsym2d_170_chain_step_by_step", lambda: _nonsym2d(170), 2),            # 28 900 rows: interface form, pivoting, last block (100 rows) shorter than a window
-    ("nonsym3d_22", lambda: _nonsym3d(22), True),              # pivoting inside the diagonal blocks
+    ("nonsym2d_170_chain_step_by_step", lambda: _nonsym2d(170), 2),            # 28 900 rows: interface form, nonsymmetric, last block (100 rows) shorter than a window
+    ("nonsym3d_22", lambda: _nonsym3d(22), True),              # nonsymmetric: 14 of 10 648 pivot steps interchange rows (coarse_info row_swaps_chip), every other case here 0; pivoting proper: test_gpu_coarse_pivoting.py
     ("p3d_ragged_last_block", lambda: problems.poisson3d(21), True),  # 9261 rows: short last block
 ])
 def test_block_tridiagonal_solver_vs_sparse_lu(name, gen, interface):
@@ -110,9 +110,9 @@ def _squared(m):
     ("p2d_150", lambda: problems.poisson2d(150), 0, -1, -1),
     ("p2d_150_no_top_merge", lambda: problems.poisson2d(150), 0, -1, 0),
     ("nonsym2d_170", lambda: _nonsym2d(170), 0, -1, -1),               # 28 900 rows, nonsymmetric
-    ("nonsym3d_22", lambda: _nonsym3d(22), 0, -1, -1),                 # not diagonally dominant: pivoting inside the pivot blocks
+    ("nonsym3d_22", lambda: _nonsym3d(22), 0, -1, -1),                 # nonsymmetric: 12 of 10 648 pivot steps interchange rows, all in blocks above 80 rows (pivoting proper: test_gpu_coarse_pivoting.py)
     ("p3d_ragged", lambda: problems.poisson3d(21), 32, 100, 300),
-    ("fem_20000", lambda: _fem(20000), 0, -1, -1),                     # unstructured P1-FEM mesh: irregular separators, many children per node
+    ("fem_20000", lambda: _fem(20000), 0, -1, -1),                     # unstructured P1-FEM mesh: irregular separators, many children per node (17 of 20 000 steps interchange rows)
     ("p3d_22_squared", lambda: _squared(22), 0, -1, -1),              # 10 648 rows, 25 entries per row: two-cell-wide separators
     ("p3d_40_top_separator_above_1024_rows", lambda: problems.poisson3d(40), 0, -1, -1),  # 64 000 rows: the top pivot block takes the whole-chip inversion
 ])

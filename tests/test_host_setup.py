@@ -202,10 +202,7 @@ def test_product_does_not_touch_oracle():
     assert not bad, bad
 
 
-@pytest.mark.parametrize("args", [("12", "3", "8"), ("40", "2", "8"), ("9", "3", "3"), ("30", "2", "2"), ("70", "2", "64")])
-def test_block_tridiagonal_plan_on_host(tmp_path_factory, args):
-    """csrc/coarse.cpp bt_make_plan (RCM blocks, diag/out/in pieces, inward/outward schedule) driven through a
-    dense host emulation of the device kernels' algebra: the twisted block factorisation must solve A x = b."""
+def _bt_plan_check(tmp_path_factory, args):
     import subprocess
 
     d = tmp_path_factory.getbasetemp() / "btplan"
@@ -220,10 +217,45 @@ def test_block_tridiagonal_plan_on_host(tmp_path_factory, args):
         assert r.returncode == 0, r.stderr[-2000:]
     r = subprocess.run([str(exe), *args], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, (r.returncode, r.stdout, r.stderr[-500:])
-    assert "relerr" in r.stdout
+    return r.stdout
 
 
-def _nd_plan_check(tmp_path_factory, args, env=None):
+def _field(out, key):
+    """The number after `key` in a check program's output."""
+    w = out.split()
+    return float(w[w.index(key) + 1])
+
+
+BT_GRID_ARGS = [("12", "3", "8"), ("40", "2", "8"), ("9", "3", "3"), ("30", "2", "2"), ("70", "2", "64")]
+
+
+@pytest.mark.parametrize("args", BT_GRID_ARGS)
+def test_block_tridiagonal_plan_on_host(tmp_path_factory, args):
+    """csrc/coarse.cpp bt_make_plan (RCM blocks, diag/out/in pieces, inward/outward schedule) driven through a
+    dense host emulation of the device kernels' algebra: the twisted block factorisation must solve A x = b."""
+    out = _bt_plan_check(tmp_path_factory, args)
+    assert "relerr" in out
+
+
+@pytest.mark.parametrize("args", BT_GRID_ARGS[:2])
+def test_block_tridiagonal_grid_inputs_never_interchange_rows(tmp_path_factory, args):
+    """The grid operators are diagonally dominant: the pivot of every step is the diagonal row, so they say nothing about the
+    interchange, the redirected source row or the column un-permutation of the inversion (emulated or on the device)."""
+    out = _bt_plan_check(tmp_path_factory, args)
+    assert _field(out, "steps") == _field(out, "n") and _field(out, "swaps") == 0, out
+
+
+@pytest.mark.parametrize("args", [("100", "2", "32", "8"), ("21", "3", "32", "8"), ("12", "3", "8", "8")])
+def test_block_tridiagonal_row_scaled_grids_interchange_rows(tmp_path_factory, args):
+    """A seeded third of the rows times 8: the emulated in-block pivoting interchanges rows in a good part of the steps and the
+    twisted factorisation still solves to 1e-12.  The first two are the shapes test_gpu_coarse_pivoting.py runs on the device (the
+    device's 32 target blocks: 10 000 rows in blocks of 320, 9261 rows in blocks of 384 with a ragged last one)."""
+    out = _bt_plan_check(tmp_path_factory, args)
+    assert _field(out, "steps") == _field(out, "n") and _field(out, "swaps") > 0.1 * _field(out, "n"), out
+    assert _field(out, "relerr") < 1e-12, out
+
+
+def _nd_plan_check(tmp_path_factory, args, env=None, expect_rc=0):
     import subprocess
 
     d = tmp_path_factory.getbasetemp() / "ndplan"
@@ -235,7 +267,7 @@ def _nd_plan_check(tmp_path_factory, args, env=None):
         r = subprocess.run(cmd, capture_output=True, text=True)
         assert r.returncode == 0, r.stderr[-2000:]
     r = subprocess.run([str(exe), *args], capture_output=True, text=True, timeout=600, env=dict(os.environ, **(env or {})))
-    assert r.returncode == 0, (r.returncode, r.stdout, r.stderr[-500:])
+    assert r.returncode == expect_rc, (r.returncode, r.stdout, r.stderr[-500:])
     return r.stdout
 
 
@@ -250,6 +282,100 @@ def test_nested_dissection_plan_solves_on_the_host(tmp_path_factory, args):
     factorisation must solve A x = b to 1e-12 on grids, a box, random nonsymmetric patterns and a matrix made of disconnected pieces."""
     out = _nd_plan_check(tmp_path_factory, list(args))
     assert "relerr" in out
+
+
+def _nd_pivoting(out):
+    """((steps, swaps) of the pivot blocks up to 80 rows, (steps, swaps) of the larger ones) from nd_plan_check's output."""
+    w = out[out.index("pivoting:"):].split()
+    return (int(w[3]), int(w[5])), (int(w[9]), int(w[11]))
+
+
+@pytest.mark.parametrize("args", [("grid3", "10", "32"), ("grid3", "12", "32", "0"), ("grid2", "40", "32"), ("blocks", "2000", "16")])
+def test_nested_dissection_old_inputs_never_interchange_rows(tmp_path_factory, args):
+    """The emulation's grid, box and random inputs are diagonally dominant: 0 interchanges in thousands of pivot steps, so its own
+    interchange and column-map code is checked by the inputs of the next test alone.  (On the device the grids of test_gpu_coarse.py
+    count 0 as well, but for nonsym3d_22 -- 12 to 14 of 10 648 steps, in Schur complements -- and the FEM mesh, 17 of 20 000.)"""
+    out = _nd_plan_check(tmp_path_factory, list(args))
+    small, large = _nd_pivoting(out)
+    assert small[0] + large[0] == _field(out, "n")
+    assert small[1] == 0 and large[1] == 0 and small[0] > 0
+
+
+@pytest.mark.parametrize("args,small_swaps,large_swaps", [
+    (("cliques", "0", "64"), True, True),                # default dissection parameters
+    (("cliques", "0", "16", "0", "0"), True, True),      # plain bisection
+    (("hadamard", "0", "64"), True, True),
+    (("grid3x8", "12", "64"), True, True),               # the top separator (578 rows) takes the whole-chip scheme
+    (("grid3x8", "14", "16", "0", "0"), True, True),     # small leaves, no merging: most pivot blocks in one workgroup's LDS
+    (("grid2x8", "80", "16"), True, True),
+])
+def test_nested_dissection_pivoting_inputs_on_the_host(tmp_path_factory, args, small_swaps, large_swaps):
+    """Inputs that make the pivot-block inversions interchange rows (tests/cpp/nd_plan_check.cpp), in both size classes of the
+    device's inverters: the emulation must still solve to 1e-12 (its exit code), which checks its interchange, its lowest-index
+    tie rule and its column un-permutation -- and fixes what test_gpu_coarse_pivoting.py may expect of the device."""
+    out = _nd_plan_check(tmp_path_factory, list(args))
+    small, large = _nd_pivoting(out)
+    assert small[0] + large[0] == _field(out, "n")
+    assert (small[1] > 0) == small_swaps and (large[1] > 0) == large_swaps, out
+    assert _field(out, "relerr") < 1e-12
+    if args[0] == "cliques":
+        # a dense component cannot be dissected: every clique is one tree node, so the pivot blocks sit on the LDS limit (80 | 81),
+        # around a wave (63, 64, 65), off the 8 rows of a workgroup (81, 129, 257) and past 256 columns (257)
+        sizes = [1, 2, 63, 64, 65, 79, 80, 81, 82, 128, 129, 257]
+        rows = [int(t) for t in out[out.index("pivot_rows"):].split()[1:]]
+        assert sorted(rows) == sizes and _field(out, "levels") == 1 and _field(out, "max_pivot") == 257
+        assert small[0] == sum(t for t in sizes if t <= 80) and large[0] == sum(t for t in sizes if t > 80)
+        assert small[1] > 0.8 * small[0] and large[1] > 0.8 * large[0]   # random integers: nearly every step interchanges
+    if args[0] == "hadamard":
+        assert _field(out, "relerr") == 0.0   # dyadic rationals throughout: exact
+
+
+@pytest.mark.parametrize("rows", ["2", "96"])
+def test_nested_dissection_emulation_meets_the_exact_zero_pivot(tmp_path_factory, rows):
+    """The singular clique (two equal rows, first pivot a power of two) leaves a pivot of exactly 0 in a block of either size class."""
+    out = _nd_plan_check(tmp_path_factory, ["singular", rows, "64"], expect_rc=4)
+    assert "singular pivot block" in out
+
+
+def test_pivoting_inputs_and_the_restated_inversion_in_numpy():
+    """tests/coarse_pivot_inputs.py, the inputs and the reference of test_gpu_coarse_pivoting.py, on the CPU: a dense partial-pivot
+    LU of the operators test_gpu_coarse.py runs (small instances, natural and random order) never interchanges rows, one of the
+    new inputs does; the numpy restatement of the device's Gauss-Jordan inverts the
+    shuffled Hadamard blocks bit for bit, solves the integer cliques as well as LAPACK does, and meets the exact zero pivot."""
+    import scipy.sparse as sp
+
+    import coarse_pivot_inputs as cp
+    from test_gpu_coarse import _nonsym2d, _nonsym3d
+
+    for gen in (lambda: _nonsym3d(7), lambda: _nonsym2d(18), lambda: problems.poisson2d(18), lambda: problems.poisson3d(7)):
+        rp, ci, v = gen()
+        n = len(rp) - 1
+        dense = sp.csr_matrix((v, ci, rp), shape=(n, n)).toarray()
+        assert cp.lu_row_swaps(dense) == 0
+        order = np.random.default_rng(2).permutation(n)
+        assert cp.lu_row_swaps(dense[np.ix_(order, order)]) == 0
+    for gen in (lambda: problems.poisson2d(18), lambda: problems.poisson3d(7)):
+        rp, ci, v = cp.scale_rows(*gen())
+        n = len(rp) - 1
+        assert cp.lu_row_swaps(sp.csr_matrix((v, ci, rp), shape=(n, n)).toarray()) > n // 10
+    blocks, perms = cp.hadamard_blocks()
+    for Bk, perm in zip(blocks, perms):
+        inv, swaps, singular = cp.gauss_jordan_inverse(Bk)
+        assert np.array_equal(inv, cp.hadamard_exact_inverse(Bk, perm)) and swaps > len(perm) // 2 and not singular
+        assert np.array_equal(Bk @ inv, np.eye(len(perm)))
+    x_true = cp.integer_vector(sum(cp.CLIQUE_SIZES), 7)
+    r0 = 0
+    for Bk in cp.clique_blocks():
+        s = Bk.shape[0]
+        xt = x_true[r0:r0 + s]
+        r0 += s
+        inv, swaps, singular = cp.gauss_jordan_inverse(Bk)
+        assert not singular and (swaps > 0.8 * s or s < 3)
+        err = np.abs(inv @ (Bk @ xt) - xt).max() / np.abs(xt).max()
+        assert err <= 1e-11, (s, err)   # (condition numbers up to 5e3: measured 0 - 2e-13, as np.linalg.solve)
+    for m in (2, 96):
+        assert cp.gauss_jordan_inverse(cp.singular_clique(m))[2]
+        assert not cp.gauss_jordan_inverse(cp.singular_clique(m) + np.eye(m))[2]
 
 
 def test_nested_dissection_plan_of_the_100cubed_coarsest_level(tmp_path_factory):
