@@ -459,7 +459,9 @@ int sparsh_op_gmres_small(sparsh_handle h, int m, int nblk, const double *hcol, 
  * SPARSH_BASIS_FP32 on the handle, SPARSH_ESTATE otherwise), 16 the last post-sweep with its dot through the plane-marching kernel on
  * the level's resident buffers (SPARSH_ESTATE where the level does not run it), 17 one Chebyshev step (the k >= 1 form: both
  * coefficients and the previous correction in use) ping-ponging on the level's resident x / x2 buffers with its d vector and r as
- * the right-hand side: the counterpart of 10 (single-GPU handles). */
+ * the right-hand side: the counterpart of 10 (single-GPU handles), 18 one projection onto mean zero with its dot (launch_sum +
+ * launch_project, see "singular systems" below) on level 0's resident x and r (`level` must be 0; single-GPU handles; needs no
+ * SPARSH_NULLSPACE_CONSTANT handle). */
 int sparsh_bench_op(sparsh_handle h, int op, int level, int reps, double *avg_seconds);
 
 /* ---- restarted GMRES (SPARSH_GMRES, SPARSH_PGMRES) ----
@@ -601,6 +603,46 @@ int sparsh_set_cycle(sparsh_handle h, int kind, int stride);
 int sparsh_cycle_info(sparsh_handle h, int *kind, int *stride, int *nlevels_wk, long *level_visits, long *bytes);
 int sparsh_level_cycle(sparsh_handle h, int level, int *is_wk, long *visits);
 int sparsh_op_kstep(sparsh_handle h, int level, const double *b, const double *c, const double *d, double *r, double *x, double *scal8);
+
+/* ---- singular systems: the constant vector as the null space (pure Neumann, fully periodic) ----
+ * Opt-in: under SPARSH_NULLSPACE_NONE (the default) every path, launch and bit is what it was.  SPARSH_NULLSPACE_CONSTANT states that
+ * A 1 = 0 and 1^T A = 0; the solvers then solve the consistent problem A x = b - mean(b) for the x of mean zero.
+ * sparsh_set_nullspace stores the kind on the handle (no device needed); the next sparsh_setup_host / sparsh_setup reads it.  Any other
+ * value is SPARSH_EINVAL and changes nothing.
+ * sparsh_nullspace_info: the kind the present hierarchy was built with (NONE before any setup), the pinned row of the coarsest level
+ * (-1: none) and the two defects of level 0 (0 under NONE); any pointer may be NULL.
+ * Setup under CONSTANT.  row_defect = max_i |sum_j a_ij| / sum_j |a_ij| and col_defect, the same over the columns, are taken on
+ * level 0; either above 1e-12 is SPARSH_EINVAL (the message says the constant vector is not in the null space and gives the value).
+ * Also SPARSH_EINVAL, each message naming the null space: Beck coarsening (params.coarsening = 1: its interpolation does not reproduce
+ * constants exactly), params.precond_fp32, a handle with a multi-rank transport.  The coarsest-level solver -- the dense inverse
+ * (sparsh_coarse_inverse returns it), the nested-dissection and the block-tridiagonal factorisation alike -- gets A_L with row and
+ * column nL - 1 replaced by the unit row and column (pinned_row = nL - 1), a nonsingular matrix; A_L itself stays on the level
+ * (sparsh_level_csr, the level's SpMV).  A single-level hierarchy is pinned the same way.  A larger null space (a disconnected
+ * domain) is out of scope and behaves as any singular matrix does under NONE.
+ * Solves on a hierarchy built under CONSTANT (one GPU, fp64):
+ *   - at the start of every solve (SPARSH_AMG .. SPARSH_FCG, sparsh_vcycle*, sparsh_krylov_init_dev) the right-hand side is copied to
+ *     a vector of the engine and projected there, b - mean(b): the caller's b is never written; the initial guess x is projected in place;
+ *   - every application of the preconditioner returns z - mean(z) (all smoothers, all cycle kinds, sparsh_op_precond included); where
+ *     the Krylov loop wants the partial sums of z.r fused, the projection launch delivers them in place of the cycle's last sweep;
+ *   - x is projected once more when a solve returns and when a sparsh_krylov_step_dev call returns (rounding drift; the Jacobi legs of
+ *     the stand-alone SPARSH_AMG iteration move the mean).
+ * Histories and the stopping test are those of the projected system.  params.use_graph is accepted and ignored under CONSTANT.
+ * sparsh_solve_multi* and sparsh_op_precond_multi return SPARSH_EINVAL on such a handle.
+ * A projection is two launches without a host read or atomics: per-workgroup partial sums of x; then every workgroup adds those in one
+ * fixed order, so all hold the same mean bit for bit, and stores x_i - mean (and the partial sums of (x_i - mean) r_i) -- bitwise
+ * reproducible run to run.
+ * Test hooks (any n > 0; they need a ready single-GPU handle for its stream only, as sparsh_op_gs_*): sparsh_op_project: x -= mean(x),
+ * *mean = the mean removed; sparsh_op_project_dot: z -= mean(z) and *dot = z.r of the projected z (partial sums + the engine's final
+ * reduction).  Host vectors; the device copies are 16-byte aligned.  sparsh_op_project_dev is the same pair of launches on device
+ * vectors, which may sit on any 8-byte boundary (r_dev NULL: no dot; mean / dot may be NULL).
+ * sparsh_bench_op op 18: one such pair with the dot on level 0's resident x and r (`level` must be 0; no CONSTANT handle needed). */
+#define SPARSH_NULLSPACE_NONE 0      /* default: every path, launch and bit as today */
+#define SPARSH_NULLSPACE_CONSTANT 1  /* A 1 = 0 and 1^T A = 0: solve the consistent, mean-free problem */
+int sparsh_set_nullspace(sparsh_handle h, int kind);
+int sparsh_nullspace_info(sparsh_handle h, int *kind, int *pinned_row, double *row_defect, double *col_defect);
+int sparsh_op_project(sparsh_handle h, int n, double *x, double *mean);                       /* x -= mean(x) */
+int sparsh_op_project_dot(sparsh_handle h, int n, double *z, const double *r, double *mean, double *dot); /* z -= mean(z); dot = z.r */
+int sparsh_op_project_dev(sparsh_handle h, int n, double *x_dev, const double *r_dev, double *mean, double *dot);
 
 /* ---- a block of up to SPARSH_MAX_RHS right-hand sides in one AMG-PCG run ----
  * k systems with one matrix -- load cases, solution components, columns of a block method -- solved together: every kernel of the

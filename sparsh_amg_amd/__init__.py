@@ -30,6 +30,8 @@ METHODS = {"amg": SPARSH_AMG, "cg": SPARSH_CG, "pcg": SPARSH_PCG, "bicg": SPARSH
 FLEXIBLE_METHODS = {"fcg": SPARSH_FCG}  # methods whose preconditioner may change between applications (the K-cycle)
 SPARSH_CYCLE_V, SPARSH_CYCLE_W, SPARSH_CYCLE_K = 0, 1, 2
 CYCLES = {"v": SPARSH_CYCLE_V, "w": SPARSH_CYCLE_W, "k": SPARSH_CYCLE_K}
+SPARSH_NULLSPACE_NONE, SPARSH_NULLSPACE_CONSTANT = 0, 1
+NULLSPACES = {"none": SPARSH_NULLSPACE_NONE, "constant": SPARSH_NULLSPACE_CONSTANT}
 SPARSH_SMOOTH_JACOBI, SPARSH_SMOOTH_SOR, SPARSH_SMOOTH_CHEBYSHEV = 0, 1, 3
 SPARSH_SOR_FORWARD, SPARSH_SOR_SYMMETRIC = 0, 1
 SPARSH_BASIS_FP64, SPARSH_BASIS_FP32 = 0, 1
@@ -221,6 +223,11 @@ def _load():
         "sparsh_cycle_info": (C.c_int, [H, c_int_p, c_int_p, c_int_p, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
         "sparsh_level_cycle": (C.c_int, [H, C.c_int, c_int_p, C.POINTER(C.c_long)]),
         "sparsh_op_kstep": (C.c_int, [H, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p]),
+        "sparsh_set_nullspace": (C.c_int, [H, C.c_int]),
+        "sparsh_nullspace_info": (C.c_int, [H, c_int_p, c_int_p, c_dbl_p, c_dbl_p]),
+        "sparsh_op_project": (C.c_int, [H, C.c_int, c_dbl_p, c_dbl_p]),
+        "sparsh_op_project_dot": (C.c_int, [H, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p]),
+        "sparsh_op_project_dev": (C.c_int, [H, C.c_int, C.c_void_p, C.c_void_p, c_dbl_p, c_dbl_p]),
         "sparsh_set_gmres": (C.c_int, [H, C.c_int]),
         "sparsh_gmres_info": (C.c_int, [H, c_int_p, C.POINTER(C.c_long)]),
         "sparsh_set_gmres_basis": (C.c_int, [H, C.c_int]),
@@ -598,6 +605,65 @@ class sp_matrix_mg:
         return r, x, s
 
     # -- restarted GMRES -----------------------------------------------------------------------
+    # -- constant null space ---------------------------------------------------------------------
+    def set_nullspace(self, kind="constant"):
+        """Null space of the matrix, read by the next setup: "none" (default) or "constant" (A 1 = 0 and 1^T A = 0: pure Neumann,
+        fully periodic).  Under "constant" the solvers return the solution of mean zero of A x = b - mean(b)."""
+        k = NULLSPACES[kind.lower()] if isinstance(kind, str) else int(kind)
+        _check(lib.sparsh_set_nullspace(self._h, k))
+        return self
+
+    def nullspace_info(self):
+        """dict(kind, pinned_row, row_defect, col_defect) of the present hierarchy ("none", -1, 0, 0 before a setup)."""
+        k, row = C.c_int(), C.c_int()
+        rd, cd = C.c_double(), C.c_double()
+        _check(lib.sparsh_nullspace_info(self._h, C.byref(k), C.byref(row), C.byref(rd), C.byref(cd)))
+        return dict(kind={v: n for n, v in NULLSPACES.items()}[k.value], pinned_row=row.value, row_defect=rd.value, col_defect=cd.value)
+
+    def _project_shifted(self, x, r, offset, r_offset):
+        """the projection launches on device copies that start `offset` / `r_offset` doubles behind a 16-byte boundary"""
+        n = x.size
+        xd = self.dev_alloc((n + offset) * 8)
+        rd = self.dev_alloc((n + r_offset) * 8) if r is not None else None
+        try:
+            xs = C.c_void_p(xd.value + 8 * offset)
+            self.h2d(xs, x)
+            rs = None
+            if r is not None:
+                rs = C.c_void_p(rd.value + 8 * r_offset)
+                self.h2d(rs, r)
+            mean, dot = C.c_double(), C.c_double()
+            _check(lib.sparsh_op_project_dev(self._h, n, xs, rs, C.byref(mean), C.byref(dot)))
+            out = np.empty(n)
+            self.d2h(out, xs)
+        finally:
+            self.dev_free(xd)
+            if rd is not None:
+                self.dev_free(rd)
+        return out, mean.value, dot.value
+
+    def op_project(self, x, offset=0):
+        """(x - mean(x), mean) through the projection kernels (any length; the handle lends its stream only).  offset = 1: the
+        device vector starts 8 bytes behind a 16-byte boundary, as a caller's _dev vector may."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if offset:
+            out, mean, _ = self._project_shifted(x, None, int(offset), 0)
+            return out, mean
+        out, mean = x.copy(), C.c_double()
+        _check(lib.sparsh_op_project(self._h, out.size, _dp(out), C.byref(mean)))
+        return out, mean.value
+
+    def op_project_dot(self, z, r, offset=0, r_offset=None):
+        """(z - mean(z), mean, (z - mean(z)) . r); offset / r_offset as for op_project (r_offset defaults to offset)."""
+        z = np.ascontiguousarray(z, dtype=np.float64)
+        r = np.ascontiguousarray(r, dtype=np.float64)
+        r_offset = offset if r_offset is None else r_offset
+        if offset or r_offset:
+            return self._project_shifted(z, r, int(offset), int(r_offset))
+        out, mean, dot = z.copy(), C.c_double(), C.c_double()
+        _check(lib.sparsh_op_project_dot(self._h, out.size, _dp(out), _dp(r), C.byref(mean), C.byref(dot)))
+        return out, mean.value, dot.value
+
     def set_gmres(self, restart=0, basis=None):
         """Restart length of "gmres" / "pgmres": 1..64, 0 = the default of 30.  basis: "fp64" (the default of a handle) or "fp32" =
         basis vectors stored as float with all arithmetic in fp64 (sparsh_set_gmres_basis); None leaves the precision alone.
@@ -960,7 +1026,7 @@ class sp_matrix_mg:
         ops = {"spmv": 0, "jacobi": 1, "residual": 2, "restrict": 3, "prolong": 4, "coarse": 5, "dot": 6, "axpby": 7, "copy_int": 8,
                "jacobi_pingpong": 9, "jacobi_pingpong_resident": 10, "jacobi_double": 11, "sor": 12,
                "gmres_orth": 13, "gmres_orth_unfused": 14, "gmres_orth_fp32_basis": 15, "jacobi_dot_marching": 16,
-               "chebyshev_pingpong_resident": 17}
+               "chebyshev_pingpong_resident": 17, "project_dot": 18}
         sec = C.c_double()
         _check(lib.sparsh_bench_op(self._h, ops[op] if isinstance(op, str) else op, level, reps, C.byref(sec)))
         return sec.value

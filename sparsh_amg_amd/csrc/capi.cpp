@@ -356,7 +356,7 @@ long sparsh_debug_hierarchy_roundtrip(sparsh_handle h, long truncate_to)
                std::memcmp(a.val, b.val, nnz * sizeof(double)) == 0;
     };
     bool same = G.levels.size() == H.levels.size() && G.nL == H.nL && G.coarse_dense == H.coarse_dense && G.extended == H.extended &&
-                G.coarse_inverse == H.coarse_inverse;
+                G.nullspace == H.nullspace && G.pinned_row == H.pinned_row && G.coarse_inverse == H.coarse_inverse;
     for (size_t l = 0; same && l < H.levels.size(); ++l)
         same = same_csr(G.levels[l].A, H.levels[l].A) && same_csr(G.levels[l].P, H.levels[l].P) && same_csr(G.levels[l].R, H.levels[l].R) &&
                G.levels[l].diag == H.levels[l].diag && G.levels[l].P_is_aggregation == H.levels[l].P_is_aggregation;
@@ -1437,6 +1437,64 @@ int sparsh_op_kstep(sparsh_handle h, int level, const double *b, const double *c
     return done(E, ok);
 }
 
+// ---- constant null space ----
+
+int sparsh_set_nullspace(sparsh_handle h, int kind)
+{
+    if (!h || !h->eng) return fail(SPARSH_EINVAL, "null handle");
+    if (kind != SPARSH_NULLSPACE_NONE && kind != SPARSH_NULLSPACE_CONSTANT)
+        return fail(SPARSH_EINVAL, "null space kind must be SPARSH_NULLSPACE_NONE (0) or SPARSH_NULLSPACE_CONSTANT (1)");
+    h->eng->set_nullspace(kind);
+    return SPARSH_OK;
+}
+
+int sparsh_nullspace_info(sparsh_handle h, int *kind, int *pinned_row, double *row_defect, double *col_defect)
+{
+    if (!h || !h->eng) return fail(SPARSH_EINVAL, "null handle");
+    const Engine &E = *h->eng;
+    const bool on = E.nullspace_built() == SPARSH_NULLSPACE_CONSTANT;
+    if (kind) *kind = E.nullspace_built();
+    if (pinned_row) *pinned_row = on ? E.pinned_row() : -1;
+    if (row_defect) *row_defect = on ? E.row_defect() : 0.0;
+    if (col_defect) *col_defect = on ? E.col_defect() : 0.0;
+    return SPARSH_OK;
+}
+
+// x -= mean(x) on a device vector of any 8-byte alignment (r_dev non-null: *dot = x.r of the projected x)
+int sparsh_op_project_dev(sparsh_handle h, int n, double *x_dev, const double *r_dev, double *mean, double *dot)
+{
+    if (!h || !h->eng || !x_dev || n <= 0) return fail(SPARSH_EINVAL, "bad arguments");
+    REQUIRE_READY(h);
+    REQUIRE_SINGLE(h);
+    Engine &E = *h->eng;
+    if (int rc = E.op_project(n, x_dev, r_dev, mean, dot); rc != SPARSH_OK) return fail(rc, E.error);
+    return SPARSH_OK;
+}
+
+int sparsh_op_project(sparsh_handle h, int n, double *x, double *mean)
+{
+    if (!h || !h->eng || !x || n <= 0) return fail(SPARSH_EINVAL, "bad arguments");
+    REQUIRE_READY(h);
+    REQUIRE_SINGLE(h);
+    Engine &E = *h->eng;
+    DBuf dx(E, (size_t)n, x);
+    if (!dx.p) return fail(SPARSH_ENODEV, E.error);
+    if (int rc = sparsh_op_project_dev(h, n, dx.p, nullptr, mean, nullptr); rc != SPARSH_OK) return rc;
+    return done(E, dx.get(x));
+}
+
+int sparsh_op_project_dot(sparsh_handle h, int n, double *z, const double *r, double *mean, double *dot)
+{
+    if (!h || !h->eng || !z || !r || n <= 0) return fail(SPARSH_EINVAL, "bad arguments");
+    REQUIRE_READY(h);
+    REQUIRE_SINGLE(h);
+    Engine &E = *h->eng;
+    DBuf dz(E, (size_t)n, z), dr(E, (size_t)n, r);
+    if (!dz.p || !dr.p) return fail(SPARSH_ENODEV, E.error);
+    if (int rc = sparsh_op_project_dev(h, n, dz.p, dr.p, mean, dot); rc != SPARSH_OK) return rc;
+    return done(E, dz.get(z));
+}
+
 int sparsh_set_gmres(sparsh_handle h, int restart)
 {
     if (!h || !h->eng) return fail(SPARSH_EINVAL, "null handle");
@@ -1691,6 +1749,7 @@ int sparsh_bench_op(sparsh_handle h, int op, int level, int reps, double *avg_se
     (void)hipMemcpy(y.p, ones.data(), n * 8, hipMemcpyHostToDevice);
     (void)hipMemcpy(c.p, ones.data(), nc * 8, hipMemcpyHostToDevice);
     hipStream_t st = E.stream();
+    std::unique_ptr<DBuf> ns_part;  // op 18: the partial sums of launch_sum
     auto run = [&]() {
         switch (op) {
         case 0: E.op_spmv(level, x.p, y.p); break;
@@ -1747,13 +1806,23 @@ int sparsh_bench_op(sparsh_handle h, int op, int level, int reps, double *avg_se
             launch_box1(L.A, 1, a, L.fine, st);
         } break;
         case 17: E.cheby_bench_step(level); break;
+        case 18: {  // one projection with the dot (launch_sum + launch_project) on level 0's resident x and r
+            int nb = 0;
+            E.project_any(L.n, L.x, L.r, ns_part->p, E.partials(), &nb);
+        } break;
         case 13: E.gmres_bench_step(true); break;
         case 14: E.gmres_bench_step(false); break;
         case 15: E.gmres_bench_step(true); break;  // (the handle's float basis)
         default: break;
         }
     };
-    if (op < 0 || op > 17) return fail(SPARSH_EINVAL, "unknown op");
+    if (op < 0 || op > 18) return fail(SPARSH_EINVAL, "unknown op");
+    if (op == 18) {
+        if (level != 0 || E.distributed()) return fail(SPARSH_EINVAL, "the projection runs on level 0 of a single-GPU handle");
+        ns_part.reset(new DBuf(E, (size_t)ns_grid(L.n)));
+        if (!ns_part->p) return fail(SPARSH_ENODEV, E.error);
+        launch_fill(L.n, 1.0, L.x, st);
+    }
     if (op == 17 && (E.distributed() || !E.build_cheby_level(level))) return fail(SPARSH_ESTATE, "no Chebyshev bounds on this handle");
     if (op == 13 || op == 14 || op == 15) {
         if (level != 0 || E.distributed()) return fail(SPARSH_EINVAL, "the GMRES orthogonalisation step runs on level 0 of a single-GPU handle");
@@ -1766,7 +1835,7 @@ int sparsh_bench_op(sparsh_handle h, int op, int level, int reps, double *avg_se
     if (op == 16 && (E.distributed() || !box1_applies(L.A, E.kernel_cfg()))) return fail(SPARSH_ESTATE, "the level does not run the plane-marching kernel (sparsh_level_marching_ops)");
     // (the ops on the level's own buffers, 10, 11 and 16: ones as the right-hand side, as in Engine::tune_box_kernels -- on zeros every quotient
     // of div_const takes the plain-division branch)
-    if (op == 10 || op == 11 || op == 16 || op == 17) launch_fill(L.n, 1.0, L.r, st);
+    if (op == 10 || op == 11 || op == 16 || op == 17 || op == 18) launch_fill(L.n, 1.0, L.r, st);
     for (int i = 0; i < 3; ++i) run();
     hipEvent_t e0, e1;
     (void)hipEventCreate(&e0);
@@ -1779,7 +1848,7 @@ int sparsh_bench_op(sparsh_handle h, int op, int level, int reps, double *avg_se
     (void)hipEventElapsedTime(&ms, e0, e1);
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
-    if (op == 10 || op == 11 || op == 16 || op == 17) {
+    if (op == 10 || op == 11 || op == 16 || op == 17 || op == 18) {
         (void)hipMemsetAsync(L.x, 0, n * 8, st);
         (void)hipMemsetAsync(L.x2, 0, n * 8, st);
         (void)hipMemsetAsync(L.r, 0, n * 8, st);

@@ -490,6 +490,52 @@ int partial_count(const DevCsr &D) { return std::max(std::max(D.nblk, D.box1.wor
 
 }  // namespace
 
+// A setup under SPARSH_NULLSPACE_CONSTANT: what it refuses, and the defects of level 0 (A 1 = 0 and 1^T A = 0 up to rounding)
+int Engine::nullspace_check(const sparsh_params &p, bool with_defects)
+{
+    if (with_defects) ns_row_defect_ = ns_col_defect_ = 0.0;
+    if (ns_kind_ != SPARSH_NULLSPACE_CONSTANT) return SPARSH_OK;
+    if (p.coarsening == 1) {
+        error = "SPARSH_NULLSPACE_CONSTANT: Beck coarsening is not available with a null space (its interpolation does not reproduce constants exactly); use HEM";
+        return SPARSH_EINVAL;
+    }
+    if (p.precond_fp32) {
+        error = "SPARSH_NULLSPACE_CONSTANT: params.precond_fp32 is not available with a null space";
+        return SPARSH_EINVAL;
+    }
+    if (dist_ || (comm_ && comm_->size > 1)) {
+        error = "SPARSH_NULLSPACE_CONSTANT: a null space is not available on a handle with a multi-rank transport";
+        return SPARSH_EINVAL;
+    }
+    if (!with_defects) return SPARSH_OK;
+    nullspace_defects(A0_, ns_row_defect_, ns_col_defect_);
+    constexpr double kDefectMax = 1e-12;  // an assembled row carries a few 1e-15 of rounding; any real boundary term is orders above
+    char buf[64];
+    if (!(ns_row_defect_ <= kDefectMax)) {
+        std::snprintf(buf, sizeof buf, "%.3e", ns_row_defect_);
+        error = std::string("SPARSH_NULLSPACE_CONSTANT: the constant vector is not in the null space of A: row defect max_i |sum_j a_ij| / sum_j |a_ij| = ") + buf + " > 1e-12";
+        return SPARSH_EINVAL;
+    }
+    if (!(ns_col_defect_ <= kDefectMax)) {
+        std::snprintf(buf, sizeof buf, "%.3e", ns_col_defect_);
+        error = std::string("SPARSH_NULLSPACE_CONSTANT: the constant vector is not in the null space of A^T: column defect max_j |sum_i a_ij| / sum_i |a_ij| = ") + buf + " > 1e-12";
+        return SPARSH_EINVAL;
+    }
+    return SPARSH_OK;
+}
+
+const HostCsr &Engine::coarse_operator()
+{
+    const HostCsr &AL = H_.levels.back().A;
+    if (H_.pinned_row < 0) return AL;
+    if (!pinned_valid_) {
+        pinned_AL_ = pinned_operator(AL, H_.pinned_row);
+        pinned_AL_.adopt();
+        pinned_valid_ = true;
+    }
+    return pinned_AL_;
+}
+
 int Engine::setup_host(const sparsh_params &p)
 {
     prm_ = p;
@@ -497,6 +543,8 @@ int Engine::setup_host(const sparsh_params &p)
     adopt_sweeps();
     ready_ = false;
     host_ready_ = false;
+    pinned_valid_ = false;
+    if (int rc = nullspace_check(p, true); rc != SPARSH_OK) return rc;
     colors_.clear();
     sor_.clear();
     cheb_.clear();
@@ -512,6 +560,7 @@ int Engine::setup_host(const sparsh_params &p)
     if (coarse_.form() == 1) sp.coarse_factor_bytes = 0;  // the estimate is the nested-dissection solver's
     sp.host_threads = p.host_threads;
     sp.print = p.print_setup != 0;
+    sp.nullspace = ns_kind_;
     if (!build_hierarchy(A0_, sp, H_)) {
         error = H_.error;
         return SPARSH_ENUMERIC;
@@ -523,7 +572,7 @@ int Engine::setup_host(const sparsh_params &p)
         // coarsening rule instead of failing: coarse_limit = dense_limit, the behaviour before the reference policy became the default.
         const double tp = omp_get_wtime();
         std::string perr;
-        if (!coarse_.probe(H_.levels.back().A, perr)) {
+        if (!coarse_.probe(coarse_operator(), perr)) {
             if (sp.print) std::printf("note: %s -- extending the hierarchy instead\n", perr.c_str());
             SetupParams sp2 = sp;
             sp2.coarse_limit = sp.dense_limit;
@@ -535,7 +584,8 @@ int Engine::setup_host(const sparsh_params &p)
                 return SPARSH_ENUMERIC;
             }
             H_.seconds += before;
-            if (!H_.coarse_dense && !coarse_.probe(H_.levels.back().A, perr)) {
+            pinned_valid_ = false;
+            if (!H_.coarse_dense && !coarse_.probe(coarse_operator(), perr)) {
                 error = perr;
                 return SPARSH_EINVAL;
             }
@@ -1183,6 +1233,7 @@ int Engine::setup(const sparsh_params &p)
     prm_ = p;
     ready_ = false;
     fault_ = SPARSH_OK;
+    if (int rc = nullspace_check(p, false); rc != SPARSH_OK) return rc;  // (the defects follow in setup_host; what no setup can make valid is a bad argument, device or not)
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
         error = "no HIP device visible: the MI355X HIP path is the only compute path (no CPU fallback)";
@@ -1206,6 +1257,7 @@ int Engine::setup(const sparsh_params &p)
     wk_.clear();    // (so are the extra vectors of the W- and K-cycles)
     kc_part_ = kc_scal_ = nullptr;
     wk_bytes_ = 0;
+    ns_part_ = ns_b_ = nullptr;
     coarse_.release();
     if (!comm_) comm_ = make_self_comm();
     const int G = comm_->size, me = comm_->rank;
@@ -1417,7 +1469,8 @@ int Engine::setup(const sparsh_params &p)
         // factorisation on the device
         const double t_f = omp_get_wtime();
         int why = 0;
-        const bool okc = coarse_.form() == 1 ? coarse_.setup_bt(H_.levels.back().A, st_, error, &why) : coarse_.setup_nd(H_.levels.back().A, st_, error, &why);
+        const HostCsr &AL = coarse_operator();  // (the pinned operator under a constant null space)
+        const bool okc = coarse_.form() == 1 ? coarse_.setup_bt(AL, st_, error, &why) : coarse_.setup_nd(AL, st_, error, &why);
         if (!okc) return why == 1 ? SPARSH_EINVAL : (why == 2 ? SPARSH_ENUMERIC : SPARSH_ENODEV);
         setup_seconds += omp_get_wtime() - t_f;
         if (p.print_setup && (G == 1 || me == 0)) {
@@ -1453,6 +1506,12 @@ int Engine::setup(const sparsh_params &p)
         if (!w) return SPARSH_ENODEV;
         if (!check(hipMemsetAsync(w, 0, wcap * 8, st_), "hipMemsetAsync")) return SPARSH_ENODEV;
         work_.push_back(w);
+    }
+    if (ns_on()) {  // the projection's partial sums and the projected right-hand side of a solve
+        ns_part_ = static_cast<double *>(dalloc((size_t)ns_grid(lev_[0].n) * 8));
+        ns_b_ = static_cast<double *>(dalloc(wcap * 8));
+        if (!ns_part_ || !ns_b_) return SPARSH_ENODEV;
+        if (!check(hipMemsetAsync(ns_b_, 0, wcap * 8, st_), "hipMemsetAsync")) return SPARSH_ENODEV;
     }
     place_tried = 0;
     place_best_us = place_worst_us = place_first_us = 0.0;
@@ -2564,7 +2623,10 @@ int Engine::amg_solve_dev(const double *b, double *x, int iterations, double *hi
     DevLevel &L0 = lev_[0];
     const int n = L0.n;
     HIPCHK(hipMemcpyAsync(L0.x, x, (size_t)n * 8, hipMemcpyDeviceToDevice, st_));
-    if (place_tried > 0 && !dist_ && !L0.deep && !ks_.active) {  // (an open Krylov session owns work_[0])
+    if (ns_on()) {  // constant null space: the cycles run on b - mean(b) from x - mean(x)
+        b = ns_rhs(b);
+        project(L0.x);
+    } else if (place_tried > 0 && !dist_ && !L0.deep && !ks_.active) {  // (an open Krylov session owns work_[0])
         // the setup chose the buffers of iterate, twin and right-hand side together (tune_placement): run the cycles on the
         // engine's copy of b instead of on a caller buffer placed wherever it happens to be (one 8n-byte copy per solve)
         HIPCHK(hipMemcpyAsync(work_[0], b, (size_t)n * 8, hipMemcpyDeviceToDevice, st_));
@@ -2595,6 +2657,7 @@ int Engine::amg_solve_dev(const double *b, double *x, int iterations, double *hi
             }
         }
     }
+    if (ns_on()) project(lev_[0].x);  // (the Jacobi legs move the mean)
     HIPCHK(hipMemcpyAsync(x, lev_[0].x, (size_t)n * 8, hipMemcpyDeviceToDevice, st_));
     HIPCHK(hipStreamSynchronize(st_));
     if (ncycles) *ncycles = cycles;
@@ -2608,8 +2671,52 @@ const double *Engine::precondition(const double *r, double *scratch, double *dot
         vcycle_f32(r, scratch, dot_partial ? dot_partial : part0_, dot_partial ? dot_nblk : &nb);
         return scratch;
     }
+    if (ns_on()) {
+        // constant null space: z = P V(r), P = I - 1 1^T / n.  The cycle runs without its fused z.r; the projection launch leaves
+        // the partial sums of (P z).r where the caller expects them
+        vcycle(r, true, nullptr, nullptr, zero_done0);
+        project(lev_[0].x, dot_partial ? r : nullptr, dot_partial, dot_nblk);
+        return lev_[0].x;
+    }
     vcycle(r, true, dot_partial, dot_nblk, zero_done0);  // z = 0 ; z = V(r), zero initial guess
     return lev_[0].x;
+}
+
+void Engine::project_any(int n, double *v, const double *r, double *part, double *dot_partial, int *dot_nblk)
+{
+    int nb = 0;
+    launch_sum(n, v, part, &nb, st_);
+    launch_project(n, part, nb, v, r, dot_partial, scal_ + S_MEAN, st_);
+    if (r && dot_nblk) *dot_nblk = ns_grid(n);
+}
+
+void Engine::project(double *v, const double *r, double *dot_partial, int *dot_nblk) { project_any(lev_[0].n, v, r, ns_part_, dot_partial, dot_nblk); }
+
+int Engine::op_project(int n, double *v, const double *r, double *mean, double *dot)
+{
+    const size_t g = (size_t)ns_grid(n);
+    double *part = static_cast<double *>(dalloc(g * 8)), *dpart = r ? static_cast<double *>(dalloc(g * 8)) : nullptr;
+    if (!part || (r && !dpart)) {
+        dfree(part);
+        dfree(dpart);
+        return SPARSH_ENODEV;
+    }
+    int nb = 0;
+    project_any(n, v, r, part, dpart, &nb);
+    if (r) finalize(FIN_STORE, dpart, nullptr, nb, S_TMP, nullptr, 0);
+    const double m = read_scalar(S_MEAN);  // (synchronises the stream)
+    if (mean) *mean = m;
+    if (r && dot) *dot = read_scalar(S_TMP);
+    dfree(part);
+    dfree(dpart);
+    return fault_;
+}
+
+const double *Engine::ns_rhs(const double *b)
+{
+    HIPCHK(hipMemcpyAsync(ns_b_, b, (size_t)lev_[0].n * 8, hipMemcpyDeviceToDevice, st_));
+    project(ns_b_);
+    return ns_b_;
 }
 
 // Solver_CG_1 (precond = false) / Solver_PCG_1 (precond = true), split into the part before
@@ -2636,6 +2743,10 @@ int Engine::pcg_init(const double *b, double *x, bool precond)
     int nb = 0;
     ks_ = KrylovState();
     ks_.precond = precond;
+    if (ns_on()) {  // constant null space: the loop reads the projected copy of b and starts from x - mean(x)
+        b = ns_rhs(b);
+        project(x);
+    }
     ks_.b = b;
     ks_.x = x;
     const double *xin = x;
@@ -2745,7 +2856,8 @@ int Engine::pcg_steps(int nsteps, int *done)
     const int check_every = std::max(1, prm_.check_every);
     // hipGraph replay: single GPU, no per-launch profiling events
     // (the W-cycle launches eagerly: its WK levels exchange their buffers from one inner cycle to the next)
-    bool use_graph = prm_.use_graph && !dist_ && !prof.enabled && (int)lev_.size() > 1 && (!precond || cycle_kind_ == SPARSH_CYCLE_V);
+    // (under a constant null space use_graph is accepted and ignored)
+    bool use_graph = prm_.use_graph && !dist_ && !prof.enabled && (int)lev_.size() > 1 && (!precond || cycle_kind_ == SPARSH_CYCLE_V) && !ns_on();
     if (use_graph && !(graph_.exec && graph_.x == ks_.x && graph_.precond == precond)) use_graph = capture_graph(precond);
     if (use_graph) HIPCHK(hipMemcpyAsync(iter_ctr_, &ks_.count, sizeof(int), hipMemcpyHostToDevice, st_));
     while (ks_.count < lev_[0].nglob && ks_.r1 > prm_.tol && did < nsteps && fault_ == SPARSH_OK) {
@@ -2764,6 +2876,10 @@ int Engine::pcg_steps(int nsteps, int *done)
                 break;
             }
         }
+    }
+    if (ns_on()) {
+        project(ks_.x);  // rounding drift of the mean
+        HIPCHK(hipStreamSynchronize(st_));  // the call returns with the stream idle, as it does without a null space
     }
     if (done) *done = did;
     return fault_ != SPARSH_OK ? fault_ : rc;
@@ -2801,6 +2917,10 @@ int Engine::bicg(const double *b, double *x, int max_iters, double *hist, int hi
     const int n = lev_[0].n;
     double *r0 = work_[0], *r = work_[1], *p = work_[2], *Ap = work_[3], *s = work_[4], *As = work_[5], *p1buf = work_[6];
     int nb = 0;
+    if (ns_on()) {
+        b = ns_rhs(b);
+        project(x);
+    }
     const double *xin = x;
     if (dist_) {
         launch_copy(n, x, work_[7], st_);
@@ -2850,6 +2970,7 @@ int Engine::bicg(const double *b, double *x, int max_iters, double *hist, int hi
             }
         }
     }
+    if (ns_on()) project(x);
     HIPCHK(hipStreamSynchronize(st_));
     if (hist) {
         const int m = std::min(std::min(count, hist_cap), hist_cap_dev_);
@@ -2876,6 +2997,10 @@ int Engine::fcg(const double *b, double *x, int max_iters, double *hist, int his
     const int n = lev_[0].n;
     double *r = work_[0], *p = work_[1], *Ap = work_[2];
     int nb = 0;
+    if (ns_on()) {
+        b = ns_rhs(b);
+        project(x);
+    }
     op_residual(0, b, x, r);  // r0 = b - A x
     launch_dot(n, r, r, part0_, &nb, st_);
     finalize(FIN_SQRT, part0_, nullptr, nb, S_RES, nullptr, 0);
@@ -2918,6 +3043,7 @@ int Engine::fcg(const double *b, double *x, int max_iters, double *hist, int his
             }
         }
     }
+    if (ns_on()) project(x);
     HIPCHK(hipStreamSynchronize(st_));
     if (hist) {
         const int m = std::min(std::min(count, hist_cap), hist_cap_dev_);
@@ -3077,6 +3203,10 @@ int Engine::gmres(const double *b, double *x, int max_iters, double *hist, int h
     double *u = work_[0], *z32 = work_[4];
     double *feed = work_[2];  // float basis: v_j as stored, widened to double
     int nb = 0, it = 0, rc = SPARSH_OK;
+    if (ns_on()) {
+        b = ns_rhs(b);
+        project(x);
+    }
     // z = M v (nullptr: the identity); the fp64 cycle leaves z in lev_[0].x, which belongs to the cycle: consumed by the next launch
     auto apply_M = [&](const double *v) { return precond ? precondition(v, z32) : v; };
     // The only exit with SPARSH_OK is the true residual of a cycle start being <= tol.  |g_{j+1}| <= tol only ends the cycle, which
@@ -3125,6 +3255,7 @@ int Engine::gmres(const double *b, double *x, int max_iters, double *hist, int h
         else launch_gs_update(n, gm_stride_, gm_basis_, steps, gm_.ny, nullptr, u, nullptr, nullptr, st_);
         launch_axpby(n, 1.0, apply_M(u), 1.0, x, st_);
     }
+    if (ns_on()) project(x);
     HIPCHK(hipStreamSynchronize(st_));
     if (hist) {
         const int cnt = std::min(std::min(it, hist_cap), hist_cap_dev_);

@@ -189,6 +189,22 @@ public:
     long cycle_visits() const { return cycle_visits_for(cycle_stride_); }
     int wk_level_count() const;
     size_t wk_bytes() const { return wk_bytes_; }
+    // ---- constant null space (SPARSH_NULLSPACE_CONSTANT).  The kind asked for is read by the next setup; the
+    // hierarchy remembers the kind it was built with (H_.nullspace), and only that one steers the solve path
+    void set_nullspace(int kind) { ns_kind_ = kind; }
+    int nullspace_built() const { return host_ready_ ? H_.nullspace : SPARSH_NULLSPACE_NONE; }
+    bool ns_on() const { return nullspace_built() == SPARSH_NULLSPACE_CONSTANT; }
+    int pinned_row() const { return host_ready_ ? H_.pinned_row : -1; }
+    double row_defect() const { return host_ready_ ? ns_row_defect_ : 0.0; }
+    double col_defect() const { return host_ready_ ? ns_col_defect_ : 0.0; }
+    // v -= mean(v) on a level-0 vector through launch_sum + launch_project; r non-null: the partial sums of (v - mean) . r go to
+    // dot_partial and their number to *dot_nblk, for finalize.  The mean removed stays in scal_[S_MEAN].
+    void project(double *v, const double *r = nullptr, double *dot_partial = nullptr, int *dot_nblk = nullptr);
+    // the same two launches on any device vector of n elements (bench); part: ns_grid(n) doubles of scratch
+    void project_any(int n, double *v, const double *r, double *part, double *dot_partial, int *dot_nblk);
+    // test hook: the two launches on any 8-byte aligned device vector with scratch of its own; *mean = the mean removed and, with r,
+    // *dot = (v - mean) . r through the engine's final reduction (either pointer may be null); SPARSH_* code
+    int op_project(int n, double *v, const double *r, double *mean, double *dot);
     // whether `method` can run under the current cycle on this handle: SPARSH_OK, or SPARSH_EINVAL with the reason in error.  Needs no
     // device; the visit cap is checked once the hierarchy exists.  SPARSH_AMG stands for every caller that takes a preconditioner
     // which changes from one application to the next (the stand-alone iteration, op_precond)
@@ -438,6 +454,17 @@ private:
     long cycle_visits_for(int stride) const;
     bool kc_scratch();  // partial sums and scalar blocks of the K step (no-op once held)
     int fcg(const double *b, double *x, int max_iters, double *hist, int hist_cap, int *iters);
+    // refusals of a setup under SPARSH_NULLSPACE_CONSTANT and the two defects of level 0: SPARSH_OK or SPARSH_EINVAL with the reason
+    int nullspace_check(const sparsh_params &p, bool with_defects);
+    // the operator the coarsest-level solver factors: A_L, or A_L with the pinned row and column under a constant null space
+    const HostCsr &coarse_operator();
+    // the right-hand side of a solve under a constant null space: a projected copy in ns_b_ (the caller's b is never written)
+    const double *ns_rhs(const double *b);
+    int ns_kind_ = SPARSH_NULLSPACE_NONE;
+    double ns_row_defect_ = 0.0, ns_col_defect_ = 0.0;
+    HostCsr pinned_AL_;
+    bool pinned_valid_ = false;
+    double *ns_part_ = nullptr, *ns_b_ = nullptr;  // partial sums of launch_sum ; the projected right-hand side (both: CONSTANT only)
     int cycle_kind_ = SPARSH_CYCLE_V, cycle_stride_ = kCycleDefaultStride;
     std::vector<WkLevel> wk_;  // per level (empty until first use)
     double *kc_part_ = nullptr, *kc_scal_ = nullptr;  // kKcPartialDoubles ; kKcScalDoubles per level and one block more for op_kstep

@@ -583,6 +583,61 @@ bool sparse_inverse(const HostCsr &A, std::vector<double> &inv)
     return true;
 }
 
+void nullspace_defects(const HostCsr &A, double &row_defect, double &col_defect)
+{
+    const int n = A.nrow;
+    std::vector<double> csum((size_t)A.ncol, 0.0), cabs((size_t)A.ncol, 0.0);
+    row_defect = 0.0;
+    col_defect = 0.0;
+    for (int i = 0; i < n; ++i) {
+        double s = 0.0, a = 0.0;
+        for (int j = A.rowptr[i]; j < A.rowptr[i + 1]; ++j) {
+            const double v = A.val[j];
+            s += v;
+            a += std::fabs(v);
+            csum[A.col[j]] += v;
+            cabs[A.col[j]] += std::fabs(v);
+        }
+        if (a > 0.0) row_defect = std::max(row_defect, std::fabs(s) / a);
+        if (s != s) row_defect = s;  // a NaN entry fails every comparison: report it
+    }
+    for (int c = 0; c < A.ncol; ++c) {
+        if (cabs[c] > 0.0) col_defect = std::max(col_defect, std::fabs(csum[c]) / cabs[c]);
+        if (csum[c] != csum[c]) col_defect = csum[c];
+    }
+}
+
+HostCsr pinned_operator(const HostCsr &A, int row)
+{
+    HostCsr B;
+    B.nrow = A.nrow;
+    B.ncol = A.ncol;
+    B.rp_store.assign((size_t)A.nrow + 1, 0);
+    B.col_store.reserve((size_t)A.nnz() + 1);
+    B.val_store.reserve((size_t)A.nnz() + 1);
+    for (int i = 0; i < A.nrow; ++i) {
+        bool have_diag = false;
+        for (int j = A.rowptr[i]; j < A.rowptr[i + 1]; ++j) {
+            const int c = A.col[j];
+            if (i == row && !have_diag && c > row) {  // the row has no diagonal entry: insert it in column order
+                B.col_store.push_back(row);
+                B.val_store.push_back(1.0);
+                have_diag = true;
+            }
+            have_diag = have_diag || (i == row && c == row);
+            B.col_store.push_back(c);
+            B.val_store.push_back(i == row ? (c == row ? 1.0 : 0.0) : (c == row ? 0.0 : A.val[j]));
+        }
+        if (i == row && !have_diag) {
+            B.col_store.push_back(row);
+            B.val_store.push_back(1.0);
+        }
+        B.rp_store[(size_t)i + 1] = (int)B.col_store.size();
+    }
+    B.adopt();
+    return B;
+}
+
 bool build_hierarchy(const HostCsr &A0, const SetupParams &prm, HostHierarchy &H)
 {
     const double t0 = wall();
@@ -650,7 +705,9 @@ bool build_hierarchy(const HostCsr &A0, const SetupParams &prm, HostHierarchy &H
     // (block-tridiagonal form, coarse.cpp) when the hierarchy is uploaded
     H.coarse_dense = H.nL <= prm.dense_limit;
     H.coarse_inverse.clear();
-    if (H.coarse_dense && !sparse_inverse(AL, H.coarse_inverse)) {
+    H.nullspace = prm.nullspace;
+    H.pinned_row = prm.nullspace != 0 ? H.nL - 1 : -1;
+    if (H.coarse_dense && !(H.pinned_row >= 0 ? sparse_inverse(pinned_operator(AL, H.pinned_row), H.coarse_inverse) : sparse_inverse(AL, H.coarse_inverse))) {
         H.error = "coarsest-level matrix is singular";
         return false;
     }
@@ -734,7 +791,7 @@ void serialize_hierarchy(const HostHierarchy &H, std::vector<char> &out)
     w.u64(H.levels.size());
     w.u64((uint64_t)H.nL);
     w.u64(H.coarse_dense ? 1 : 0);
-    w.u64(H.extended ? 1 : 0);
+    w.u64((H.extended ? 1 : 0) | ((uint64_t)(H.nullspace & 0xff) << 8));  // (without a null space: the word it always was)
     for (size_t l = 0; l < H.levels.size(); ++l) {
         const HostLevel &L = H.levels[l];
         if (l > 0) w.csr(L.A);
@@ -757,8 +814,11 @@ bool deserialize_hierarchy(const char *buf, size_t bytes, const HostCsr &A0, Hos
     const uint64_t nl = r.u64();
     H.nL = (int)r.u64();
     H.coarse_dense = r.u64() != 0;
-    H.extended = r.u64() != 0;
-    if (!r.ok || nl == 0 || nl > 64) {
+    const uint64_t flags = r.u64();
+    H.extended = (flags & 1) != 0;
+    H.nullspace = (int)((flags >> 8) & 0xff);
+    H.pinned_row = H.nullspace != 0 ? H.nL - 1 : -1;
+    if (!r.ok || nl == 0 || nl > 64 || (flags & ~(uint64_t)0xff01) != 0 || H.nullspace > 1) {
         H.error = "hierarchy image: bad header";
         return false;
     }

@@ -59,6 +59,7 @@ struct SetupParams {
                                                    // nested-dissection factors stay below this (0: coarse_limit alone decides)
     int host_threads = 0;
     bool print = true;
+    int nullspace = 0;  // SPARSH_NULLSPACE_*: under CONSTANT the coarsest-level solver gets the pinned operator (pinned_operator)
 };
 
 struct HostLevel {
@@ -78,6 +79,10 @@ struct HostHierarchy {
     std::vector<double> coarse_inverse;
     double seconds = 0.0;
     bool extended = false;  // hierarchy continued past max_levels because of coarse_limit
+    // null space the hierarchy was built for (SPARSH_NULLSPACE_*) and, under CONSTANT, the row of the coarsest operator that every
+    // form of the coarsest-level solver sees replaced by the unit row and column (-1: none); levels.back().A itself stays untouched
+    int nullspace = 0;
+    int pinned_row = -1;
     std::string error;
 };
 
@@ -93,6 +98,14 @@ std::vector<double> extract_diagonal(const HostCsr &A);
 std::vector<int> rcm_order(const HostCsr &A);
 // dense inverse of a sparse matrix through RCM + banded LU (partial pivoting); false if singular
 bool sparse_inverse(const HostCsr &A, std::vector<double> &inv);
+
+// Constant null space (A 1 = 0 and 1^T A = 0): row_defect = max_i |sum_j a_ij| / sum_j |a_ij|, col_defect the same over the
+// columns (rows / columns without entries count as 0)
+void nullspace_defects(const HostCsr &A, double &row_defect, double &col_defect);
+// A with row and column `row` replaced by the unit row and column: the nonsingular operator the coarsest-level solver factors
+// for a matrix whose null space is the constant vector.  The pattern is kept (the replaced entries are stored zeros; the diagonal
+// entry is inserted where the row has none), so orderings and dissections see the graph of A.
+HostCsr pinned_operator(const HostCsr &A, int row);
 
 // Colour classes of the multicolour SOR smoother: greedy first-fit over the rows in ascending order on the pattern of
 // A + A^T without the diagonal (no two rows of one colour refer to each other, also for an unsymmetric pattern).  Colours are

@@ -269,6 +269,15 @@ void launch_axpby(int n, double a, const double *x, double b, double *y, hipStre
 // partial sums of x.y (nblocks returned through *nblk)
 void launch_dot(int n, const double *x, const double *y, double *partial, int *nblk, hipStream_t st);
 
+// ---- projection onto mean zero (nullspace_kernels.hip; constant null space): two launches, no host read, no atomics.  x may be any
+// 8-byte aligned device pointer.  launch_sum: one partial sum of x per workgroup, *nblk = ns_grid(n) of them (at most 2048).
+// launch_project: every workgroup adds the nblk partials in one fixed order, m = S / n, x_i = x_i - m; r non-null: dot_partial gets
+// ns_grid(n) partial sums of (x_i - m) * r_i (r any 8-byte aligned pointer); workgroup 0 writes m to *mean_slot.
+int ns_grid(int n);
+void launch_sum(int n, const double *x, double *partial, int *nblk, hipStream_t st);
+void launch_project(int n, const double *partial, int nblk, double *x, const double *r, double *dot_partial, double *mean_slot,
+                    hipStream_t st);
+
 // ---- fp32 preconditioner hierarchy (opt-in; SURVEY §8f-4 "mixed precision"): the V-cycle runs on a
 // float copy of the sliced-diagonal layout with float vectors, the Krylov loop stays fp64.
 struct SdiaF32 {
@@ -296,7 +305,9 @@ void launch_cvt_f2d_dot(int n, const float *z32, const double *r64, double *z64,
 // device-resident scalar slots used by the Krylov loops
 enum Slot : int {
     S_RZ = 0, S_PAP, S_ALPHA, S_NALPHA, S_BETA, S_RR, S_RES, S_ZR,
-    S_ALPHA1, S_APR0, S_ASS, S_ASAS, S_OMEGA1, S_RR0, S_TMP, S_SUM0, S_SUM1, S_COUNT
+    S_ALPHA1, S_APR0, S_ASS, S_ASAS, S_OMEGA1, S_RR0, S_TMP, S_SUM0, S_SUM1,
+    S_MEAN,  // the mean the last projection removed (nullspace_kernels.hip)
+    S_COUNT
 };
 
 // finalize codes: reduce partial arrays, then one thread updates the scalar slots

@@ -52,6 +52,15 @@ def poisson3d(n: int, ny: int | None = None, nz: int | None = None):
     return _stencil_csr((n, ny or n, nz or n), 6.0)
 
 
+def poisson3d_neumann(nx: int, ny: int | None = None, nz: int | None = None):
+    """7-pt Laplacian with Neumann conditions on every face of an nx x ny x nz grid: off-diagonal entries -1, the diagonal the
+    number of neighbours.  Singular: the constant vector spans the null space (``set_nullspace("constant")``)."""
+    rp, ci, v = _stencil_csr((nx, ny or nx, nz or nx), 0.0)
+    rows = np.repeat(np.arange(len(rp) - 1), np.diff(rp))
+    v[ci == rows] = (np.diff(rp) - 1).astype(np.float64)
+    return rp, ci, v
+
+
 def _morton_order(pts):
     """Z-order (Morton) rank of 2D points in the unit square, 16 bits per axis."""
     q = np.minimum((pts * 65536.0).astype(np.uint64), 65535)
