@@ -312,7 +312,8 @@ int sparsh_setup_host(sparsh_handle h, const sparsh_params *p);
 /* hierarchy inspection (tests; "Level k:\t nrow" lines of src/AMG_phases.cpp:55-58) */
 int sparsh_num_levels(sparsh_handle h);
 int sparsh_level_info(sparsh_handle h, int level, int *nrow, int *nnz, int *p_ncol, int *p_nnz);
-/* which: 0 = A_level, 1 = P_level (level < last).  Buffers sized from sparsh_level_info. */
+/* which: 0 = A_level, 1 = P_level, 2 = R_level = P_level^T as the restriction kernels read it (rows = coarse rows, entries in ascending
+ * fine-row order); 1 and 2 on level < last.  Buffers sized from sparsh_level_info (R: p_ncol rows, p_nnz entries). */
 int sparsh_level_csr(sparsh_handle h, int level, int which, int *rowptr, int *colindex, double *val);
 /* explicit inverse of the coarsest operator, row-major nL x nL (what the device GEMV applies in
  * place of Direct_Solver_Pardiso_solve); available after sparsh_setup_host when the coarsest level
@@ -416,6 +417,27 @@ int sparsh_op_coarse(sparsh_handle h, const double *b, double *x);
 /* z = V32(r): one application of the opt-in fp32 preconditioner (params.precond_fp32 = 1): a V(nu,nu) cycle from a
  * zero guess on the float copy of the hierarchy, fp64 in/out.  Checked against oracle_vcycle_f32. */
 int sparsh_op_precond_f32(sparsh_handle h, const double *r, double *z);
+/* The steps sparsh_op_precond_f32's cycle is made of, one at a time (the cycle itself calls the same engine functions): float vectors in
+ * and out, nothing converted on the way.  Every call needs params.precond_fp32 = 1 and at least two levels (else SPARSH_ESTATE with the
+ * message of sparsh_op_precond_f32, also on a host-only handle); `level` is a level below the coarsest (SPARSH_EINVAL for a level out
+ * of range and for the coarsest one, which has no float operator).
+ *   sparsh_level_f32_layout: *layout = 1 the level's float operator is the sliced-diagonal mirror, 2 float CSR values, 0 none (coarsest)
+ *   sparsh_op_jacobi_f32:    `sweeps` sweeps x <- x + (w (b - A x)) / d, w = (float)omega; x_is_zero: the first is x = (w b) / d
+ *   sparsh_op_residual_f32:  r = b - A_level x
+ *   sparsh_op_restrict_f32:  bc = R_level r, the products (float)R_ij * r_j added in R's stored order (sparsh_level_csr, which = 2)
+ *   sparsh_op_prolong_f32:   xf <- P_level xc + xf (one gathered entry per row under aggregation)
+ *   sparsh_op_coarse_f32:    x = the coarsest-level solve of b: the float copy of the dense inverse applied by one wavefront per row,
+ *                            or b widened, the fp64 factors, the solution rounded to float
+ *   sparsh_op_cvt_f32:       out[i] = (float)in[i] (round to nearest even), any n > 0
+ *   sparsh_op_cvt_f2d_dot:   z[i] = (double)z32[i] and *dot = sum z[i] r[i], any n > 0 */
+int sparsh_level_f32_layout(sparsh_handle h, int level, int *layout);
+int sparsh_op_jacobi_f32(sparsh_handle h, int level, const float *b, float *x, int sweeps, int x_is_zero);
+int sparsh_op_residual_f32(sparsh_handle h, int level, const float *b, const float *x, float *r);
+int sparsh_op_restrict_f32(sparsh_handle h, int level, const float *r, float *bc);
+int sparsh_op_prolong_f32(sparsh_handle h, int level, const float *xc, float *xf);
+int sparsh_op_coarse_f32(sparsh_handle h, const float *b, float *x);
+int sparsh_op_cvt_f32(sparsh_handle h, long n, const double *in, float *out);
+int sparsh_op_cvt_f2d_dot(sparsh_handle h, int n, const float *z32, const double *r, double *z, double *dot);
 /* z = M r exactly as the Krylov loops (SPARSH_PBICG, SPARSH_PGMRES) apply it: the V-cycle of the current smoother from a zero
  * guess with the launches a zero start takes, or the fp32 cycle under params.precond_fp32 */
 int sparsh_op_precond(sparsh_handle h, const double *r, double *z);

@@ -51,6 +51,7 @@ def _method(method):
 
 c_int_p = C.POINTER(C.c_int)
 c_dbl_p = C.POINTER(C.c_double)
+c_flt_p = C.POINTER(C.c_float)
 
 
 class SparshError(RuntimeError):
@@ -150,6 +151,14 @@ def _load():
         "sparsh_level_csr": (C.c_int, [H, C.c_int, C.c_int, c_int_p, c_int_p, c_dbl_p]),
         "sparsh_coarse_inverse": (C.c_int, [H, c_dbl_p]),
         "sparsh_op_precond_f32": (C.c_int, [H, c_dbl_p, c_dbl_p]),
+        "sparsh_level_f32_layout": (C.c_int, [H, C.c_int, c_int_p]),
+        "sparsh_op_jacobi_f32": (C.c_int, [H, C.c_int, c_flt_p, c_flt_p, C.c_int, C.c_int]),
+        "sparsh_op_residual_f32": (C.c_int, [H, C.c_int, c_flt_p, c_flt_p, c_flt_p]),
+        "sparsh_op_restrict_f32": (C.c_int, [H, C.c_int, c_flt_p, c_flt_p]),
+        "sparsh_op_prolong_f32": (C.c_int, [H, C.c_int, c_flt_p, c_flt_p]),
+        "sparsh_op_coarse_f32": (C.c_int, [H, c_flt_p, c_flt_p]),
+        "sparsh_op_cvt_f32": (C.c_int, [H, C.c_long, c_dbl_p, c_flt_p]),
+        "sparsh_op_cvt_f2d_dot": (C.c_int, [H, C.c_int, c_flt_p, c_dbl_p, c_dbl_p, c_dbl_p]),
         "sparsh_coarse_info": (C.c_int, [H, c_int_p, C.POINTER(C.c_long)]),
         "sparsh_coarse_window": (C.c_int, [H, c_int_p]),
         "sparsh_set_coarse_interface": (C.c_int, [H, C.c_int]),
@@ -268,6 +277,19 @@ def _dp(a):
 
 def _ip(a):
     return a.ctypes.data_as(c_int_p)
+
+
+def _fp(a):
+    return a.ctypes.data_as(c_flt_p)
+
+
+def _f32(a, copy=False):
+    """A float32 vector as the float entry points take it.  Other dtypes are refused, not converted: a hidden rounding of a float64
+    argument is what these entry points exist to rule out."""
+    a = np.asarray(a)
+    if a.dtype != np.float32:
+        raise TypeError(f"the fp32 entry points take float32 arrays, not {a.dtype}")
+    return np.array(a, dtype=np.float32) if copy else np.ascontiguousarray(a)
 
 
 def _check(rc, allow=()):
@@ -768,14 +790,15 @@ class sp_matrix_mg:
         return sl.value, vb.value, mb.value
 
     def level_csr(self, level, which="A"):
+        """(rowptr, colindex, val, ncol) of A, of P or of R = P^T in its stored order (the order the restriction adds in)."""
         info = self.level_info(level)
-        nrow = info["nrow"]
+        nrow = info["p_ncol"] if which == "R" else info["nrow"]
         nnz = info["nnz"] if which == "A" else info["p_nnz"]
         rp = np.zeros(nrow + 1, dtype=np.int32)
         ci = np.zeros(max(nnz, 1), dtype=np.int32)
         v = np.zeros(max(nnz, 1), dtype=np.float64)
-        _check(lib.sparsh_level_csr(self._h, level, 0 if which == "A" else 1, _ip(rp), _ip(ci), _dp(v)))
-        ncol = nrow if which == "A" else info["p_ncol"]
+        _check(lib.sparsh_level_csr(self._h, level, {"A": 0, "P": 1, "R": 2}[which], _ip(rp), _ip(ci), _dp(v)))
+        ncol = {"A": info["nrow"], "P": info["p_ncol"], "R": info["nrow"]}[which]
         return rp, ci[:nnz], v[:nnz], ncol
 
     def level_scipy(self, level, which="A"):
@@ -1121,6 +1144,59 @@ class sp_matrix_mg:
         z = np.zeros_like(r)
         _check(lib.sparsh_op_precond_f32(self._h, _dp(r), _dp(z)))
         return z
+
+    # -- the steps of the fp32 cycle one at a time: float32 arrays in and out (needs precond_fp32=1 and two levels) ----------------
+    def level_f32_layout(self, level):
+        """"sdia" (float sliced-diagonal mirror), "csr" (float CSR values) or None (the coarsest level: no float operator)."""
+        k = C.c_int()
+        _check(lib.sparsh_level_f32_layout(self._h, int(level), C.byref(k)))
+        return {0: None, 1: "sdia", 2: "csr"}[k.value]
+
+    def op_jacobi_f32(self, level, b, x, sweeps, x_is_zero=False):
+        b, x = _f32(b), _f32(x, copy=True)
+        _check(lib.sparsh_op_jacobi_f32(self._h, int(level), _fp(b), _fp(x), int(sweeps), 1 if x_is_zero else 0))
+        return x
+
+    def op_residual_f32(self, level, b, x):
+        b, x = _f32(b), _f32(x)
+        r = np.zeros_like(b)
+        _check(lib.sparsh_op_residual_f32(self._h, int(level), _fp(b), _fp(x), _fp(r)))
+        return r
+
+    def op_restrict_f32(self, level, r):
+        r = _f32(r)
+        bc = np.zeros(self.level_info(level)["p_ncol"], dtype=np.float32)
+        _check(lib.sparsh_op_restrict_f32(self._h, int(level), _fp(r), _fp(bc)))
+        return bc
+
+    def op_prolong_f32(self, level, xc, xf):
+        xc, xf = _f32(xc), _f32(xf, copy=True)
+        _check(lib.sparsh_op_prolong_f32(self._h, int(level), _fp(xc), _fp(xf)))
+        return xf
+
+    def op_coarse_f32(self, b):
+        b = _f32(b)
+        x = np.zeros_like(b)
+        _check(lib.sparsh_op_coarse_f32(self._h, _fp(b), _fp(x)))
+        return x
+
+    def op_cvt_f32(self, x64):
+        """(float)x element by element, on the device."""
+        x64 = np.ascontiguousarray(x64, dtype=np.float64)
+        out = np.zeros(len(x64), dtype=np.float32)
+        _check(lib.sparsh_op_cvt_f32(self._h, len(x64), _dp(x64), _fp(out)))
+        return out
+
+    def op_cvt_f2d_dot(self, z32, r64):
+        """(z, z . r): z32 widened to float64 and its dot product with r64, through the launch that ends the fp32 cycle."""
+        z32 = _f32(z32)
+        r64 = np.ascontiguousarray(r64, dtype=np.float64)
+        if len(r64) != len(z32):
+            raise ValueError("z32 and r64 differ in length")
+        z = np.zeros(len(z32))
+        dot = C.c_double()
+        _check(lib.sparsh_op_cvt_f2d_dot(self._h, len(z32), _fp(z32), _dp(r64), _dp(z), C.byref(dot)))
+        return z, dot.value
 
     def op_precond(self, r):
         """z = M r as "pbicg" / "pgmres" apply it: the V-cycle of the current smoother from a zero guess, or the fp32 cycle."""

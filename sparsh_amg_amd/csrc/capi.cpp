@@ -729,7 +729,8 @@ int sparsh_level_csr(sparsh_handle h, int level, int which, int *rowptr, int *co
     REQUIRE_HOST(h);
     REQUIRE_LEVEL(h, level);
     const HostLevel &L = h->eng->host().levels[level];
-    const HostCsr &M = (which == 0) ? L.A : L.P;
+    if (which < 0 || which > 2) return fail(SPARSH_EINVAL, "which must be 0 (A), 1 (P) or 2 (R)");
+    const HostCsr &M = (which == 0) ? L.A : (which == 1 ? L.P : L.R);
     if (!M.rowptr) return fail(SPARSH_EINVAL, "no such matrix on this level");
     std::memcpy(rowptr, M.rowptr, sizeof(int) * ((size_t)M.nrow + 1));
     std::memcpy(colindex, M.col, sizeof(int) * (size_t)M.nnz());
@@ -1375,6 +1376,144 @@ int sparsh_op_precond_f32(sparsh_handle h, const double *r, double *z)
     const size_t n = (size_t)E.level(0).n;
     DBuf dr(E, n, r), dz(E, n);
     if (!E.op_precond_f32(dr.p, dz.p)) return fail(SPARSH_ESTATE, E.error);
+    return done(E, dz.get(z));
+}
+
+// ---- the steps of the fp32 cycle one at a time (Engine::f32_*): float vectors in and out, nothing converted on the way
+}  // extern "C"
+
+namespace {
+
+// RAII device buffer of floats (DBuf's twin)
+struct FBuf {
+    Engine &E;
+    float *p = nullptr;
+    size_t n;
+    FBuf(Engine &e, size_t count, const float *src = nullptr) : E(e), n(count)
+    {
+        p = static_cast<float *>(E.dalloc(std::max(count, (size_t)1) * sizeof(float)));
+        if (p && src && count) (void)hipMemcpy(p, src, count * sizeof(float), hipMemcpyHostToDevice);
+    }
+    ~FBuf() { E.dfree(p); }
+    bool get(float *dst, const float *from = nullptr)
+    {
+        (void)hipStreamSynchronize(E.stream());
+        return n == 0 || hipMemcpy(dst, from ? from : p, n * sizeof(float), hipMemcpyDeviceToHost) == hipSuccess;
+    }
+};
+
+// The checks that need no device come first, so that they answer the same on a host-only handle: the mode (SPARSH_ESTATE), then the
+// level (SPARSH_EINVAL).  After the device checks, precond_fp32_active() covers a float hierarchy whose setup failed.
+#define REQUIRE_F32_MODE(h)                                                                                                          \
+    REQUIRE_HOST(h);                                                                                                                 \
+    if (!(h)->eng->params().precond_fp32 || (h)->eng->host().levels.size() < 2) return fail(SPARSH_ESTATE, kF32NotBuilt)
+
+#define REQUIRE_F32_DEVICE(h) \
+    REQUIRE_READY(h);         \
+    REQUIRE_SINGLE(h);        \
+    if (!(h)->eng->precond_fp32_active()) return fail(SPARSH_ESTATE, kF32NotBuilt)
+
+// a level with a float operator and transfer operators: every level but the coarsest
+#define REQUIRE_F32_LEVEL(h, l)                                                                                             \
+    REQUIRE_F32_MODE(h);                                                                                                    \
+    REQUIRE_LEVEL(h, l);                                                                                                    \
+    if ((l) + 1 >= (int)(h)->eng->host().levels.size())                                                                     \
+        return fail(SPARSH_EINVAL, "the coarsest level has no float operator (sparsh_op_coarse_f32 solves on it)"); \
+    REQUIRE_F32_DEVICE(h)
+
+}  // namespace
+
+extern "C" {
+
+int sparsh_level_f32_layout(sparsh_handle h, int level, int *layout)
+{
+    REQUIRE_F32_MODE(h);
+    REQUIRE_LEVEL(h, level);
+    REQUIRE_F32_DEVICE(h);
+    const Engine &E = *h->eng;
+    if (layout) *layout = level + 1 >= E.nlevels() ? 0 : (E.level_f32_sdia(level) ? 1 : 2);
+    return SPARSH_OK;
+}
+
+int sparsh_op_jacobi_f32(sparsh_handle h, int level, const float *b, float *x, int sweeps, int x_is_zero)
+{
+    REQUIRE_F32_LEVEL(h, level);
+    if (sweeps < 0) return fail(SPARSH_EINVAL, "sweeps < 0");
+    Engine &E = *h->eng;
+    const size_t n = (size_t)E.level(level).n;
+    FBuf db(E, n, b), dx(E, n, x), dt(E, n);
+    if (!db.p || !dx.p || !dt.p) return fail(SPARSH_ENODEV, E.error);
+    const float *res = E.op_jacobi_f32(level, db.p, dx.p, dt.p, sweeps, x_is_zero != 0);
+    return done(E, dx.get(x, res));
+}
+
+int sparsh_op_residual_f32(sparsh_handle h, int level, const float *b, const float *x, float *r)
+{
+    REQUIRE_F32_LEVEL(h, level);
+    Engine &E = *h->eng;
+    const size_t n = (size_t)E.level(level).n;
+    FBuf db(E, n, b), dx(E, n, x), dr(E, n);
+    if (!db.p || !dx.p || !dr.p) return fail(SPARSH_ENODEV, E.error);
+    E.f32_residual(level, db.p, dx.p, dr.p);
+    return done(E, dr.get(r));
+}
+
+int sparsh_op_restrict_f32(sparsh_handle h, int level, const float *r, float *bc)
+{
+    REQUIRE_F32_LEVEL(h, level);
+    Engine &E = *h->eng;
+    FBuf dr(E, (size_t)E.level(level).n, r), dc(E, (size_t)E.level(level + 1).n);
+    if (!dr.p || !dc.p) return fail(SPARSH_ENODEV, E.error);
+    E.f32_restrict(level, dr.p, dc.p);
+    return done(E, dc.get(bc));
+}
+
+int sparsh_op_prolong_f32(sparsh_handle h, int level, const float *xc, float *xf)
+{
+    REQUIRE_F32_LEVEL(h, level);
+    Engine &E = *h->eng;
+    FBuf dc(E, (size_t)E.level(level + 1).n, xc), df(E, (size_t)E.level(level).n, xf);
+    if (!dc.p || !df.p) return fail(SPARSH_ENODEV, E.error);
+    E.f32_prolong(level, dc.p, df.p);
+    return done(E, df.get(xf));
+}
+
+int sparsh_op_coarse_f32(sparsh_handle h, const float *b, float *x)
+{
+    REQUIRE_F32_MODE(h);
+    REQUIRE_F32_DEVICE(h);
+    Engine &E = *h->eng;
+    const size_t n = (size_t)E.level(E.nlevels() - 1).n;
+    FBuf db(E, n, b), dx(E, n);
+    if (!db.p || !dx.p) return fail(SPARSH_ENODEV, E.error);
+    E.f32_coarse(db.p, dx.p);
+    return done(E, dx.get(x));
+}
+
+int sparsh_op_cvt_f32(sparsh_handle h, long n, const double *in, float *out)
+{
+    REQUIRE_F32_MODE(h);
+    if (n <= 0) return fail(SPARSH_EINVAL, "n <= 0");
+    REQUIRE_F32_DEVICE(h);
+    Engine &E = *h->eng;
+    DBuf di(E, (size_t)n, in);
+    FBuf dout(E, (size_t)n);
+    if (!di.p || !dout.p) return fail(SPARSH_ENODEV, E.error);
+    E.f32_cvt(n, di.p, dout.p);
+    return done(E, dout.get(out));
+}
+
+int sparsh_op_cvt_f2d_dot(sparsh_handle h, int n, const float *z32, const double *r, double *z, double *dot)
+{
+    REQUIRE_F32_MODE(h);
+    if (n <= 0) return fail(SPARSH_EINVAL, "n <= 0");
+    REQUIRE_F32_DEVICE(h);
+    Engine &E = *h->eng;
+    FBuf dz32(E, (size_t)n, z32);
+    DBuf dr(E, (size_t)n, r), dz(E, (size_t)n);
+    if (!dz32.p || !dr.p || !dz.p) return fail(SPARSH_ENODEV, E.error);
+    const double d = E.op_cvt_f2d_dot(n, dz32.p, dr.p, dz.p);
+    if (dot) *dot = d;
     return done(E, dz.get(z));
 }
 

@@ -1594,55 +1594,116 @@ bool Engine::setup_f32()
     return true;
 }
 
+// ---- the steps of the fp32 cycle, each one launch (the factored coarsest level: convert, fp64 solve, convert) on the vectors it is
+// given.  vcycle_f32 is made of these calls alone, and the operator-level entry points (sparsh_op_*_f32) run the same functions one
+// at a time, so what the tests pin step by step is what the cycle launches.
+void Engine::f32_zero_sweep(int l, const float *b, float *x) { launch_jacobi_zero_f32(lev_[l].n, b, f32_[l].diag, (float)prm_.omega, x, st_); }
+
+void Engine::f32_apply(int l, CsrOp op, const float *b, const float *x, float *y)
+{
+    const F32Level &f = f32_[l];
+    const float w = (float)prm_.omega;
+    if (f.A.val)
+        launch_sdia_f32(f.A, op, x, b, y, w, st_);
+    else
+        launch_csr_f32(lev_[l].A, f.csr_val, op, f.diag, x, b, y, w, st_);
+}
+
+void Engine::f32_jacobi(int l, const float *b, const float *x, float *y) { f32_apply(l, OP_JACOBI, b, x, y); }
+
+void Engine::f32_residual(int l, const float *b, const float *x, float *r) { f32_apply(l, OP_RESID, b, x, r); }
+
+void Engine::f32_restrict(int l, const float *r, float *bc)
+{
+    launch_restrict_f32(lev_[l + 1].n, lev_[l].R.rowptr, lev_[l].R.col, lev_[l].R.val, r, bc, st_);
+}
+
+void Engine::f32_prolong(int l, const float *xc, float *xf)
+{
+    const DevLevel &F = lev_[l];
+    if (F.P_is_aggregation)
+        launch_prolong_agg_f32(F.n, F.P.col, xc, xf, st_);
+    else
+        launch_prolong_csr_f32(F.n, F.P.rowptr, F.P.col, F.P.val, xc, xf, st_);
+}
+
+void Engine::f32_coarse(const float *b, float *x)
+{
+    if (coarse_inv_f32_) {
+        launch_gemv_f32(nL_, coarse_inv_f32_, b, x, st_);
+    } else {
+        launch_cvt_f2d(nL_, b, coarse_tmp_, st_);
+        coarse_.solve(coarse_tmp_, coarse_tmp_ + nL_, st_);
+        launch_cvt_d2f(nL_, coarse_tmp_ + nL_, x, st_);
+    }
+}
+
+void Engine::f32_cvt(long n, const double *in, float *out) { launch_cvt_d2f(n, in, out, st_); }
+
+void Engine::f32_cvt_dot(int n, const float *z32, const double *r64, double *z64, double *partial, int *nblk)
+{
+    launch_cvt_f2d_dot(n, z32, r64, z64, partial, nblk, st_);
+}
+
 void Engine::vcycle_f32(const double *r64, double *z64, double *partial, int *nblk)
 {
     const int last = (int)lev_.size() - 1;
     const int nu = prm_.sweeps;
-    const float w = (float)prm_.omega;
-    launch_cvt_d2f((long)lev_[0].n, r64, f32_[0].b, st_);
-    auto apply = [&](int l, CsrOp op, const float *x, float *y) {
-        F32Level &f = f32_[l];
-        if (f.A.val)
-            launch_sdia_f32(f.A, op, x, f.b, y, w, st_);
-        else
-            launch_csr_f32(lev_[l].A, f.csr_val, op, f.diag, x, f.b, y, w, st_);
-    };
+    f32_cvt((long)lev_[0].n, r64, f32_[0].b);
     auto sweeps = [&](int l, int count) {
         F32Level &f = f32_[l];
         for (int k = 0; k < count; ++k) {
-            apply(l, OP_JACOBI, f.x, f.x2);
+            f32_jacobi(l, f.b, f.x, f.x2);
             std::swap(f.x, f.x2);
         }
     };
     for (int l = 0; l < last; ++l) {
         F32Level &f = f32_[l];
-        launch_jacobi_zero_f32(lev_[l].n, f.b, f.diag, w, f.x, st_);
+        f32_zero_sweep(l, f.b, f.x);
         sweeps(l, nu - 1);
-        apply(l, OP_RESID, f.x, f.r);
-        launch_restrict_f32(lev_[l + 1].n, lev_[l].R.rowptr, lev_[l].R.col, lev_[l].R.val, f.r, f32_[l + 1].b, st_);
+        f32_residual(l, f.b, f.x, f.r);
+        f32_restrict(l, f.r, f32_[l + 1].b);
     }
-    if (coarse_inv_f32_) {
-        launch_gemv_f32(nL_, coarse_inv_f32_, f32_[last].b, f32_[last].x, st_);
-    } else {
-        launch_cvt_f2d(nL_, f32_[last].b, coarse_tmp_, st_);
-        coarse_.solve(coarse_tmp_, coarse_tmp_ + nL_, st_);
-        launch_cvt_d2f(nL_, coarse_tmp_ + nL_, f32_[last].x, st_);
-    }
+    f32_coarse(f32_[last].b, f32_[last].x);
     for (int l = last; l > 0; --l) {
-        DevLevel &F = lev_[l - 1];
-        if (F.P_is_aggregation)
-            launch_prolong_agg_f32(F.n, F.P.col, f32_[l].x, f32_[l - 1].x, st_);
-        else
-            launch_prolong_csr_f32(F.n, F.P.rowptr, F.P.col, F.P.val, f32_[l].x, f32_[l - 1].x, st_);
+        f32_prolong(l - 1, f32_[l].x, f32_[l - 1].x);
         sweeps(l - 1, nu);
     }
-    launch_cvt_f2d_dot(lev_[0].n, f32_[0].x, r64, z64, partial, nblk, st_);
+    f32_cvt_dot(lev_[0].n, f32_[0].x, r64, z64, partial, nblk);
+}
+
+// Operator-level forms of the steps (device float vectors of the caller).  `sweeps` Jacobi sweeps of level l from x, the first one the
+// zero-guess sweep under x_is_zero; tmp is the ping-pong twin.  Returns the buffer (x or tmp) that holds the result.
+float *Engine::op_jacobi_f32(int l, const float *b, float *x, float *tmp, int sweeps, bool x_is_zero)
+{
+    int k = 0;
+    if (x_is_zero) {
+        if (sweeps > 0) {
+            f32_zero_sweep(l, b, x);
+            k = 1;
+        } else {
+            HIPCHK(hipMemsetAsync(x, 0, (size_t)lev_[l].n * 4, st_));
+        }
+    }
+    for (; k < sweeps; ++k) {
+        f32_jacobi(l, b, x, tmp);
+        std::swap(x, tmp);
+    }
+    return x;
+}
+
+double Engine::op_cvt_f2d_dot(int n, const float *z32, const double *r64, double *z64)
+{
+    int nb = 0;
+    f32_cvt_dot(n, z32, r64, z64, part0_, &nb);
+    finalize(FIN_STORE, part0_, nullptr, nb, S_TMP, nullptr, 0);
+    return read_scalar(S_TMP);
 }
 
 bool Engine::op_precond_f32(const double *r, double *z)
 {
     if (!f32_ready_) {
-        error = "the fp32 preconditioner hierarchy was not built (sparsh_params.precond_fp32 = 0, or a single level)";
+        error = kF32NotBuilt;
         return false;
     }
     int nb = 0;

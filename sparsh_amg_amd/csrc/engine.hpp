@@ -88,6 +88,9 @@ struct KrylovState {
     double r1 = 0.0;
 };
 
+// what every entry point of the fp32 cycle answers (SPARSH_ESTATE) on a handle that has no float hierarchy
+inline constexpr const char *kF32NotBuilt = "the fp32 preconditioner hierarchy was not built (sparsh_params.precond_fp32 = 0, or a single level)";
+
 // float mirror of one level for the opt-in fp32 preconditioner
 struct F32Level {
     SdiaF32 A;
@@ -337,6 +340,19 @@ public:
     void op_coarse(const double *b, double *x);
     // z = V32(r): one application of the opt-in fp32 preconditioner (fp64 in/out); needs precond_fp32
     bool op_precond_f32(const double *r, double *z);
+    // ---- the steps of the fp32 cycle on device float vectors (precond_fp32_active() only).  vcycle_f32 is made of these calls alone;
+    // sparsh_op_*_f32 run them one at a time on the caller's vectors
+    bool level_f32_sdia(int l) const { return f32_[l].A.val != nullptr; }  // float sliced-diagonal mirror (else float CSR values); l < last
+    void f32_zero_sweep(int l, const float *b, float *x);                 // x = (omega b) / d: the sweep from a zero guess
+    void f32_jacobi(int l, const float *b, const float *x, float *y);    // y = one Jacobi sweep of x
+    void f32_residual(int l, const float *b, const float *x, float *r);  // r = b - A_l x
+    void f32_restrict(int l, const float *r, float *bc);                 // b_{l+1} = R_l r
+    void f32_prolong(int l, const float *xc, float *xf);                 // x_l += P_l x_{l+1} (aggregation gather or CSR rows, as the level decides)
+    void f32_coarse(const float *b, float *x);                           // float inverse GEMV, or convert / fp64 factors / convert
+    void f32_cvt(long n, const double *in, float *out);                  // out = (float)in
+    void f32_cvt_dot(int n, const float *z32, const double *r64, double *z64, double *partial, int *nblk);  // z64 = z32 and the partial sums of z.r
+    float *op_jacobi_f32(int l, const float *b, float *x, float *tmp, int sweeps, bool x_is_zero);  // returns x or tmp: the one with the result
+    double op_cvt_f2d_dot(int n, const float *z32, const double *r64, double *z64);                  // f32_cvt_dot with the sum read back
     // z = M r as the Krylov loops apply it: the V-cycle of the current smoother from a zero guess, or the fp32 cycle; SPARSH_* code
     int op_precond(const double *r, double *z);
     // ---- restarted GMRES: restart length (0 = kGmresDefaultRestart); a changed length frees the basis
@@ -487,6 +503,7 @@ private:
     bool setup_f32();
     // V(nu,nu) cycle on the float hierarchy from a zero guess: z64 = V32(r64), partial sums of z.r
     void vcycle_f32(const double *r64, double *z64, double *partial, int *nblk);
+    void f32_apply(int l, CsrOp op, const float *b, const float *x, float *y);  // the level's sweep / residual launch (sdia or CSR mirror)
     void pcg_body(bool precond, int slot);
     bool capture_graph(bool precond);
     void drop_graph();
