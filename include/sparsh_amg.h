@@ -707,8 +707,67 @@ int sparsh_op_prolong_multi(sparsh_handle h, int level, int nrhs, const double *
 int sparsh_op_coarse_multi(sparsh_handle h, int nrhs, const double *B, double *X);
 int sparsh_op_precond_multi(sparsh_handle h, int nrhs, const double *R, double *Z);
 /* average seconds of `reps` back-to-back block launches on the level's resident block buffers: op 0 = SpMV + dot, 1 = Jacobi
- * sweeps ping-ponging (the counterpart of sparsh_bench_op 10) */
+ * sweeps ping-ponging (the counterpart of sparsh_bench_op 10); on the eigensolver's resident blocks of width multi_width(nrhs)
+ * (level 0 whatever `level` says; reserved by the call): op 2 = the twelve-pair Gram launch with its finalise, 3 = one update */
 int sparsh_bench_op_multi(sparsh_handle h, int op, int level, int nrhs, int reps, double *avg_seconds);
+
+/* ---- the lowest eigenpairs of the SPD level-0 operator by LOBPCG on the block path ----
+ * nev <= SPARSH_MAX_RHS eigenpairs A x = lambda x with the smallest lambda, the block V-cycle as preconditioner.  Standard problem
+ * only (no A x = lambda B x), SPD operators only, no null-space handles.  X is column-major, column c at X + c * ldx, ldx >= n: the
+ * start block on entry (it must have full rank), the Ritz vectors on return, orthonormal and ordered by ascending lambda[c].
+ * Notation: k = nev, W = the block width 2, 4 or 8 (k rounded up; padding columns hold zeros and are never active).
+ *  1. start: AX = A X; Rayleigh-Ritz on the pencil (X^T AX, X^T X) gives theta and C; X <- X C, AX <- AX C; there is no P yet.
+ *  2. R = AX - X diag(theta) (product and subtraction rounded separately), rn_c = ||R_c||_2.  Column c is active when
+ *     rn_c > tol |theta_c|; this is evaluated afresh every iteration (soft locking).  The solve stops when no column is active.
+ *  3. W = M R: one block V-cycle from a zero guess on all columns; AW = A W: one block SpMV.
+ *  4. the Gram matrices S^T S and S^T A S of S = [X, W, P], A S = [AX, AW, AP]: the upper block triangles, twelve W x W blocks, from one
+ *     launch over the pair list and one that adds the per-workgroup partial sums in a fixed order (no atomics).  Both matrices and
+ *     the residual norms reach the host in one pinned read.
+ *  5. host Rayleigh-Ritz on the rows and columns [all k of X, the active of W, the active of P] (no P in the first iteration):
+ *     scale by D = diag(GB)^-1/2, Cholesky D GB D = L L^T (a diagonal entry of L below 1e-7 is a breakdown: a condition number
+ *     near 1e14, past which the Ritz values carry no digits), T = L^-1 D GA D L^-T symmetrised, cyclic Jacobi to an off-diagonal
+ *     norm of at most eps ||T||_F, eigenvalues ascending, C = D L^-T Y[:, :k].  After a breakdown the step is repeated once without
+ *     P and a restart is counted; a second breakdown ends the solve.  C returns to the device as three W x W matrices Cx, Cw, Cp
+ *     whose rows of inactive and padding columns are zero.
+ *  6. update, one pass, every product and sum rounded on its own and c ascending over 0 .. k - 1:
+ *     P'_ij = sum_c W_ic Cw_cj, the running sum continued by + P_ic Cp_cj;  X'_ij = (sum_c X_ic Cx_cj) + P'_ij;  AP' and AX' likewise
+ *     from AW, AP, AX with the same coefficients.  Then theta <- the new Ritz values.
+ * One iteration is one host synchronisation: (3W)^2 * 16 + W * 8 bytes down, (3 W^2 + W) * 8 bytes up.  params.check_every is
+ * ignored.  The Gram launch of an iteration is queued before the host knows the residual norms, so the iteration that finds every
+ * column converged has run one cycle it did not need.
+ * hist[c * hist_cap + it] = rn_c at the start of iteration it (the evaluation that ends the solve included, while it < hist_cap; other
+ * entries are left untouched); iters[c] = the iterations in which column c was active; status[c] = SPARSH_OK or SPARSH_ENOCONV.
+ * max_iters <= 0 means params.max_iter.  Returns SPARSH_OK; SPARSH_ENOCONV at the cap (X and lambda then hold the last Ritz pairs,
+ * still orthonormal); SPARSH_ENUMERIC on a NaN or when the Rayleigh-Ritz step breaks down at the start (the message then says that
+ * the start block is rank deficient) or even after a restart (status[c] = SPARSH_ENUMERIC for every column, X is not written).
+ * SPARSH_EINVAL (with or without a device): nev outside 1..8 or above n, a NULL array, ldx below n, tol not finite or not positive,
+ * and every handle sparsh_solve_multi refuses: a partitioned (multi-GPU) handle, params.precond_fp32, a W- or K-cycle, a smoother
+ * other than Jacobi, a null-space handle.  SPARSH_ESTATE before sparsh_setup.  params.use_graph is accepted and ignored.  On a
+ * constant-coefficient box grid the solver runs the block path's CSR kernels, not the matrix-free ones.
+ * Memory: seven blocks of n * W doubles (X, AX, W, AW, P, AP, R), (12 W^2 + W) * 512 partial sums, 18 W^2 + W doubles of Gram
+ * matrices and residual norms and 3 W^2 + W of coefficients and theta, the solver's own: reserved at the first call for a width,
+ * replaced by a call with another width, freed by sparsh_setup and sparsh_destroy.  The cycle runs in the block vectors of
+ * sparsh_solve_multi (reserved alongside, see sparsh_multi_info), which carry nothing from call to call: a single or block solve
+ * before and after an eigen solve gives the same bits.  sparsh_eig_info: the width in force, the device bytes held by the above
+ * (both 0 until the first call) and the restarts of the last solve. */
+int sparsh_eigs(sparsh_handle h, int nev, double *X, long ldx, double tol, int max_iters, double *lambda, double *hist, int hist_cap,
+                int *iters, int *status);
+/* the same on a device array; *seconds (may be NULL): HIP-event time of the whole call on the engine's stream */
+int sparsh_eigs_dev(sparsh_handle h, int nev, double *X_dev, long ldx, double tol, int max_iters, double *lambda, double *hist, int hist_cap,
+                    int *iters, int *status, double *seconds);
+int sparsh_eig_info(sparsh_handle h, int *width, long *bytes, int *restarts);
+/* step 5 alone on a compacted pencil of order m <= 24 (row-major, upper triangles read): theta[k], C (m x k, row-major).  Returns
+ * 0, or 1 for a breakdown.  Needs no handle and no device. */
+int sparsh_debug_eig_small(int m, int k, const double *GA, const double *GB, double *theta, double *C);
+/* Operator-level hooks of the eigensolver's kernels: column-major host arrays of any n > 0 rows (ld = n); a ready handle lends its
+ * stream only.  gram: G = U^T V (nu x nv, row-major; nu, nv in 1..8).  eig_residual: R = AX - X diag(theta), norms[c] = ||R_c||_2.
+ * eig_update: step 6 with k x k row-major coefficient matrices; an output that is the array it replaces (Xo == X, Po == P,
+ * AXo == AX, APo == AP) is updated in place on the device too. */
+int sparsh_op_gram_multi(sparsh_handle h, int n, int nu, const double *U, int nv, const double *V, double *G);
+int sparsh_op_eig_residual(sparsh_handle h, int n, int k, const double *AX, const double *X, const double *theta, double *R, double *norms);
+int sparsh_op_eig_update(sparsh_handle h, int n, int k, const double *X, const double *W, const double *P, const double *AX, const double *AW,
+                         const double *AP, const double *Cx, const double *Cw, const double *Cp, double *Xo, double *Po, double *AXo,
+                         double *APo);
 
 /* device memory helpers so a host language needs no HIP binding of its own */
 int sparsh_dev_alloc(sparsh_handle h, long nbytes, void **out);

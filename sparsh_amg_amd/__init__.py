@@ -254,6 +254,14 @@ def _load():
         "sparsh_op_coarse_multi": (C.c_int, [H, C.c_int, c_dbl_p, c_dbl_p]),
         "sparsh_op_precond_multi": (C.c_int, [H, C.c_int, c_dbl_p, c_dbl_p]),
         "sparsh_bench_op_multi": (C.c_int, [H, C.c_int, C.c_int, C.c_int, C.c_int, c_dbl_p]),
+        "sparsh_eigs": (C.c_int, [H, C.c_int, c_dbl_p, C.c_long, C.c_double, C.c_int, c_dbl_p, c_dbl_p, C.c_int, c_int_p, c_int_p]),
+        "sparsh_eigs_dev": (C.c_int, [H, C.c_int, C.c_void_p, C.c_long, C.c_double, C.c_int, c_dbl_p, c_dbl_p, C.c_int, c_int_p, c_int_p,
+                                      c_dbl_p]),
+        "sparsh_eig_info": (C.c_int, [H, c_int_p, C.POINTER(C.c_long), c_int_p]),
+        "sparsh_debug_eig_small": (C.c_int, [C.c_int, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p]),
+        "sparsh_op_gram_multi": (C.c_int, [H, C.c_int, C.c_int, c_dbl_p, C.c_int, c_dbl_p, c_dbl_p]),
+        "sparsh_op_eig_residual": (C.c_int, [H, C.c_int, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p]),
+        "sparsh_op_eig_update": (C.c_int, [H, C.c_int, C.c_int] + [c_dbl_p] * 13),
         "sparsh_op_gs_dot": (C.c_int, [H, C.c_int, C.c_int, C.c_int, c_dbl_p, c_dbl_p, C.c_int, c_dbl_p]),
         "sparsh_op_gs_update": (C.c_int, [H, C.c_int, C.c_int, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p, C.c_int, C.c_int, C.c_int, C.c_double,
                                           c_dbl_p, c_dbl_p, c_dbl_p, c_int_p]),
@@ -359,6 +367,18 @@ def box_plan_candidates(kernel, nx, ny, nz, part_cap=0):
     if n < 0:
         raise ValueError("kernel must be 2 (double sweep) or 1 (plane-marching kernel)")
     return [tuple(buf[4 * i:4 * i + 4]) for i in range(min(n, cap))]
+
+
+def eig_small(GA, GB, k):
+    """Debug hook (host only): the Rayleigh-Ritz step of the eigensolver on the pencil (GA, GB) of order m <= 24.  Returns
+    (breakdown, theta[k], C (m, k))."""
+    GA, GB = np.ascontiguousarray(GA, dtype=np.float64), np.ascontiguousarray(GB, dtype=np.float64)
+    m = GA.shape[0]
+    if GA.shape != (m, m) or GB.shape != (m, m):
+        raise ValueError("GA and GB are square matrices of one order")
+    theta, Cm = np.zeros(max(int(k), 1)), np.zeros((m, max(int(k), 1)))
+    rc = _check(lib.sparsh_debug_eig_small(m, int(k), _dp(GA), _dp(GB), _dp(theta), _dp(Cm)), allow=(1,))
+    return rc, theta, Cm
 
 
 def device_count() -> int:
@@ -1289,9 +1309,76 @@ class sp_matrix_mg:
         _check(lib.sparsh_op_precond_multi(self._h, Rf.shape[1], _dp(Rf), _dp(Z)))
         return Z
 
+    # -- lowest eigenpairs by AMG-preconditioned LOBPCG on the block path -----------------------------------------
+    def eigs(self, k, X0=None, tol=1e-8, max_iters=0, seed=0, hist_cap=1024):
+        """The k <= 8 lowest eigenpairs of the SPD level-0 operator.  X0 (n, k): the start block (None: default_rng(seed)
+        .standard_normal((n, k))).  Returns (lam, X, iters, hist, status): lam ascending, X (n, k) orthonormal Ritz vectors, iters[c] the
+        iterations column c was active in, hist (k, evaluations) with hist[c, it] = ||A x_c - lam_c x_c|| at the start of iteration
+        it, status[c] SPARSH_OK or SPARSH_ENOCONV (the cap; the code of the call is kept in last_eigs_rc).  Other codes raise."""
+        k = int(k)
+        if X0 is None:
+            X0 = np.random.default_rng(seed).standard_normal((self.nrow, max(k, 0)))
+        Xf = self._block(X0)
+        if Xf.shape[1] != k:
+            raise ValueError(f"the start block has {Xf.shape[1]} columns, k = {k}")
+        kk = max(k, 1)
+        lam, hist = np.zeros(kk), np.full((kk, hist_cap), np.nan)
+        iters, status = np.zeros(kk, dtype=np.int32), np.zeros(kk, dtype=np.int32)
+        self.last_eigs_rc = _check(lib.sparsh_eigs(self._h, k, _dp(Xf), max(Xf.shape[0], 1), float(tol), int(max_iters), _dp(lam), _dp(hist),
+                                                   hist_cap, _ip(iters), _ip(status)), allow=(SPARSH_ENOCONV,))
+        nev = int(np.count_nonzero(~np.isnan(hist[0])))
+        return lam[:k].copy(), Xf, iters[:k].copy(), hist[:k, :nev].copy(), status[:k].copy()
+
+    def eigs_dev(self, k, X_dev, ldx, tol=1e-8, max_iters=0, hist_cap=1024):
+        """The same on a column-major device array (dev_alloc / h2d): the start block in, the Ritz vectors out.  Returns
+        (lam, iters, hist, status, seconds, rc)."""
+        kk = max(int(k), 1)
+        lam, hist = np.zeros(kk), np.full((kk, hist_cap), np.nan)
+        iters, status = np.zeros(kk, dtype=np.int32), np.zeros(kk, dtype=np.int32)
+        sec = C.c_double()
+        rc = _check(lib.sparsh_eigs_dev(self._h, int(k), X_dev, ldx, float(tol), int(max_iters), _dp(lam), _dp(hist), hist_cap, _ip(iters),
+                                        _ip(status), C.byref(sec)), allow=(SPARSH_ENOCONV,))
+        nev = int(np.count_nonzero(~np.isnan(hist[0])))
+        return lam[:k].copy(), iters[:k].copy(), hist[:k, :nev].copy(), status[:k].copy(), sec.value, rc
+
+    def eig_info(self):
+        """Width in force and device bytes held by the eigensolver's own blocks (both 0 until the first eigs call), and the
+        restarts of the last solve."""
+        w, b, r = C.c_int(), C.c_long(), C.c_int()
+        _check(lib.sparsh_eig_info(self._h, C.byref(w), C.byref(b), C.byref(r)))
+        return dict(width=w.value, bytes=b.value, restarts=r.value)
+
+    def op_gram_multi(self, U, V):
+        """G = U^T V (nu x nv) through the Gram launch of the eigensolver; U (n, nu), V (n, nv), any n > 0."""
+        Uf, Vf = self._block(U), self._block(V, np.shape(U)[0])
+        G = np.zeros((Uf.shape[1], Vf.shape[1]))
+        _check(lib.sparsh_op_gram_multi(self._h, Uf.shape[0], Uf.shape[1], _dp(Uf), Vf.shape[1], _dp(Vf), _dp(G)))
+        return G
+
+    def op_eig_residual(self, AX, X, theta):
+        """(R, norms): R = AX - X * theta and its column norms through the eigensolver's residual kernel."""
+        Af, Xf = self._block(AX), self._block(X, np.shape(AX)[0])
+        th = np.ascontiguousarray(theta, dtype=np.float64)
+        R, norms = np.zeros_like(Af, order="F"), np.zeros(Af.shape[1])
+        _check(lib.sparsh_op_eig_residual(self._h, Af.shape[0], Af.shape[1], _dp(Af), _dp(Xf), _dp(th), _dp(R), _dp(norms)))
+        return R, norms
+
+    def op_eig_update(self, X, W, P, AX, AW, AP, Cx, Cw, Cp, in_place=False):
+        """(X', P', AX', AP') of the eigensolver's update kernel; in_place: every output replaces its block on the device."""
+        n = np.shape(X)[0]
+        blocks = [self._block(b, n) for b in (X, W, P, AX, AW, AP)]
+        k = blocks[0].shape[1]
+        cs = [np.ascontiguousarray(c, dtype=np.float64) for c in (Cx, Cw, Cp)]
+        if any(c.shape != (k, k) for c in cs):
+            raise ValueError("the coefficient matrices are k x k")
+        outs = [blocks[i] for i in (0, 2, 3, 5)] if in_place else [np.zeros_like(blocks[0], order="F") for _ in range(4)]
+        _check(lib.sparsh_op_eig_update(self._h, n, k, *[_dp(b) for b in blocks], *[_dp(c) for c in cs], *[_dp(o) for o in outs]))
+        return tuple(outs)
+
     def bench_op_multi(self, op, level=0, nrhs=8, reps=20):
-        """Average seconds of one block launch on the level's resident block buffers: "spmv_dot" (0) or "jacobi_pingpong_resident" (1)."""
-        ops = {"spmv_dot": 0, "jacobi_pingpong_resident": 1}
+        """Average seconds of one block launch on the level's resident block buffers: "spmv_dot" (0) or "jacobi_pingpong_resident" (1);
+        on the eigensolver's resident blocks: "eig_gram" (2, the twelve-pair Gram launch with its finalise) or "eig_update" (3)."""
+        ops = {"spmv_dot": 0, "jacobi_pingpong_resident": 1, "eig_gram": 2, "eig_update": 3}
         sec = C.c_double()
         _check(lib.sparsh_bench_op_multi(self._h, ops[op] if isinstance(op, str) else op, int(level), int(nrhs), int(reps), C.byref(sec)))
         return sec.value

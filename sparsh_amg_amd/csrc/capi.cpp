@@ -11,6 +11,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include "../../include/sparsh_amg.h"
+#include "eig_small.hpp"
 #include "engine.hpp"
 
 using namespace sparsh;
@@ -2211,20 +2212,22 @@ int sparsh_op_precond_multi(sparsh_handle h, int nrhs, const double *R, double *
 int sparsh_bench_op_multi(sparsh_handle h, int op, int level, int nrhs, int reps, double *avg_seconds)
 {
     REQUIRE_MULTI_ARGS(h, nrhs);
-    if (op < 0 || op > 1) return fail(SPARSH_EINVAL, "unknown op");
+    if (op < 0 || op > 3) return fail(SPARSH_EINVAL, "unknown op");
     if (reps <= 0 || !avg_seconds) return fail(SPARSH_EINVAL, "bad reps");
     REQUIRE_READY(h);
     REQUIRE_SINGLE(h);
     REQUIRE_LEVEL(h, level);
     Engine &E = *h->eng;
-    if (int rc = E.multi_reserve(nrhs); rc != SPARSH_OK) return fail(rc, E.error);
+    const bool eig = op >= 2;  // the eigensolver's launches run on its own resident blocks (level 0)
+    if (int rc = eig ? E.eig_reserve(nrhs) : E.multi_reserve(nrhs); rc != SPARSH_OK) return fail(rc, E.error);
     hipStream_t st = E.stream();
-    for (int i = 0; i < 3; ++i) E.bench_multi_launch(op, level);
+    auto launch = [&]() { return eig ? E.bench_eig_launch(op) : E.bench_multi_launch(op, level); };
+    for (int i = 0; i < 3; ++i) launch();
     hipEvent_t e0, e1;
     (void)hipEventCreate(&e0);
     (void)hipEventCreate(&e1);
     (void)hipEventRecord(e0, st);
-    for (int i = 0; i < reps; ++i) E.bench_multi_launch(op, level);
+    for (int i = 0; i < reps; ++i) launch();
     (void)hipEventRecord(e1, st);
     (void)hipEventSynchronize(e1);
     float ms = 0.f;
@@ -2233,6 +2236,164 @@ int sparsh_bench_op_multi(sparsh_handle h, int op, int level, int nrhs, int reps
     (void)hipEventDestroy(e1);
     *avg_seconds = ms * 1e-3 / reps;
     return done(E, true);
+}
+
+// ---- lowest eigenpairs by LOBPCG on the block path ----
+
+// like REQUIRE_MULTI_ARGS: what no setup can make valid is SPARSH_EINVAL with or without a device
+#define REQUIRE_EIG_ARGS(h, nev, X, ldx, tol, lambda, hist, hist_cap, iters, status)                                          \
+    if (!(h) || !(h)->eng) return fail(SPARSH_EINVAL, "null handle");                                                         \
+    if ((nev) < 1 || (nev) > SPARSH_MAX_RHS) return fail(SPARSH_EINVAL, "nev must be 1 .. SPARSH_MAX_RHS (8)");                 \
+    if ((nev) > (h)->eng->n0()) return fail(SPARSH_EINVAL, "nev exceeds the number of rows");                                  \
+    if (!(X) || !(lambda) || !(iters) || !(status) || ((hist_cap) > 0 && !(hist))) return fail(SPARSH_EINVAL, "NULL array"); \
+    if ((hist_cap) < 0) return fail(SPARSH_EINVAL, "hist_cap < 0");                                                           \
+    if ((ldx) < (h)->eng->n0()) return fail(SPARSH_EINVAL, "ldx must be at least the number of rows");                         \
+    if (!std::isfinite(tol) || !((tol) > 0.0)) return fail(SPARSH_EINVAL, "tol must be finite and positive");                 \
+    REQUIRE_MULTI_FITS(h)
+
+int sparsh_eigs_dev(sparsh_handle h, int nev, double *X_dev, long ldx, double tol, int max_iters, double *lambda, double *hist, int hist_cap,
+                    int *iters, int *status, double *seconds)
+{
+    REQUIRE_EIG_ARGS(h, nev, X_dev, ldx, tol, lambda, hist, hist_cap, iters, status);
+    REQUIRE_READY(h);
+    int rc = h->eng->eigs_dev(nev, X_dev, ldx, tol, max_iters, lambda, hist, hist_cap, iters, status, seconds);
+    if (rc != SPARSH_OK) return fail(rc, h->eng->error);
+    return rc;
+}
+
+int sparsh_eigs(sparsh_handle h, int nev, double *X, long ldx, double tol, int max_iters, double *lambda, double *hist, int hist_cap,
+                int *iters, int *status)
+{
+    REQUIRE_EIG_ARGS(h, nev, X, ldx, tol, lambda, hist, hist_cap, iters, status);
+    REQUIRE_READY(h);
+    Engine &E = *h->eng;
+    const size_t n = (size_t)E.n0();
+    DBuf dx(E, n * nev);  // packed (leading dimension n): only the n rows of every column travel
+    if (!dx.p) return fail(SPARSH_ENODEV, E.error);
+    for (int c = 0; c < nev; ++c) (void)hipMemcpy(dx.p + (size_t)c * n, X + (size_t)c * ldx, n * 8, hipMemcpyHostToDevice);
+    int rc = E.eigs_dev(nev, dx.p, (long)n, tol, max_iters, lambda, hist, hist_cap, iters, status, nullptr);
+    (void)hipStreamSynchronize(E.stream());
+    if (rc == SPARSH_OK || rc == SPARSH_ENOCONV)
+        for (int c = 0; c < nev; ++c) (void)hipMemcpy(X + (size_t)c * ldx, dx.p + (size_t)c * n, n * 8, hipMemcpyDeviceToHost);
+    if (rc != SPARSH_OK) return fail(rc, E.error);
+    return rc;
+}
+
+int sparsh_eig_info(sparsh_handle h, int *width, long *bytes, int *restarts)
+{
+    if (!h || !h->eng) return fail(SPARSH_EINVAL, "null handle");
+    if (width) *width = h->eng->eig_width_now();
+    if (bytes) *bytes = (long)h->eng->eig_bytes();
+    if (restarts) *restarts = h->eng->eig_restarts();
+    return SPARSH_OK;
+}
+
+int sparsh_debug_eig_small(int m, int k, const double *GA, const double *GB, double *theta, double *C)
+{
+    if (m < 1 || m > kEigSmallMax || k < 1 || k > m || k > SPARSH_MAX_RHS) return fail(SPARSH_EINVAL, "m must be 1 .. 24 and k 1 .. min(m, 8)");
+    if (!GA || !GB || !theta || !C) return fail(SPARSH_EINVAL, "NULL array");
+    return eig_small(m, k, GA, GB, theta, C);
+}
+
+// ---- operator-level hooks of the eigensolver's kernels (eig_kernels.hip): the handle lends its stream and allocator only
+
+#define REQUIRE_EIG_OP(h, n)                                          \
+    if (!(h) || !(h)->eng) return fail(SPARSH_EINVAL, "null handle"); \
+    if ((n) <= 0) return fail(SPARSH_EINVAL, "n <= 0");               \
+    REQUIRE_READY(h);                                                 \
+    REQUIRE_SINGLE(h)
+
+int sparsh_op_gram_multi(sparsh_handle h, int n, int nu, const double *U, int nv, const double *V, double *G)
+{
+    REQUIRE_EIG_OP(h, n);
+    if (nu < 1 || nu > SPARSH_MAX_RHS || nv < 1 || nv > SPARSH_MAX_RHS) return fail(SPARSH_EINVAL, "nu and nv must be 1 .. SPARSH_MAX_RHS (8)");
+    if (!U || !V || !G) return fail(SPARSH_EINVAL, "NULL array");
+    Engine &E = *h->eng;
+    const int W = multi_width(std::max(nu, nv));
+    const size_t len = (size_t)n * W;
+    DBuf du(E, (size_t)n * nu, U), dv(E, (size_t)n * nv, V), bu(E, len), bv(E, len), part(E, (size_t)W * W * eig_grid(n, W)), g(E, (size_t)W * W);
+    if (!du.p || !dv.p || !bu.p || !bv.p || !part.p || !g.p) return fail(SPARSH_ENODEV, "device allocation or H2D copy failed");
+    launch_interleave(n, nu, W, du.p, n, bu.p, E.stream());
+    launch_interleave(n, nv, W, dv.p, n, bv.p, E.stream());
+    GramPairs prs{};
+    prs.u[0] = bu.p;
+    prs.v[0] = bv.p;
+    launch_gram_multi(n, W, 1, prs, part.p, g.p, W, E.stream());
+    std::vector<double> full((size_t)W * W);
+    if (!g.get(full.data())) return done(E, false);
+    for (int a = 0; a < nu; ++a)
+        for (int b = 0; b < nv; ++b) G[a * nv + b] = full[(size_t)a * W + b];
+    return done(E, true);
+}
+
+int sparsh_op_eig_residual(sparsh_handle h, int n, int k, const double *AX, const double *X, const double *theta, double *R, double *norms)
+{
+    REQUIRE_EIG_OP(h, n);
+    if (k < 1 || k > SPARSH_MAX_RHS) return fail(SPARSH_EINVAL, "k must be 1 .. SPARSH_MAX_RHS (8)");
+    if (!AX || !X || !theta || !R || !norms) return fail(SPARSH_EINVAL, "NULL array");
+    Engine &E = *h->eng;
+    const int W = multi_width(k);
+    const size_t len = (size_t)n * W;
+    std::vector<double> th(W, 0.0);
+    std::copy(theta, theta + k, th.begin());
+    DBuf dax(E, (size_t)n * k, AX), dx(E, (size_t)n * k, X), bax(E, len), bx(E, len), br(E, len), dth(E, (size_t)W, th.data()),
+        part(E, (size_t)W * eig_grid(n, W)), dn(E, (size_t)W), dr(E, (size_t)n * k);
+    if (!dax.p || !dx.p || !bax.p || !bx.p || !br.p || !dth.p || !part.p || !dn.p || !dr.p)
+        return fail(SPARSH_ENODEV, "device allocation or H2D copy failed");
+    launch_interleave(n, k, W, dax.p, n, bax.p, E.stream());
+    launch_interleave(n, k, W, dx.p, n, bx.p, E.stream());
+    launch_eig_residual(n, W, bax.p, bx.p, dth.p, br.p, part.p, dn.p, E.stream());
+    launch_deinterleave(n, k, W, br.p, dr.p, n, E.stream());
+    if (!dr.get(R) || !dn.get(th.data())) return done(E, false);
+    std::copy(th.begin(), th.begin() + k, norms);
+    return done(E, true);
+}
+
+int sparsh_op_eig_update(sparsh_handle h, int n, int k, const double *X, const double *W, const double *P, const double *AX, const double *AW,
+                         const double *AP, const double *Cx, const double *Cw, const double *Cp, double *Xo, double *Po, double *AXo,
+                         double *APo)
+{
+    REQUIRE_EIG_OP(h, n);
+    if (k < 1 || k > SPARSH_MAX_RHS) return fail(SPARSH_EINVAL, "k must be 1 .. SPARSH_MAX_RHS (8)");
+    if (!X || !W || !P || !AX || !AW || !AP || !Cx || !Cw || !Cp || !Xo || !Po || !AXo || !APo) return fail(SPARSH_EINVAL, "NULL array");
+    Engine &E = *h->eng;
+    const int Wd = multi_width(k);
+    const size_t len = (size_t)n * Wd, cm = (size_t)n * k;
+    // an output that is the array it replaces (Xo == X, ...) is updated in place on the device as well
+    const double *in[6] = {X, W, P, AX, AW, AP};
+    double *out[4] = {Xo, Po, AXo, APo};
+    const int replaces[4] = {0, 2, 3, 5};
+    std::vector<double> coef(3 * (size_t)Wd * Wd, 0.0);
+    const double *cs[3] = {Cx, Cw, Cp};
+    for (int m = 0; m < 3; ++m)
+        for (int a = 0; a < k; ++a)
+            for (int b = 0; b < k; ++b) coef[(size_t)m * Wd * Wd + a * Wd + b] = cs[m][a * k + b];
+    DBuf stage(E, cm), dcoef(E, coef.size(), coef.data());
+    std::vector<std::unique_ptr<DBuf>> bi, bo;
+    bool ok = stage.p && dcoef.p;
+    for (int i = 0; i < 6 && ok; ++i) {
+        bi.emplace_back(new DBuf(E, len));
+        ok = bi.back()->p && hipMemcpy(stage.p, in[i], cm * 8, hipMemcpyHostToDevice) == hipSuccess;
+        if (ok) launch_interleave(n, k, Wd, stage.p, n, bi.back()->p, E.stream());
+        if (ok) ok = hipStreamSynchronize(E.stream()) == hipSuccess;
+    }
+    double *dst[4] = {nullptr, nullptr, nullptr, nullptr};
+    for (int o = 0; o < 4 && ok; ++o) {
+        if (out[o] == in[replaces[o]]) {
+            dst[o] = bi[replaces[o]]->p;
+        } else {
+            bo.emplace_back(new DBuf(E, len));
+            ok = bo.back()->p != nullptr;
+            dst[o] = bo.back()->p;
+        }
+    }
+    if (!ok) return fail(SPARSH_ENODEV, "device allocation or H2D copy failed");
+    launch_eig_update(n, Wd, k, bi[0]->p, bi[1]->p, bi[2]->p, bi[3]->p, bi[4]->p, bi[5]->p, dcoef.p, dst[0], dst[1], dst[2], dst[3], E.stream());
+    for (int o = 0; o < 4 && ok; ++o) {
+        launch_deinterleave(n, k, Wd, dst[o], stage.p, n, E.stream());
+        ok = stage.get(out[o]);
+    }
+    return done(E, ok);
 }
 
 }  // extern "C"

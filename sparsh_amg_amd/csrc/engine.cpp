@@ -84,6 +84,7 @@ Engine::~Engine()
     for (auto e : prof.ev) (void)hipEventDestroy(e);
     for (void *p : allocs_) (void)hipFree(p);
     if (pinned_) (void)hipHostFree(pinned_);
+    if (epinned_) (void)hipHostFree(epinned_);
     if (ev_ready_) (void)hipEventDestroy(ev_ready_);
     if (ev_halo_) (void)hipEventDestroy(ev_halo_);
     if (st2_) (void)hipStreamDestroy(st2_);
@@ -1252,6 +1253,7 @@ int Engine::setup(const sparsh_params &p)
     gm_basisf_ = nullptr;
     gm_bytes_ = 0;
     multi_forget();  // (the block vectors too: the next block call reallocates them)
+    eig_forget();    // (and the eigensolver's blocks)
     sor_.clear();
     cheb_.clear();  // (the d vectors are freed with the rest)
     wk_.clear();    // (so are the extra vectors of the W- and K-cycles)

@@ -396,6 +396,20 @@ public:
     // bench: op 0 = SpMV + dot, 1 = Jacobi sweeps ping-ponging, on level l's block buffers of the width in force
     int bench_multi_launch(int op, int l);
 
+    // ---- lowest eigenpairs by LOBPCG on the block path (engine_eig.cpp).  The handles multi_refusal() turns
+    // away are turned away here too.  The solver's blocks (X, AX, W, AW, P, AP, R), partial sums and small matrices are its own,
+    // reserved at the first call for a width and freed by setup and the destructor; the cycle runs in the block path's level buffers.
+    int eig_reserve(int nev);
+    void eig_release();
+    int eig_width_now() const { return ew_; }
+    size_t eig_bytes() const { return eig_bytes_; }
+    int eig_restarts() const { return eig_restarts_; }
+    // column-major device array X (start block in, Ritz vectors out), host arrays lambda[nev], hist[c * hist_cap + it], iters, status
+    int eigs_dev(int nev, double *X, long ldx, double tol, int max_iters, double *lambda, double *hist, int hist_cap, int *iters, int *status,
+                 double *seconds);
+    // bench: op 2 = the twelve-pair Gram launch with its finalise, 3 = one update, on the resident eig blocks
+    int bench_eig_launch(int op);
+
     // device memory helpers
     void *dalloc(size_t bytes);
     void dfree(void *p);
@@ -553,6 +567,18 @@ private:
     MultiState ms_;
     int mflip_ = 0;  // bench_multi_launch
     std::vector<void *> multi_allocs_;
+
+    // LOBPCG (engine_eig.cpp): seven interleaved blocks of n * width doubles, the partial sums of the Gram and residual launches,
+    // G = [S^T S, S^T A S, residual norms] and coef = [Cx, Cw, Cp, theta]
+    void eig_forget();  // the buffers went with allocs_ (setup): drop the pointers
+    void eig_gram_pairs(GramPairs &prs) const;
+    int ew_ = 0;        // width in force (0: nothing allocated)
+    size_t eig_bytes_ = 0;
+    int eig_restarts_ = 0;
+    double *eX_ = nullptr, *eAX_ = nullptr, *eW_ = nullptr, *eAW_ = nullptr, *eP_ = nullptr, *eAP_ = nullptr, *eR_ = nullptr;
+    double *epart_ = nullptr, *eG_ = nullptr, *ecoef_ = nullptr;
+    double *epinned_ = nullptr;  // host-pinned: G coming down, coef going up
+    std::vector<void *> eig_allocs_;
 
     std::unique_ptr<Comm> comm_;
     std::vector<Partition> parts_;  // row partition of every level

@@ -1,0 +1,267 @@
+// engine_eig.cpp -- the lowest eigenpairs of the SPD level-0 operator by LOBPCG, preconditioned with the block V-cycle (DESIGN.md
+// section 5i).
+//
+// The device keeps the search space S = [X, W, P] and A S as interleaved blocks and computes the Gram matrices S^T S and S^T A S; the
+// host solves the small pencil (eig_small.cpp) on the rows and columns of the active columns and sends back the coefficients of the
+// update.  One iteration is one host synchronisation.  The cycle and the block SpMV are those of engine_multi.cpp (vcycle_multi,
+// multi_spmv_dot) and run in the block path's level buffers, which hold nothing between calls; everything that carries state here is
+// the solver's own allocation.
+#include "eig_small.hpp"
+#include "engine.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+
+namespace sparsh {
+
+#define HIPCHK(call) note_hip((call), #call)
+
+namespace {
+
+constexpr int kEigPinnedDown = 2 * kEigSmallMax * kEigSmallMax + kMultiMax;  // both Gram matrices and the residual norms
+constexpr int kEigPinnedUp = 3 * kMultiMax * kMultiMax + kMultiMax;          // Cx, Cw, Cp and theta
+
+}  // namespace
+
+void Engine::eig_forget()
+{
+    ew_ = 0;
+    eig_bytes_ = 0;
+    eig_restarts_ = 0;
+    eig_allocs_.clear();
+    eX_ = eAX_ = eW_ = eAW_ = eP_ = eAP_ = eR_ = epart_ = eG_ = ecoef_ = nullptr;
+}
+
+void Engine::eig_release()
+{
+    if (st_ && !eig_allocs_.empty()) (void)hipStreamSynchronize(st_);
+    for (void *p : eig_allocs_) dfree(p);
+    eig_forget();
+}
+
+int Engine::eig_reserve(int nev)
+{
+    const int W = multi_width(nev);
+    if (W == ew_) return SPARSH_OK;
+    eig_release();
+    bool ok = true;
+    auto take = [&](size_t doubles) -> double * {
+        if (!ok) return nullptr;
+        const size_t bytes = doubles * 8;
+        double *p = static_cast<double *>(dalloc(bytes));
+        if (!p || !check(hipMemsetAsync(p, 0, bytes, st_), "hipMemsetAsync")) {
+            ok = false;
+            return p;
+        }
+        eig_allocs_.push_back(p);
+        eig_bytes_ += bytes;
+        return p;
+    };
+    const size_t len = (size_t)lev_[0].n * W;
+    double **blocks[7] = {&eX_, &eAX_, &eW_, &eAW_, &eP_, &eAP_, &eR_};
+    for (double **b : blocks) *b = take(len);
+    epart_ = take((size_t)(kEigPairs * W * W + W) * kEigMaxGrid);  // Gram partials, then the residual's
+    eG_ = take((size_t)2 * 9 * W * W + W);                         // S^T S, S^T A S (order 3 W each), residual norms
+    ecoef_ = take((size_t)3 * W * W + W);                          // Cx, Cw, Cp, theta
+    if (ok && !epinned_)
+        ok = check(hipHostMalloc(reinterpret_cast<void **>(&epinned_), (kEigPinnedDown + kEigPinnedUp) * sizeof(double), hipHostMallocDefault),
+                   "hipHostMalloc");
+    if (!ok) {
+        eig_release();
+        return SPARSH_ENODEV;
+    }
+    ew_ = W;
+    return SPARSH_OK;
+}
+
+// the pair list of one Gram launch: X^T X and X^T AX first (the start needs these two only), then the rest of the upper block
+// triangles of S^T S (at G) and S^T A S (at G + 9 W^2), S = [X, W, P]
+void Engine::eig_gram_pairs(GramPairs &prs) const
+{
+    const int W = ew_, ld = 3 * W;
+    const double *S[3] = {eX_, eW_, eP_}, *AS[3] = {eAX_, eAW_, eAP_};
+    int p = 0;
+    auto add = [&](int bi, int bj, bool a) {
+        prs.u[p] = S[bi];
+        prs.v[p] = a ? AS[bj] : S[bj];
+        prs.dst[p] = (a ? ld * ld : 0) + bi * W * ld + bj * W;
+        ++p;
+    };
+    add(0, 0, false);
+    add(0, 0, true);
+    for (int a = 0; a < 2; ++a)
+        for (int bi = 0; bi < 3; ++bi)
+            for (int bj = bi; bj < 3; ++bj)
+                if (bi + bj > 0) add(bi, bj, a != 0);
+}
+
+int Engine::eigs_dev(int nev, double *X, long ldx, double tol, int max_iters, double *lambda, double *hist, int hist_cap, int *iters,
+                     int *status, double *seconds)
+{
+    if (!ready_) {
+        error = "sparsh_setup has not been called";
+        return SPARSH_ESTATE;
+    }
+    if (fault_ != SPARSH_OK) return fault_;
+    if (const char *why = multi_refusal()) {
+        error = why;
+        return SPARSH_EINVAL;
+    }
+    if (int rc = multi_reserve(nev); rc != SPARSH_OK) return rc;  // the cycle's own blocks
+    if (int rc = eig_reserve(nev); rc != SPARSH_OK) return rc;
+    if (max_iters <= 0) max_iters = prm_.max_iter;
+    const int W = ew_, n = lev_[0].n, k = nev, ld = 3 * W;
+    const size_t len = (size_t)n * W;
+    const int ndown = 2 * ld * ld + W, nup = 3 * W * W + W;
+    double *down = epinned_, *up = epinned_ + kEigPinnedDown;
+    eig_restarts_ = 0;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (seconds) {
+        HIPCHK(hipEventCreate(&e0));
+        HIPCHK(hipEventCreate(&e1));
+        HIPCHK(hipEventRecord(e0, st_));
+    }
+    GramPairs prs;
+    eig_gram_pairs(prs);
+    double *norms = eG_ + 2 * ld * ld, *theta_dev = ecoef_ + 3 * W * W, *rpart = epart_ + (size_t)kEigPairs * W * W * kEigMaxGrid;
+    double theta[kMultiMax] = {0}, rn[kMultiMax] = {0};
+    bool active[kMultiMax] = {false};
+    double GA[kEigSmallMax * kEigSmallMax], GB[kEigSmallMax * kEigSmallMax], C[kEigSmallMax * kMultiMax];
+    int idx[kEigSmallMax];
+
+    auto read_down = [&](int first, int count) {  // G[first, first + count) -> down[first, ...), one pinned read
+        HIPCHK(hipMemcpyAsync(down + first, eG_ + first, (size_t)count * 8, hipMemcpyDeviceToHost, st_));
+        HIPCHK(hipStreamSynchronize(st_));
+    };
+    // the compacted pencil on the rows and columns idx[0, m) of G, its k lowest pairs, and the coefficient matrices on their way up
+    auto rayleigh_ritz = [&](int m) -> int {
+        for (int i = 0; i < m; ++i)
+            for (int j = 0; j < m; ++j) {
+                const int a = std::min(idx[i], idx[j]), b = std::max(idx[i], idx[j]);  // the device fills the upper block triangle
+                GB[i * m + j] = down[a * ld + b];
+                GA[i * m + j] = down[ld * ld + a * ld + b];
+            }
+        if (eig_small(m, k, GA, GB, theta, C) != 0) return 1;
+        std::fill(up, up + nup, 0.0);
+        for (int i = 0; i < m; ++i)
+            for (int j = 0; j < k; ++j) up[(idx[i] / W) * W * W + (idx[i] % W) * W + j] = C[i * k + j];
+        std::copy(theta, theta + k, up + 3 * W * W);
+        HIPCHK(hipMemcpyAsync(ecoef_, up, (size_t)nup * 8, hipMemcpyHostToDevice, st_));
+        return 0;
+    };
+    auto finite = [&](const double *p, int cnt) {
+        for (int i = 0; i < cnt; ++i)
+            if (!std::isfinite(p[i])) return false;
+        return true;
+    };
+    auto stop_clock = [&]() {
+        if (!seconds) return;
+        HIPCHK(hipEventRecord(e1, st_));
+        HIPCHK(hipEventSynchronize(e1));
+        float ms = 0.f;
+        HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+        *seconds = ms * 1e-3;
+        HIPCHK(hipEventDestroy(e0));
+        HIPCHK(hipEventDestroy(e1));
+    };
+    auto numeric = [&](const char *what) {
+        stop_clock();
+        for (int c = 0; c < k; ++c) status[c] = SPARSH_ENUMERIC;
+        if (fault_ != SPARSH_OK) return fault_;  // (a NaN that a failed launch left behind: the fault's own message stands)
+        error = what;
+        return (int)SPARSH_ENUMERIC;
+    };
+
+    // 1. start: AX = A X, Rayleigh-Ritz on (X^T AX, X^T X), X <- X C, AX <- AX C; no P yet
+    for (int c = 0; c < k; ++c) iters[c] = 0, status[c] = SPARSH_OK;
+    launch_interleave(n, k, W, X, ldx, eX_, st_);
+    for (double *b : {eW_, eAW_, eP_, eAP_}) HIPCHK(hipMemsetAsync(b, 0, len * 8, st_));
+    HIPCHK(hipMemsetAsync(eG_, 0, (size_t)ndown * 8, st_));
+    multi_spmv_dot(0, eX_, eAX_, mpart0_);
+    launch_gram_multi(n, W, 2, prs, epart_, eG_, ld, st_);
+    read_down(0, 2 * ld * ld);
+    for (int c = 0; c < k; ++c) idx[c] = c;
+    if (fault_ != SPARSH_OK) {  // (the fault's own message stands)
+        stop_clock();
+        return fault_;
+    }
+    if (!finite(down, 2 * ld * ld)) return numeric("NaN in the start block or in A times the start block");
+    if (rayleigh_ritz(k) != 0) return numeric("Rayleigh-Ritz breakdown at the start: the start block is rank deficient");
+    launch_eig_update(n, W, k, eX_, eW_, eP_, eAX_, eAW_, eAP_, ecoef_, eX_, eP_, eAX_, eAP_, st_);  // (Cw = Cp = 0: P stays 0)
+
+    bool have_p = false, converged = false;
+    for (int it = 0; fault_ == SPARSH_OK; ++it) {
+        // 2. residual; at the cap only its norms are wanted
+        launch_eig_residual(n, W, eAX_, eX_, theta_dev, eR_, rpart, norms, st_);
+        const bool last = it >= max_iters;
+        if (!last) {
+            // 3. W = M R, AW = A W ; 4. the Gram matrices of S = [X, W, P] and A S
+            vcycle_multi(eR_);
+            HIPCHK(hipMemcpyAsync(eW_, mlev_[0].x, len * 8, hipMemcpyDeviceToDevice, st_));
+            multi_spmv_dot(0, eW_, eAW_, mpart0_);
+            launch_gram_multi(n, W, kEigPairs, prs, epart_, eG_, ld, st_);
+            read_down(0, ndown);
+        } else {
+            read_down(2 * ld * ld, W);
+        }
+        if (fault_ != SPARSH_OK) break;
+        std::copy(down + 2 * ld * ld, down + 2 * ld * ld + k, rn);
+        if (!finite(rn, k)) return numeric("NaN residual in the eigensolver");
+        int nact = 0;
+        for (int c = 0; c < k; ++c) {
+            active[c] = rn[c] > tol * std::fabs(theta[c]);  // re-evaluated every iteration: soft locking
+            nact += active[c];
+            if (hist && it < hist_cap) hist[(size_t)c * hist_cap + it] = rn[c];
+        }
+        if (prm_.print_solve) std::printf("%d\t%d of %d eigenpairs active\n", it, nact, k);
+        if (nact == 0) {
+            converged = true;
+            break;
+        }
+        if (last) break;
+        if (!finite(down, 2 * ld * ld)) return numeric("NaN in the Gram matrices of the eigensolver");
+        // 5. Rayleigh-Ritz on [all of X, active of W, active of P]; after a breakdown once more without P
+        int m = k;
+        for (int c = 0; c < k; ++c)
+            if (active[c]) idx[m++] = W + c;
+        const int m_xw = m;
+        if (have_p)
+            for (int c = 0; c < k; ++c)
+                if (active[c]) idx[m++] = 2 * W + c;
+        if (rayleigh_ritz(m) != 0) {
+            ++eig_restarts_;
+            if (m == m_xw || rayleigh_ritz(m_xw) != 0)
+                return numeric("Rayleigh-Ritz breakdown even after a restart without P (the start block had full rank)");
+        }
+        for (int c = 0; c < k; ++c) iters[c] += active[c];
+        // 6. update
+        launch_eig_update(n, W, k, eX_, eW_, eP_, eAX_, eAW_, eAP_, ecoef_, eX_, eP_, eAX_, eAP_, st_);
+        have_p = true;
+    }
+    launch_deinterleave(n, k, W, eX_, X, ldx, st_);
+    HIPCHK(hipStreamSynchronize(st_));
+    stop_clock();
+    note_hip(hipGetLastError(), "kernel launch during the eigensolve");
+    if (fault_ != SPARSH_OK) return fault_;
+    std::copy(theta, theta + k, lambda);
+    if (converged) return SPARSH_OK;
+    for (int c = 0; c < k; ++c) status[c] = active[c] ? SPARSH_ENOCONV : SPARSH_OK;
+    error = "iteration cap reached before ||A x - lambda x|| <= tol |lambda| for every eigenpair";
+    return SPARSH_ENOCONV;
+}
+
+int Engine::bench_eig_launch(int op)
+{
+    const int n = lev_[0].n;
+    if (op == 2) {
+        GramPairs prs;
+        eig_gram_pairs(prs);
+        launch_gram_multi(n, ew_, kEigPairs, prs, epart_, eG_, 3 * ew_, st_);
+    } else {
+        launch_eig_update(n, ew_, ew_, eX_, eW_, eP_, eAX_, eAW_, eAP_, ecoef_, eX_, eP_, eAX_, eAP_, st_);
+    }
+    return SPARSH_OK;
+}
+
+}  // namespace sparsh

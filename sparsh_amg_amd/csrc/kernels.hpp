@@ -465,4 +465,25 @@ void launch_p_update_multi(int n, int W, const MultiState &s, const double *z, d
 void launch_finalize_multi(MultiFin code, int W, int nrhs, const double *p0, int n0, const double *p1, int n1, const MultiState &s, int slot,
                            double tol, double *hist, int hist_cap, int it, hipStream_t st);
 
+// ---- LOBPCG eigensolver on interleaved blocks (eig_kernels.hip).  Every product and sum is rounded on its own;
+// reducing launches write one partial per sum and workgroup, eig_grid(n, W) of them, and combine them in a fixed order.
+constexpr int kEigPairs = 12;     // block pairs of one Gram launch: the upper block triangles of S^T S and S^T A S, S = [X, W, P]
+constexpr int kEigMaxGrid = 512;  // workgroups (per pair) of a launch: one per 512 / W rows, capped
+int eig_grid(int n, int W);
+struct GramPairs {
+    const double *u[kEigPairs], *v[kEigPairs];  // pair p: U^T V of the blocks u[p], v[p] (n x W, interleaved; may be one block)
+    int dst[kEigPairs];                         // offset of its W x W result in G
+};
+// G[dst[p] + a * ldg + b] = sum_i u[p]_ia v[p]_ib for p < npairs, one launch for all pairs (blockIdx.y) and one that adds the partials;
+// partial holds npairs * W * W * eig_grid(n, W) doubles.  Returns the number of partials per sum.
+int launch_gram_multi(int n, int W, int npairs, const GramPairs &prs, double *partial, double *G, int ldg, hipStream_t st);
+// R = AX - X * theta_c with theta in device memory, norms[c] = ||R_c||_2 (partial: W * eig_grid(n, W) doubles)
+void launch_eig_residual(int n, int W, const double *AX, const double *X, const double *theta, double *R, double *partial, double *norms,
+                         hipStream_t st);
+// the subspace update on the columns j < k, coef = Cx, Cw, Cp (W x W each, row-major, device memory), every sum over c < k ascending:
+//   P'_ij = sum_c W_ic Cw_cj, continued by + sum_c P_ic Cp_cj ;  X'_ij = (sum_c X_ic Cx_cj) + P'_ij ;  AP', AX' likewise from AW, AP, AX.
+// Columns j >= k are written as zeros.  An output may be the block it replaces.
+void launch_eig_update(int n, int W, int k, const double *X, const double *Wb, const double *P, const double *AX, const double *AW,
+                       const double *AP, const double *coef, double *Xo, double *Po, double *AXo, double *APo, hipStream_t st);
+
 }  // namespace sparsh
