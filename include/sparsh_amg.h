@@ -708,12 +708,14 @@ int sparsh_op_coarse_multi(sparsh_handle h, int nrhs, const double *B, double *X
 int sparsh_op_precond_multi(sparsh_handle h, int nrhs, const double *R, double *Z);
 /* average seconds of `reps` back-to-back block launches on the level's resident block buffers: op 0 = SpMV + dot, 1 = Jacobi
  * sweeps ping-ponging (the counterpart of sparsh_bench_op 10); on the eigensolver's resident blocks of width multi_width(nrhs)
- * (level 0 whatever `level` says; reserved by the call): op 2 = the twelve-pair Gram launch with its finalise, 3 = one update */
+ * (level 0 whatever `level` says; reserved by the call): op 2 = the twelve-pair Gram launch with its finalise, 3 = one update;
+ * with the generalised solver's blocks beside them (reserved by the call; SPARSH_ESTATE without a B): 4 = the generalised update,
+ * 5 = the block SpMV with B */
 int sparsh_bench_op_multi(sparsh_handle h, int op, int level, int nrhs, int reps, double *avg_seconds);
 
 /* ---- the lowest eigenpairs of the SPD level-0 operator by LOBPCG on the block path ----
- * nev <= SPARSH_MAX_RHS eigenpairs A x = lambda x with the smallest lambda, the block V-cycle as preconditioner.  Standard problem
- * only (no A x = lambda B x), SPD operators only, no null-space handles.  X is column-major, column c at X + c * ldx, ldx >= n: the
+ * nev <= SPARSH_MAX_RHS eigenpairs A x = lambda x with the smallest lambda, the block V-cycle as preconditioner.  The standard
+ * problem here, the generalised one A x = lambda B x in sparsh_eigs_gen below; SPD operators only, no null-space handles.  X is column-major, column c at X + c * ldx, ldx >= n: the
  * start block on entry (it must have full rank), the Ritz vectors on return, orthonormal and ordered by ascending lambda[c].
  * Notation: k = nev, W = the block width 2, 4 or 8 (k rounded up; padding columns hold zeros and are never active).
  *  1. start: AX = A X; Rayleigh-Ritz on the pencil (X^T AX, X^T X) gives theta and C; X <- X C, AX <- AX C; there is no P yet.
@@ -756,6 +758,39 @@ int sparsh_eigs(sparsh_handle h, int nev, double *X, long ldx, double tol, int m
 int sparsh_eigs_dev(sparsh_handle h, int nev, double *X_dev, long ldx, double tol, int max_iters, double *lambda, double *hist, int hist_cap,
                     int *iters, int *status, double *seconds);
 int sparsh_eig_info(sparsh_handle h, int *width, long *bytes, int *restarts);
+
+/* ---- the generalised problem A x = lambda B x ----
+ * sparsh_eig_set_b: B is n x n (n = the handle's rows), symmetric positive definite, 0-based CSR with sorted columns.  The arrays are
+ * copied to the device: the caller may free them.  rowptr == NULL drops B.  B lives until the next sparsh_setup, sparsh_destroy or
+ * sparsh_eig_set_b.  Arguments are checked first, on the host, with or without a device, SPARSH_EINVAL with a message that names
+ * the defect: a NULL colindex or val; rowptr[0] != 0 or rowptr not non-decreasing; a column out of range or not strictly ascending
+ * within its row; a value that is not finite; a row without a stored diagonal or with a diagonal <= 0; B not symmetric, which is some
+ * |b_ij - b_ji| > 1e-12 max|b| with a missing transpose entry counting as 0; a handle sparsh_solve_multi refuses.  Then
+ * SPARSH_ESTATE before sparsh_setup.  Positive definiteness beyond the diagonal is the caller's statement: an indefinite B surfaces as
+ * the Rayleigh-Ritz breakdown at the start.  sparsh_eig_b_info: whether a B is set, its stored entries and the device bytes it holds
+ * (all 0 without one).
+ * sparsh_eigs_gen / sparsh_eigs_gen_dev: the arguments, refusals, return codes and memory rules of sparsh_eigs / sparsh_eigs_dev, and
+ * SPARSH_ESTATE when no B is set.  They return the nev lowest pairs of A x = lambda B x, X B-orthonormal (X^T B X = I) and ordered
+ * by ascending lambda.  The steps are those above with B S = [BX, BW, BP] carried beside A S:
+ *  1. AX = A X and BX = B X; Rayleigh-Ritz on (X^T AX, X^T BX); X, AX, BX <- . C.
+ *  2. R = AX - BX diag(theta) (product and subtraction rounded separately); rn_c = ||R_c||_2 and bn_c = ||BX_c||_2 from one pass.
+ *     Column c is active when rn_c > tol |theta_c| bn_c, which no scaling of B changes and which is the rule above for B = I.  hist
+ *     stores rn_c.
+ *  3. W = M R; AW = A W and BW = B W by two block SpMVs.
+ *  4. S^T A S and S^T B S from the same Gram launch, the pairs (S_i, BS_j) in place of (S_i, S_j): twelve pairs, two at the start.
+ *     Both matrices and both norm vectors reach the host in the one pinned read (bn in the first row of the unused block below the
+ *     diagonal of S^T B S).
+ *  5. as above.
+ *  6. as above, and BP', BX' from BW, BP, BX with the same coefficients in the same pass (nine blocks in, six out).
+ * Memory: the blocks BX, BW, BP (n * W doubles each) are reserved at the first generalised call for a width, beside the seven blocks
+ * and small arrays of sparsh_eigs, and are counted in sparsh_eig_info from then on; until then sparsh_eigs, sparsh_eigs_dev and
+ * sparsh_eig_info keep their bits, launches and byte counts. */
+int sparsh_eig_set_b(sparsh_handle h, const int *rowptr, const int *colindex, const double *val);
+int sparsh_eig_b_info(sparsh_handle h, int *is_set, long *nnz, long *bytes);
+int sparsh_eigs_gen(sparsh_handle h, int nev, double *X, long ldx, double tol, int max_iters, double *lambda, double *hist, int hist_cap,
+                    int *iters, int *status);
+int sparsh_eigs_gen_dev(sparsh_handle h, int nev, double *X_dev, long ldx, double tol, int max_iters, double *lambda, double *hist,
+                        int hist_cap, int *iters, int *status, double *seconds);
 /* step 5 alone on a compacted pencil of order m <= 24 (row-major, upper triangles read): theta[k], C (m x k, row-major).  Returns
  * 0, or 1 for a breakdown.  Needs no handle and no device. */
 int sparsh_debug_eig_small(int m, int k, const double *GA, const double *GB, double *theta, double *C);
@@ -768,6 +803,15 @@ int sparsh_op_eig_residual(sparsh_handle h, int n, int k, const double *AX, cons
 int sparsh_op_eig_update(sparsh_handle h, int n, int k, const double *X, const double *W, const double *P, const double *AX, const double *AW,
                          const double *AP, const double *Cx, const double *Cw, const double *Cp, double *Xo, double *Po, double *AXo,
                          double *APo);
+/* The generalised solver's: eig_b_multi: Y = B X (n rows of the handle, nrhs columns) through the block SpMV on the stored B
+ * (SPARSH_ESTATE without one).  eig_residual_gen: R = AX - BX diag(theta), rnorms[c] = ||R_c||_2, bnorms[c] = ||BX_c||_2, any n > 0.
+ * eig_update_gen: step 6 on nine blocks; in = X, W, P, AX, AW, AP, BX, BW, BP and out = X', P', AX', AP', BX', BP'; an out[i] that is
+ * the array it replaces (in[0], in[2], in[3], in[5], in[6], in[8] in that order) is updated in place on the device too. */
+int sparsh_op_eig_b_multi(sparsh_handle h, int nrhs, const double *X, double *Y);
+int sparsh_op_eig_residual_gen(sparsh_handle h, int n, int k, const double *AX, const double *BX, const double *theta, double *R,
+                               double *rnorms, double *bnorms);
+int sparsh_op_eig_update_gen(sparsh_handle h, int n, int k, const double *const in[9], const double *Cx, const double *Cw, const double *Cp,
+                             double *const out[6]);
 
 /* device memory helpers so a host language needs no HIP binding of its own */
 int sparsh_dev_alloc(sparsh_handle h, long nbytes, void **out);

@@ -262,6 +262,14 @@ def _load():
         "sparsh_op_gram_multi": (C.c_int, [H, C.c_int, C.c_int, c_dbl_p, C.c_int, c_dbl_p, c_dbl_p]),
         "sparsh_op_eig_residual": (C.c_int, [H, C.c_int, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p]),
         "sparsh_op_eig_update": (C.c_int, [H, C.c_int, C.c_int] + [c_dbl_p] * 13),
+        "sparsh_eig_set_b": (C.c_int, [H, c_int_p, c_int_p, c_dbl_p]),
+        "sparsh_eig_b_info": (C.c_int, [H, c_int_p, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
+        "sparsh_eigs_gen": (C.c_int, [H, C.c_int, c_dbl_p, C.c_long, C.c_double, C.c_int, c_dbl_p, c_dbl_p, C.c_int, c_int_p, c_int_p]),
+        "sparsh_eigs_gen_dev": (C.c_int, [H, C.c_int, C.c_void_p, C.c_long, C.c_double, C.c_int, c_dbl_p, c_dbl_p, C.c_int, c_int_p, c_int_p,
+                                          c_dbl_p]),
+        "sparsh_op_eig_b_multi": (C.c_int, [H, C.c_int, c_dbl_p, c_dbl_p]),
+        "sparsh_op_eig_residual_gen": (C.c_int, [H, C.c_int, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p]),
+        "sparsh_op_eig_update_gen": (C.c_int, [H, C.c_int, C.c_int, C.POINTER(c_dbl_p), c_dbl_p, c_dbl_p, c_dbl_p, C.POINTER(c_dbl_p)]),
         "sparsh_op_gs_dot": (C.c_int, [H, C.c_int, C.c_int, C.c_int, c_dbl_p, c_dbl_p, C.c_int, c_dbl_p]),
         "sparsh_op_gs_update": (C.c_int, [H, C.c_int, C.c_int, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p, C.c_int, C.c_int, C.c_int, C.c_double,
                                           c_dbl_p, c_dbl_p, c_dbl_p, c_int_p]),
@@ -1315,6 +1323,9 @@ class sp_matrix_mg:
         .standard_normal((n, k))).  Returns (lam, X, iters, hist, status): lam ascending, X (n, k) orthonormal Ritz vectors, iters[c] the
         iterations column c was active in, hist (k, evaluations) with hist[c, it] = ||A x_c - lam_c x_c|| at the start of iteration
         it, status[c] SPARSH_OK or SPARSH_ENOCONV (the cap; the code of the call is kept in last_eigs_rc).  Other codes raise."""
+        return self._eigs(lib.sparsh_eigs, k, X0, tol, max_iters, seed, hist_cap)
+
+    def _eigs(self, fn, k, X0, tol, max_iters, seed, hist_cap):
         k = int(k)
         if X0 is None:
             X0 = np.random.default_rng(seed).standard_normal((self.nrow, max(k, 0)))
@@ -1324,20 +1335,23 @@ class sp_matrix_mg:
         kk = max(k, 1)
         lam, hist = np.zeros(kk), np.full((kk, hist_cap), np.nan)
         iters, status = np.zeros(kk, dtype=np.int32), np.zeros(kk, dtype=np.int32)
-        self.last_eigs_rc = _check(lib.sparsh_eigs(self._h, k, _dp(Xf), max(Xf.shape[0], 1), float(tol), int(max_iters), _dp(lam), _dp(hist),
-                                                   hist_cap, _ip(iters), _ip(status)), allow=(SPARSH_ENOCONV,))
+        self.last_eigs_rc = _check(fn(self._h, k, _dp(Xf), max(Xf.shape[0], 1), float(tol), int(max_iters), _dp(lam), _dp(hist), hist_cap,
+                                      _ip(iters), _ip(status)), allow=(SPARSH_ENOCONV,))
         nev = int(np.count_nonzero(~np.isnan(hist[0])))
         return lam[:k].copy(), Xf, iters[:k].copy(), hist[:k, :nev].copy(), status[:k].copy()
 
     def eigs_dev(self, k, X_dev, ldx, tol=1e-8, max_iters=0, hist_cap=1024):
         """The same on a column-major device array (dev_alloc / h2d): the start block in, the Ritz vectors out.  Returns
         (lam, iters, hist, status, seconds, rc)."""
+        return self._eigs_dev(lib.sparsh_eigs_dev, k, X_dev, ldx, tol, max_iters, hist_cap)
+
+    def _eigs_dev(self, fn, k, X_dev, ldx, tol, max_iters, hist_cap):
         kk = max(int(k), 1)
         lam, hist = np.zeros(kk), np.full((kk, hist_cap), np.nan)
         iters, status = np.zeros(kk, dtype=np.int32), np.zeros(kk, dtype=np.int32)
         sec = C.c_double()
-        rc = _check(lib.sparsh_eigs_dev(self._h, int(k), X_dev, ldx, float(tol), int(max_iters), _dp(lam), _dp(hist), hist_cap, _ip(iters),
-                                        _ip(status), C.byref(sec)), allow=(SPARSH_ENOCONV,))
+        rc = _check(fn(self._h, int(k), X_dev, ldx, float(tol), int(max_iters), _dp(lam), _dp(hist), hist_cap, _ip(iters), _ip(status),
+                       C.byref(sec)), allow=(SPARSH_ENOCONV,))
         nev = int(np.count_nonzero(~np.isnan(hist[0])))
         return lam[:k].copy(), iters[:k].copy(), hist[:k, :nev].copy(), status[:k].copy(), sec.value, rc
 
@@ -1347,6 +1361,68 @@ class sp_matrix_mg:
         w, b, r = C.c_int(), C.c_long(), C.c_int()
         _check(lib.sparsh_eig_info(self._h, C.byref(w), C.byref(b), C.byref(r)))
         return dict(width=w.value, bytes=b.value, restarts=r.value)
+
+    # -- the generalised problem A x = lambda B x ---------------------------------------------------------------
+    def set_eig_b(self, rowptr, col=None, val=None):
+        """The SPD matrix B of the generalised problem as 0-based CSR with sorted columns (copied to the device); None drops it.  B lives
+        until the next setup, close or set_eig_b."""
+        if rowptr is None:
+            _check(lib.sparsh_eig_set_b(self._h, None, None, None))
+            return self
+        rp = np.ascontiguousarray(rowptr, dtype=np.int32)
+        if col is None or val is None:  # (the library's refusal and its message)
+            _check(lib.sparsh_eig_set_b(self._h, _ip(rp), None, None))
+        ci, v = np.ascontiguousarray(col, dtype=np.int32), np.ascontiguousarray(val, dtype=np.float64)
+        if len(rp) != self.nrow + 1 or len(ci) != len(v) or (len(rp) and rp[-1] > len(ci)):
+            raise ValueError("B must have the handle's number of rows, and rowptr[-1] entries in col and val")
+        _check(lib.sparsh_eig_set_b(self._h, _ip(rp), _ip(ci), _dp(v)))
+        return self
+
+    def eig_b_info(self):
+        """Whether a B is set, its stored entries and the device bytes it holds (all 0 without one)."""
+        s, nnz, b = C.c_int(), C.c_long(), C.c_long()
+        _check(lib.sparsh_eig_b_info(self._h, C.byref(s), C.byref(nnz), C.byref(b)))
+        return dict(is_set=bool(s.value), nnz=nnz.value, bytes=b.value)
+
+    def eigs_gen(self, k, X0=None, tol=1e-8, max_iters=0, seed=0, hist_cap=1024):
+        """The k <= 8 lowest eigenpairs of A x = lam B x with the B of set_eig_b.  Arguments and results are those of eigs; X is
+        B-orthonormal and hist[c, it] = ||A x_c - lam_c B x_c||."""
+        return self._eigs(lib.sparsh_eigs_gen, k, X0, tol, max_iters, seed, hist_cap)
+
+    def eigs_gen_dev(self, k, X_dev, ldx, tol=1e-8, max_iters=0, hist_cap=1024):
+        """eigs_dev for the generalised problem."""
+        return self._eigs_dev(lib.sparsh_eigs_gen_dev, k, X_dev, ldx, tol, max_iters, hist_cap)
+
+    def op_eig_b_multi(self, X):
+        """Y = B X through the block SpMV on the stored B."""
+        Xf = self._block(X, self.nrow)
+        Y = np.zeros_like(Xf, order="F")
+        _check(lib.sparsh_op_eig_b_multi(self._h, Xf.shape[1], _dp(Xf), _dp(Y)))
+        return Y
+
+    def op_eig_residual_gen(self, AX, BX, theta):
+        """(R, rnorms, bnorms): R = AX - BX * theta, the column norms of R and those of BX, through the generalised residual kernel."""
+        Af, Bf = self._block(AX), self._block(BX, np.shape(AX)[0])
+        th = np.ascontiguousarray(theta, dtype=np.float64)
+        R, rn, bn = np.zeros_like(Af, order="F"), np.zeros(Af.shape[1]), np.zeros(Af.shape[1])
+        _check(lib.sparsh_op_eig_residual_gen(self._h, Af.shape[0], Af.shape[1], _dp(Af), _dp(Bf), _dp(th), _dp(R), _dp(rn), _dp(bn)))
+        return R, rn, bn
+
+    def op_eig_update_gen(self, blocks, Cx, Cw, Cp, in_place=False):
+        """(X', P', AX', AP', BX', BP') of the generalised update kernel from blocks = (X, W, P, AX, AW, AP, BX, BW, BP); in_place: every
+        output replaces its block on the device."""
+        n = np.shape(blocks[0])[0]
+        blocks = [self._block(b, n) for b in blocks]
+        if len(blocks) != 9:
+            raise ValueError("nine blocks: X, W, P, AX, AW, AP, BX, BW, BP")
+        k = blocks[0].shape[1]
+        cs = [np.ascontiguousarray(c, dtype=np.float64) for c in (Cx, Cw, Cp)]
+        if any(c.shape != (k, k) for c in cs):
+            raise ValueError("the coefficient matrices are k x k")
+        outs = [blocks[i] for i in (0, 2, 3, 5, 6, 8)] if in_place else [np.zeros_like(blocks[0], order="F") for _ in range(6)]
+        pin, pout = (c_dbl_p * 9)(*[_dp(b) for b in blocks]), (c_dbl_p * 6)(*[_dp(o) for o in outs])
+        _check(lib.sparsh_op_eig_update_gen(self._h, n, k, pin, *[_dp(c) for c in cs], pout))
+        return tuple(outs)
 
     def op_gram_multi(self, U, V):
         """G = U^T V (nu x nv) through the Gram launch of the eigensolver; U (n, nu), V (n, nv), any n > 0."""
@@ -1377,8 +1453,9 @@ class sp_matrix_mg:
 
     def bench_op_multi(self, op, level=0, nrhs=8, reps=20):
         """Average seconds of one block launch on the level's resident block buffers: "spmv_dot" (0) or "jacobi_pingpong_resident" (1);
-        on the eigensolver's resident blocks: "eig_gram" (2, the twelve-pair Gram launch with its finalise) or "eig_update" (3)."""
-        ops = {"spmv_dot": 0, "jacobi_pingpong_resident": 1, "eig_gram": 2, "eig_update": 3}
+        on the eigensolver's resident blocks: "eig_gram" (2, the twelve-pair Gram launch with its finalise) or "eig_update" (3); with
+        the generalised solver's blocks and a B set: "eig_update_gen" (4) or "eig_b_spmv" (5)."""
+        ops = {"spmv_dot": 0, "jacobi_pingpong_resident": 1, "eig_gram": 2, "eig_update": 3, "eig_update_gen": 4, "eig_b_spmv": 5}
         sec = C.c_double()
         _check(lib.sparsh_bench_op_multi(self._h, ops[op] if isinstance(op, str) else op, int(level), int(nrhs), int(reps), C.byref(sec)))
         return sec.value

@@ -2212,14 +2212,16 @@ int sparsh_op_precond_multi(sparsh_handle h, int nrhs, const double *R, double *
 int sparsh_bench_op_multi(sparsh_handle h, int op, int level, int nrhs, int reps, double *avg_seconds)
 {
     REQUIRE_MULTI_ARGS(h, nrhs);
-    if (op < 0 || op > 3) return fail(SPARSH_EINVAL, "unknown op");
+    if (op < 0 || op > 5) return fail(SPARSH_EINVAL, "unknown op");
     if (reps <= 0 || !avg_seconds) return fail(SPARSH_EINVAL, "bad reps");
     REQUIRE_READY(h);
     REQUIRE_SINGLE(h);
     REQUIRE_LEVEL(h, level);
     Engine &E = *h->eng;
     const bool eig = op >= 2;  // the eigensolver's launches run on its own resident blocks (level 0)
-    if (int rc = eig ? E.eig_reserve(nrhs) : E.multi_reserve(nrhs); rc != SPARSH_OK) return fail(rc, E.error);
+    const bool gen = op >= 4;  // 4, 5: the generalised solver's blocks beside them, and its B
+    if (gen && !E.eig_b_set()) return fail(SPARSH_ESTATE, "sparsh_eig_set_b has not been called");
+    if (int rc = gen ? E.eig_reserve_gen(nrhs) : (eig ? E.eig_reserve(nrhs) : E.multi_reserve(nrhs)); rc != SPARSH_OK) return fail(rc, E.error);
     hipStream_t st = E.stream();
     auto launch = [&]() { return eig ? E.bench_eig_launch(op) : E.bench_multi_launch(op, level); };
     for (int i = 0; i < 3; ++i) launch();
@@ -2261,22 +2263,116 @@ int sparsh_eigs_dev(sparsh_handle h, int nev, double *X_dev, long ldx, double to
     return rc;
 }
 
-int sparsh_eigs(sparsh_handle h, int nev, double *X, long ldx, double tol, int max_iters, double *lambda, double *hist, int hist_cap,
-                int *iters, int *status)
+namespace {
+
+// sparsh_eigs and sparsh_eigs_gen on host arrays
+int eigs_host(sparsh_handle h, bool gen, int nev, double *X, long ldx, double tol, int max_iters, double *lambda, double *hist, int hist_cap,
+              int *iters, int *status)
 {
     REQUIRE_EIG_ARGS(h, nev, X, ldx, tol, lambda, hist, hist_cap, iters, status);
     REQUIRE_READY(h);
     Engine &E = *h->eng;
+    if (gen && !E.eig_b_set()) return fail(SPARSH_ESTATE, "sparsh_eig_set_b has not been called: the generalised problem needs its B");
     const size_t n = (size_t)E.n0();
     DBuf dx(E, n * nev);  // packed (leading dimension n): only the n rows of every column travel
     if (!dx.p) return fail(SPARSH_ENODEV, E.error);
     for (int c = 0; c < nev; ++c) (void)hipMemcpy(dx.p + (size_t)c * n, X + (size_t)c * ldx, n * 8, hipMemcpyHostToDevice);
-    int rc = E.eigs_dev(nev, dx.p, (long)n, tol, max_iters, lambda, hist, hist_cap, iters, status, nullptr);
+    int rc = gen ? E.eigs_gen_dev(nev, dx.p, (long)n, tol, max_iters, lambda, hist, hist_cap, iters, status, nullptr)
+                 : E.eigs_dev(nev, dx.p, (long)n, tol, max_iters, lambda, hist, hist_cap, iters, status, nullptr);
     (void)hipStreamSynchronize(E.stream());
     if (rc == SPARSH_OK || rc == SPARSH_ENOCONV)
         for (int c = 0; c < nev; ++c) (void)hipMemcpy(X + (size_t)c * ldx, dx.p + (size_t)c * n, n * 8, hipMemcpyDeviceToHost);
     if (rc != SPARSH_OK) return fail(rc, E.error);
     return rc;
+}
+
+}  // namespace
+
+int sparsh_eigs(sparsh_handle h, int nev, double *X, long ldx, double tol, int max_iters, double *lambda, double *hist, int hist_cap,
+                int *iters, int *status)
+{
+    return eigs_host(h, false, nev, X, ldx, tol, max_iters, lambda, hist, hist_cap, iters, status);
+}
+
+// ---- the generalised problem A x = lambda B x ----
+
+namespace {
+
+// what sparsh_eig_set_b refuses in B itself (nullptr: nothing); host only
+const char *eig_b_defect(int n, const int *rp, const int *ci, const double *v)
+{
+    if (rp[0] != 0) return "B: rowptr[0] must be 0";
+    for (int i = 0; i < n; ++i)
+        if (rp[i + 1] < rp[i]) return "B: rowptr must be non-decreasing";
+    double vmax = 0.0;
+    for (int i = 0; i < n; ++i) {
+        bool diag = false;
+        for (int p = rp[i]; p < rp[i + 1]; ++p) {
+            if (ci[p] < 0 || ci[p] >= n) return "B: column index out of range";
+            if (p > rp[i] && ci[p] <= ci[p - 1]) return "B: the columns of a row must be strictly ascending";
+            if (!std::isfinite(v[p])) return "B: a value is not finite";
+            vmax = std::max(vmax, std::fabs(v[p]));
+            if (ci[p] == i) {
+                diag = true;
+                if (!(v[p] > 0.0)) return "B: a diagonal entry is not positive";
+            }
+        }
+        if (!diag) return "B: a row has no stored diagonal entry";
+    }
+    const double bound = 1e-12 * vmax;
+    for (int i = 0; i < n; ++i)
+        for (int p = rp[i]; p < rp[i + 1]; ++p) {
+            const int j = ci[p];
+            if (j == i) continue;
+            const int *lo = ci + rp[j], *hi = ci + rp[j + 1];
+            const int *q = std::lower_bound(lo, hi, i);
+            const double t = (q != hi && *q == i) ? v[q - ci] : 0.0;  // a missing transpose entry counts as 0
+            if (std::fabs(v[p] - t) > bound) return "B is not symmetric: some |b_ij - b_ji| > 1e-12 max|b|";
+        }
+    return nullptr;
+}
+
+}  // namespace
+
+int sparsh_eig_set_b(sparsh_handle h, const int *rowptr, const int *colindex, const double *val)
+{
+    if (!h || !h->eng) return fail(SPARSH_EINVAL, "null handle");
+    Engine &E = *h->eng;
+    if (!rowptr) {  // drop B: nothing to check, and nothing to drop before a setup
+        if (E.eig_b_set()) (void)E.eig_set_b(nullptr, nullptr, nullptr);
+        return SPARSH_OK;
+    }
+    if (!colindex || !val) return fail(SPARSH_EINVAL, "B: NULL colindex or val with a rowptr");
+    if (const char *why = eig_b_defect(E.n0(), rowptr, colindex, val)) return fail(SPARSH_EINVAL, why);
+    REQUIRE_MULTI_FITS(h);
+    REQUIRE_READY(h);
+    if (int rc = E.eig_set_b(rowptr, colindex, val); rc != SPARSH_OK) return fail(rc, E.error);
+    return SPARSH_OK;
+}
+
+int sparsh_eig_b_info(sparsh_handle h, int *is_set, long *nnz, long *bytes)
+{
+    if (!h || !h->eng) return fail(SPARSH_EINVAL, "null handle");
+    if (is_set) *is_set = h->eng->eig_b_set() ? 1 : 0;
+    if (nnz) *nnz = h->eng->eig_b_nnz();
+    if (bytes) *bytes = (long)h->eng->eig_b_bytes();
+    return SPARSH_OK;
+}
+
+int sparsh_eigs_gen_dev(sparsh_handle h, int nev, double *X_dev, long ldx, double tol, int max_iters, double *lambda, double *hist,
+                        int hist_cap, int *iters, int *status, double *seconds)
+{
+    REQUIRE_EIG_ARGS(h, nev, X_dev, ldx, tol, lambda, hist, hist_cap, iters, status);
+    REQUIRE_READY(h);
+    int rc = h->eng->eigs_gen_dev(nev, X_dev, ldx, tol, max_iters, lambda, hist, hist_cap, iters, status, seconds);
+    if (rc != SPARSH_OK) return fail(rc, h->eng->error);
+    return rc;
+}
+
+int sparsh_eigs_gen(sparsh_handle h, int nev, double *X, long ldx, double tol, int max_iters, double *lambda, double *hist, int hist_cap,
+                    int *iters, int *status)
+{
+    return eigs_host(h, true, nev, X, ldx, tol, max_iters, lambda, hist, hist_cap, iters, status);
 }
 
 int sparsh_eig_info(sparsh_handle h, int *width, long *bytes, int *restarts)
@@ -2390,6 +2486,95 @@ int sparsh_op_eig_update(sparsh_handle h, int n, int k, const double *X, const d
     if (!ok) return fail(SPARSH_ENODEV, "device allocation or H2D copy failed");
     launch_eig_update(n, Wd, k, bi[0]->p, bi[1]->p, bi[2]->p, bi[3]->p, bi[4]->p, bi[5]->p, dcoef.p, dst[0], dst[1], dst[2], dst[3], E.stream());
     for (int o = 0; o < 4 && ok; ++o) {
+        launch_deinterleave(n, k, Wd, dst[o], stage.p, n, E.stream());
+        ok = stage.get(out[o]);
+    }
+    return done(E, ok);
+}
+
+int sparsh_op_eig_b_multi(sparsh_handle h, int nrhs, const double *X, double *Y)
+{
+    REQUIRE_MULTI_ARGS(h, nrhs);
+    if (!X || !Y) return fail(SPARSH_EINVAL, "NULL array");
+    REQUIRE_READY(h);
+    REQUIRE_SINGLE(h);
+    Engine &E = *h->eng;
+    if (!E.eig_b_set()) return fail(SPARSH_ESTATE, "sparsh_eig_set_b has not been called");
+    const size_t cm = (size_t)E.n0() * nrhs;
+    DBuf dx(E, cm, X), dy(E, cm);
+    if (!dx.p || !dy.p) return fail(SPARSH_ENODEV, "device allocation or H2D copy failed");
+    if (int rc = E.op_eig_b_multi(nrhs, dx.p, dy.p); rc != SPARSH_OK) return fail(rc, E.error);
+    return done(E, dy.get(Y));
+}
+
+int sparsh_op_eig_residual_gen(sparsh_handle h, int n, int k, const double *AX, const double *BX, const double *theta, double *R,
+                               double *rnorms, double *bnorms)
+{
+    REQUIRE_EIG_OP(h, n);
+    if (k < 1 || k > SPARSH_MAX_RHS) return fail(SPARSH_EINVAL, "k must be 1 .. SPARSH_MAX_RHS (8)");
+    if (!AX || !BX || !theta || !R || !rnorms || !bnorms) return fail(SPARSH_EINVAL, "NULL array");
+    Engine &E = *h->eng;
+    const int W = multi_width(k);
+    const size_t len = (size_t)n * W;
+    std::vector<double> th(W, 0.0), bn(W, 0.0);
+    std::copy(theta, theta + k, th.begin());
+    DBuf dax(E, (size_t)n * k, AX), dbx(E, (size_t)n * k, BX), bax(E, len), bbx(E, len), br(E, len), dth(E, (size_t)W, th.data()),
+        part(E, (size_t)2 * W * eig_grid(n, W)), drn(E, (size_t)W), dbn(E, (size_t)W), dr(E, (size_t)n * k);
+    if (!dax.p || !dbx.p || !bax.p || !bbx.p || !br.p || !dth.p || !part.p || !drn.p || !dbn.p || !dr.p)
+        return fail(SPARSH_ENODEV, "device allocation or H2D copy failed");
+    launch_interleave(n, k, W, dax.p, n, bax.p, E.stream());
+    launch_interleave(n, k, W, dbx.p, n, bbx.p, E.stream());
+    launch_eig_residual_gen(n, W, bax.p, bbx.p, dth.p, br.p, part.p, drn.p, dbn.p, E.stream());
+    launch_deinterleave(n, k, W, br.p, dr.p, n, E.stream());
+    if (!dr.get(R) || !drn.get(th.data()) || !dbn.get(bn.data())) return done(E, false);
+    std::copy(th.begin(), th.begin() + k, rnorms);
+    std::copy(bn.begin(), bn.begin() + k, bnorms);
+    return done(E, true);
+}
+
+int sparsh_op_eig_update_gen(sparsh_handle h, int n, int k, const double *const in[9], const double *Cx, const double *Cw, const double *Cp,
+                             double *const out[6])
+{
+    REQUIRE_EIG_OP(h, n);
+    if (k < 1 || k > SPARSH_MAX_RHS) return fail(SPARSH_EINVAL, "k must be 1 .. SPARSH_MAX_RHS (8)");
+    if (!in || !out || !Cx || !Cw || !Cp) return fail(SPARSH_EINVAL, "NULL array");
+    for (int i = 0; i < 9; ++i)
+        if (!in[i]) return fail(SPARSH_EINVAL, "NULL array");
+    for (int o = 0; o < 6; ++o)
+        if (!out[o]) return fail(SPARSH_EINVAL, "NULL array");
+    Engine &E = *h->eng;
+    const int Wd = multi_width(k);
+    const size_t len = (size_t)n * Wd, cm = (size_t)n * k;
+    const int replaces[6] = {0, 2, 3, 5, 6, 8};
+    std::vector<double> coef(3 * (size_t)Wd * Wd, 0.0);
+    const double *cs[3] = {Cx, Cw, Cp};
+    for (int m = 0; m < 3; ++m)
+        for (int a = 0; a < k; ++a)
+            for (int b = 0; b < k; ++b) coef[(size_t)m * Wd * Wd + a * Wd + b] = cs[m][a * k + b];
+    DBuf stage(E, cm), dcoef(E, coef.size(), coef.data());
+    std::vector<std::unique_ptr<DBuf>> bi, bo;
+    bool ok = stage.p && dcoef.p;
+    for (int i = 0; i < 9 && ok; ++i) {
+        bi.emplace_back(new DBuf(E, len));
+        ok = bi.back()->p && hipMemcpy(stage.p, in[i], cm * 8, hipMemcpyHostToDevice) == hipSuccess;
+        if (ok) launch_interleave(n, k, Wd, stage.p, n, bi.back()->p, E.stream());
+        if (ok) ok = hipStreamSynchronize(E.stream()) == hipSuccess;
+    }
+    const double *src[9] = {nullptr};
+    double *dst[6] = {nullptr};
+    for (int i = 0; i < 9 && ok; ++i) src[i] = bi[i]->p;
+    for (int o = 0; o < 6 && ok; ++o) {
+        if (out[o] == in[replaces[o]]) {
+            dst[o] = bi[replaces[o]]->p;
+        } else {
+            bo.emplace_back(new DBuf(E, len));
+            ok = bo.back()->p != nullptr;
+            dst[o] = bo.back()->p;
+        }
+    }
+    if (!ok) return fail(SPARSH_ENODEV, "device allocation or H2D copy failed");
+    launch_eig_update_gen(n, Wd, k, src, dcoef.p, dst, E.stream());
+    for (int o = 0; o < 6 && ok; ++o) {
         launch_deinterleave(n, k, Wd, dst[o], stage.p, n, E.stream());
         ok = stage.get(out[o]);
     }

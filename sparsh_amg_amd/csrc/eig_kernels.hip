@@ -149,6 +149,78 @@ __global__ __launch_bounds__(kMultiMax * 64) void eig_norm_finalize_kernel(int W
     if (lane == 0) out[c] = sqrt(v);
 }
 
+// ------------------------------------------------------------------ residual of the pencil (A, B)
+
+// R = AX - BX * theta_c (two roundings); rr[c * nblk + j] and bb[c * nblk + j] = the shares of R_c . R_c and BX_c . BX_c, nblk =
+// eig_grid(n, W) = gridDim.x * 2 (rounded up).  A lane owns two neighbouring columns of one row (16-byte accesses).  The sums are those
+// of eig_residual_kernel, bit for bit: with B = I the two solvers see the same residual norms.  There thread t of workgroup j adds the
+// elements (j + m * nblk) * 256 + t, m ascending; here one half of a workgroup (128 lanes) stands for workgroup j = 2 * blockIdx.x +
+// half, and its lane q holds the sums of t = 2 q and 2 q + 1 in the two components.  A 64-row wave of that kernel is 32 lanes here,
+// so its butterfly over t ^ 32 ... t ^ W is the one over q ^ 16 ... q ^ (W / 2), and its four waves are added in the same order.
+template <int W>
+__global__ __launch_bounds__(kBlock) void eig_residual_gen_kernel(int n, int nblk, const double *__restrict__ AX, const double *__restrict__ BX,
+                                                                   const double *__restrict__ theta, double *__restrict__ R,
+                                                                   double *__restrict__ rr, double *__restrict__ bb)
+{
+    constexpr int HALF = kBlock / 2;  // lanes that stand for one workgroup of eig_residual_kernel
+    __shared__ double red[2][2][HALF / 32][kMultiMax];  // quantity, half, 32-lane group, column
+    const int half = threadIdx.x / HALF, q = threadIdx.x % HALF;
+    const int j = 2 * blockIdx.x + half;
+    const int col = (2 * q) % W;
+    const d2e th = {theta[col], theta[col + 1]};
+    const size_t total = (size_t)n * W;  // even: a pair never straddles the end
+    d2e acc = {0.0, 0.0}, bacc = {0.0, 0.0};
+    if (j < nblk) {
+        for (size_t i = (size_t)j * kBlock + 2 * q; i < total; i += (size_t)nblk * kBlock) {
+            const d2e bx = *reinterpret_cast<const d2e *>(BX + i);
+            const d2e ax = *reinterpret_cast<const d2e *>(AX + i);
+            const d2e t = bx * th;
+            const d2e r = ax - t;
+            *reinterpret_cast<d2e *>(R + i) = r;
+            acc += r * r;
+            bacc += bx * bx;
+        }
+    }
+#pragma unroll
+    for (int off = 16; off >= W / 2; off >>= 1) {
+        acc.x += __shfl_xor(acc.x, off, 64);
+        acc.y += __shfl_xor(acc.y, off, 64);
+        bacc.x += __shfl_xor(bacc.x, off, 64);
+        bacc.y += __shfl_xor(bacc.y, off, 64);
+    }
+    const int l32 = q & 31, g32 = q >> 5;
+    if (l32 < W / 2) {
+        red[0][half][g32][2 * l32] = acc.x;
+        red[0][half][g32][2 * l32 + 1] = acc.y;
+        red[1][half][g32][2 * l32] = bacc.x;
+        red[1][half][g32][2 * l32 + 1] = bacc.y;
+    }
+    __syncthreads();
+    if (threadIdx.x < 4 * W) {
+        const int what = threadIdx.x / (2 * W), hh = (threadIdx.x / W) % 2, c = threadIdx.x % W;
+        double s = 0.0;
+#pragma unroll
+        for (int k = 0; k < HALF / 32; ++k) s += red[what][hh][k][c];
+        const int jj = 2 * blockIdx.x + hh;
+        if (jj < nblk) (what ? bb : rr)[(size_t)c * nblk + jj] = s;
+    }
+}
+
+// blockIdx.x = 0: out0[c] = sqrt of the sum of column c's partials in p0; 1: out1 from p1.  One wave per column, the order of
+// eig_norm_finalize_kernel.
+__global__ __launch_bounds__(kMultiMax * 64) void eig_norm2_finalize_kernel(int W, const double *__restrict__ p0, const double *__restrict__ p1, int nblk,
+                                                                             double *__restrict__ out0, double *__restrict__ out1)
+{
+    const double *__restrict__ partial = blockIdx.x ? p1 : p0;
+    double *__restrict__ out = blockIdx.x ? out1 : out0;
+    const int lane = threadIdx.x & 63, c = threadIdx.x >> 6;
+    if (c >= W) return;
+    double v = 0.0;
+    for (int i = lane; i < nblk; i += 64) v += partial[(size_t)c * nblk + i];
+    v = eig_wave_sum_down(v);
+    if (lane == 0) out[c] = sqrt(v);
+}
+
 // ------------------------------------------------------------------ update
 
 // the two entries j, j + 1 of sum_{c < k} B_ic C_cj, c ascending, continuing the running sum `acc` (first: the sum starts with the
@@ -208,6 +280,47 @@ __global__ __launch_bounds__(kBlock) void eig_update_kernel(int n, int k, const 
     }
 }
 
+// eig_update_kernel with B S carried along: BP' = BW Cw + BP Cp ; BX' = BX Cx + BP' with the same coefficients and the same order of
+// sums.  Nine blocks in, six out; all loads of a row come before its stores, so an output may be the block it replaces.
+template <int W>
+__global__ __launch_bounds__(kBlock) void eig_update_gen_kernel(int n, int k, const double *X, const double *Wb, const double *P, const double *AX,
+                                                                 const double *AW, const double *AP, const double *BX, const double *BW,
+                                                                 const double *BP, const double *__restrict__ coef, double *Xo, double *Po,
+                                                                 double *AXo, double *APo, double *BXo, double *BPo)
+{
+    constexpr int LPR = W / 2;
+    constexpr int RP = kBlock / LPR;
+    __shared__ __attribute__((aligned(16))) double sc[3 * W * W];  // Cx, Cw, Cp
+    for (int i = threadIdx.x; i < 3 * W * W; i += kBlock) sc[i] = coef[i];
+    __syncthreads();
+    const double *cx = sc, *cw = sc + W * W, *cp = sc + 2 * W * W;
+    const int j = 2 * (threadIdx.x % LPR);
+    const d2e zero = {0.0, 0.0};
+    for (size_t row = (size_t)blockIdx.x * RP + threadIdx.x / LPR; row < (size_t)n; row += (size_t)gridDim.x * RP) {
+        const size_t base = row * W;
+        d2e p = eig_row_times<W>(Wb, base, cw, j, k, zero, true);
+        p = eig_row_times<W>(P, base, cp, j, k, p, false);
+        d2e ap = eig_row_times<W>(AW, base, cw, j, k, zero, true);
+        ap = eig_row_times<W>(AP, base, cp, j, k, ap, false);
+        d2e bp = eig_row_times<W>(BW, base, cw, j, k, zero, true);
+        bp = eig_row_times<W>(BP, base, cp, j, k, bp, false);
+        d2e x = eig_row_times<W>(X, base, cx, j, k, zero, true);
+        d2e ax = eig_row_times<W>(AX, base, cx, j, k, zero, true);
+        d2e bx = eig_row_times<W>(BX, base, cx, j, k, zero, true);
+        x = x + p;
+        ax = ax + ap;
+        bx = bx + bp;
+        if (j >= k) x = ax = bx = p = ap = bp = zero;
+        else if (j + 1 >= k) x.y = ax.y = bx.y = p.y = ap.y = bp.y = 0.0;
+        *reinterpret_cast<d2e *>(Po + base + j) = p;
+        *reinterpret_cast<d2e *>(APo + base + j) = ap;
+        *reinterpret_cast<d2e *>(BPo + base + j) = bp;
+        *reinterpret_cast<d2e *>(Xo + base + j) = x;
+        *reinterpret_cast<d2e *>(AXo + base + j) = ax;
+        *reinterpret_cast<d2e *>(BXo + base + j) = bx;
+    }
+}
+
 }  // namespace
 
 #define EIG_DISPATCH(W, CALL) \
@@ -250,6 +363,23 @@ void launch_eig_update(int n, int W, int k, const double *X, const double *Wb, c
     const long passes = ((long)n + kBlock / (W / 2) - 1) / (kBlock / (W / 2));
     const int g = passes < 1 ? 1 : (passes > kEigUpdateMaxGrid ? kEigUpdateMaxGrid : (int)passes);
     EIG_DISPATCH(W, hipLaunchKernelGGL(eig_update_kernel<kW>, dim3(g), dim3(kBlock), 0, st, n, k, X, Wb, P, AX, AW, AP, coef, Xo, Po, AXo, APo));
+}
+
+void launch_eig_residual_gen(int n, int W, const double *AX, const double *BX, const double *theta, double *R, double *partial, double *rnorms,
+                             double *bnorms, hipStream_t st)
+{
+    const int g = eig_grid(n, W);
+    double *rr = partial, *bb = partial + (size_t)W * g;
+    EIG_DISPATCH(W, hipLaunchKernelGGL(eig_residual_gen_kernel<kW>, dim3((g + 1) / 2), dim3(kBlock), 0, st, n, g, AX, BX, theta, R, rr, bb));
+    hipLaunchKernelGGL(eig_norm2_finalize_kernel, dim3(2), dim3(kMultiMax * 64), 0, st, W, rr, bb, g, rnorms, bnorms);
+}
+
+void launch_eig_update_gen(int n, int W, int k, const double *const in[9], const double *coef, double *const out[6], hipStream_t st)
+{
+    const long passes = ((long)n + kBlock / (W / 2) - 1) / (kBlock / (W / 2));  // the grid of launch_eig_update
+    const int g = passes < 1 ? 1 : (passes > kEigUpdateMaxGrid ? kEigUpdateMaxGrid : (int)passes);
+    EIG_DISPATCH(W, hipLaunchKernelGGL(eig_update_gen_kernel<kW>, dim3(g), dim3(kBlock), 0, st, n, k, in[0], in[1], in[2], in[3], in[4], in[5], in[6],
+                                       in[7], in[8], coef, out[0], out[1], out[2], out[3], out[4], out[5]));
 }
 
 }  // namespace sparsh

@@ -61,6 +61,7 @@ void *Engine::dalloc(size_t bytes)
     if (bytes == 0) bytes = 8;
     if (!check(hipMalloc(&p, bytes), "hipMalloc")) return nullptr;
     allocs_.push_back(p);
+    dalloc_total_ += bytes;
     return p;
 }
 
@@ -485,6 +486,39 @@ bool upload_csr(Engine &E, const HostCsr &A, DevCsr &D, bool with_sell, const st
     }
     return true;
 }
+
+}  // namespace
+
+void Engine::eig_b_forget()
+{
+    eB_ = DevCsr();
+    eb_set_ = false;
+    eb_bytes_ = 0;
+    eb_allocs_.clear();
+}
+
+int Engine::eig_set_b(const int *rowptr, const int *col, const double *val)
+{
+    if (st_ && !eb_allocs_.empty()) (void)hipStreamSynchronize(st_);
+    for (void *p : eb_allocs_) dfree(p);
+    eig_b_forget();
+    if (!rowptr) return SPARSH_OK;
+    const int n = lev_[0].n;
+    const HostCsr B = HostCsr::alias(n, n, rowptr, col, val);
+    const size_t mark = allocs_.size(), bytes0 = dalloc_total_;
+    const bool ok = upload_csr(*this, B, eB_, false);  // the block path reads rowptr / col / val and the row-block records only
+    eb_allocs_.assign(allocs_.begin() + (long)mark, allocs_.end());
+    eb_bytes_ = dalloc_total_ - bytes0;
+    if (!ok) {
+        for (void *p : eb_allocs_) dfree(p);
+        eig_b_forget();
+        return SPARSH_ENODEV;
+    }
+    eb_set_ = true;
+    return SPARSH_OK;
+}
+
+namespace {
 
 // partials of a reducing launch on D: one per row block / four wave blocks / four slices, one per workgroup of the plane-marching kernel
 int partial_count(const DevCsr &D) { return std::max(std::max(D.nblk, D.box1.workgroups(D.box_ny, D.box_nz)), std::max((D.nwblk + 3) / 4, (D.nslice + 3) / 4)); }
@@ -1254,6 +1288,7 @@ int Engine::setup(const sparsh_params &p)
     gm_bytes_ = 0;
     multi_forget();  // (the block vectors too: the next block call reallocates them)
     eig_forget();    // (and the eigensolver's blocks)
+    eig_b_forget();  // (and the B of its generalised problem)
     sor_.clear();
     cheb_.clear();  // (the d vectors are freed with the rest)
     wk_.clear();    // (so are the extra vectors of the W- and K-cycles)

@@ -407,8 +407,22 @@ public:
     // column-major device array X (start block in, Ritz vectors out), host arrays lambda[nev], hist[c * hist_cap + it], iters, status
     int eigs_dev(int nev, double *X, long ldx, double tol, int max_iters, double *lambda, double *hist, int hist_cap, int *iters, int *status,
                  double *seconds);
-    // bench: op 2 = the twelve-pair Gram launch with its finalise, 3 = one update, on the resident eig blocks
+    // bench: op 2 = the twelve-pair Gram launch with its finalise, 3 = one update, on the resident eig blocks; with the blocks of the
+    // generalised solver reserved (eig_reserve_gen) 4 = its update, 5 = the block SpMV with B
     int bench_eig_launch(int op);
+    // ---- the generalised problem A x = lambda B x.  B is the caller's SPD matrix of n0() rows, checked on the host by the C layer and
+    // kept on the device as a CSR operator of the block path until the next setup, the destructor or the next eig_set_b (nullptr
+    // drops it).  BX, BW and BP are reserved at the first generalised call for a width, on top of eig_reserve's blocks.
+    int eig_set_b(const int *rowptr, const int *col, const double *val);
+    bool eig_b_set() const { return eb_set_; }
+    long eig_b_nnz() const { return eb_set_ ? eB_.nnz : 0; }
+    size_t eig_b_bytes() const { return eb_bytes_; }
+    int eig_reserve_gen(int nev);
+    // as eigs_dev; X comes back B-orthonormal
+    int eigs_gen_dev(int nev, double *X, long ldx, double tol, int max_iters, double *lambda, double *hist, int hist_cap, int *iters,
+                     int *status, double *seconds);
+    // hook: Y = B X on column-major device arrays through the block SpMV on the stored B
+    int op_eig_b_multi(int nrhs, const double *X, double *Y);
 
     // device memory helpers
     void *dalloc(size_t bytes);
@@ -571,13 +585,24 @@ private:
     // LOBPCG (engine_eig.cpp): seven interleaved blocks of n * width doubles, the partial sums of the Gram and residual launches,
     // G = [S^T S, S^T A S, residual norms] and coef = [Cx, Cw, Cp, theta]
     void eig_forget();  // the buffers went with allocs_ (setup): drop the pointers
-    void eig_gram_pairs(GramPairs &prs) const;
+    void eig_gram_pairs(GramPairs &prs, bool gen = false) const;
+    int eigs_run(bool gen, int nev, double *X, long ldx, double tol, int max_iters, double *lambda, double *hist, int hist_cap, int *iters,
+                 int *status, double *seconds);
+    void eig_b_spmv(const double *x, double *y);  // y = B x on interleaved blocks of width ew_
+    void eig_b_forget();                          // B went with allocs_ (setup): drop the pointers
+    void eig_update(bool gen, int k);             // step 6 in place on the resident blocks
     int ew_ = 0;        // width in force (0: nothing allocated)
     size_t eig_bytes_ = 0;
     int eig_restarts_ = 0;
     double *eX_ = nullptr, *eAX_ = nullptr, *eW_ = nullptr, *eAW_ = nullptr, *eP_ = nullptr, *eAP_ = nullptr, *eR_ = nullptr;
     double *epart_ = nullptr, *eG_ = nullptr, *ecoef_ = nullptr;
     double *epinned_ = nullptr;  // host-pinned: G coming down, coef going up
+    double *eBX_ = nullptr, *eBW_ = nullptr, *eBP_ = nullptr;  // the generalised solver's three extra blocks (in eig_allocs_)
+    DevCsr eB_;                                                  // B of the pencil
+    bool eb_set_ = false;
+    size_t eb_bytes_ = 0;
+    std::vector<void *> eb_allocs_;
+    size_t dalloc_total_ = 0;  // bytes dalloc ever handed out: the difference around an upload is that upload's size
     std::vector<void *> eig_allocs_;
 
     std::unique_ptr<Comm> comm_;

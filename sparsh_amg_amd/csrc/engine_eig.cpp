@@ -31,6 +31,7 @@ void Engine::eig_forget()
     eig_restarts_ = 0;
     eig_allocs_.clear();
     eX_ = eAX_ = eW_ = eAW_ = eP_ = eAP_ = eR_ = epart_ = eG_ = ecoef_ = nullptr;
+    eBX_ = eBW_ = eBP_ = nullptr;
 }
 
 void Engine::eig_release()
@@ -75,16 +76,45 @@ int Engine::eig_reserve(int nev)
     return SPARSH_OK;
 }
 
+// the three blocks B X, B W, B P of the generalised solver, on top of eig_reserve's: a change of width drops them with the rest
+int Engine::eig_reserve_gen(int nev)
+{
+    if (int rc = eig_reserve(nev); rc != SPARSH_OK) return rc;
+    if (eBX_) return SPARSH_OK;
+    const size_t bytes = (size_t)lev_[0].n * ew_ * 8;
+    double **blocks[3] = {&eBX_, &eBW_, &eBP_};
+    for (double **b : blocks) {
+        double *p = static_cast<double *>(dalloc(bytes));
+        if (!p || !check(hipMemsetAsync(p, 0, bytes, st_), "hipMemsetAsync")) {
+            if (p) dfree(p);
+            eig_release();
+            return SPARSH_ENODEV;
+        }
+        eig_allocs_.push_back(p);
+        eig_bytes_ += bytes;
+        *b = p;
+    }
+    return SPARSH_OK;
+}
+
+void Engine::eig_b_spmv(const double *x, double *y)
+{
+    MultiArgs a;
+    a.x = x;
+    a.y = y;
+    launch_csr_multi(eB_, ew_, OP_SPMV, a, st_, cfg_);
+}
+
 // the pair list of one Gram launch: X^T X and X^T AX first (the start needs these two only), then the rest of the upper block
-// triangles of S^T S (at G) and S^T A S (at G + 9 W^2), S = [X, W, P]
-void Engine::eig_gram_pairs(GramPairs &prs) const
+// triangles of S^T S (at G) and S^T A S (at G + 9 W^2), S = [X, W, P].  gen: S^T B S in place of S^T S, from the pairs (S_i, B S_j)
+void Engine::eig_gram_pairs(GramPairs &prs, bool gen) const
 {
     const int W = ew_, ld = 3 * W;
-    const double *S[3] = {eX_, eW_, eP_}, *AS[3] = {eAX_, eAW_, eAP_};
+    const double *S[3] = {eX_, eW_, eP_}, *AS[3] = {eAX_, eAW_, eAP_}, *BS[3] = {eBX_, eBW_, eBP_};
     int p = 0;
     auto add = [&](int bi, int bj, bool a) {
         prs.u[p] = S[bi];
-        prs.v[p] = a ? AS[bj] : S[bj];
+        prs.v[p] = a ? AS[bj] : (gen ? BS[bj] : S[bj]);
         prs.dst[p] = (a ? ld * ld : 0) + bi * W * ld + bj * W;
         ++p;
     };
@@ -99,6 +129,32 @@ void Engine::eig_gram_pairs(GramPairs &prs) const
 int Engine::eigs_dev(int nev, double *X, long ldx, double tol, int max_iters, double *lambda, double *hist, int hist_cap, int *iters,
                      int *status, double *seconds)
 {
+    return eigs_run(false, nev, X, ldx, tol, max_iters, lambda, hist, hist_cap, iters, status, seconds);
+}
+
+int Engine::eigs_gen_dev(int nev, double *X, long ldx, double tol, int max_iters, double *lambda, double *hist, int hist_cap, int *iters,
+                         int *status, double *seconds)
+{
+    return eigs_run(true, nev, X, ldx, tol, max_iters, lambda, hist, hist_cap, iters, status, seconds);
+}
+
+// step 6 in place on the resident blocks
+void Engine::eig_update(bool gen, int k)
+{
+    const int n = lev_[0].n;
+    if (!gen) {
+        launch_eig_update(n, ew_, k, eX_, eW_, eP_, eAX_, eAW_, eAP_, ecoef_, eX_, eP_, eAX_, eAP_, st_);
+        return;
+    }
+    const double *in[9] = {eX_, eW_, eP_, eAX_, eAW_, eAP_, eBX_, eBW_, eBP_};
+    double *out[6] = {eX_, eP_, eAX_, eAP_, eBX_, eBP_};
+    launch_eig_update_gen(n, ew_, k, in, ecoef_, out, st_);
+}
+
+// the loop of both solvers.  gen: the pencil (A, B) with B S carried beside A S; the standard solve's launches are those it always had
+int Engine::eigs_run(bool gen, int nev, double *X, long ldx, double tol, int max_iters, double *lambda, double *hist, int hist_cap, int *iters,
+                     int *status, double *seconds)
+{
     if (!ready_) {
         error = "sparsh_setup has not been called";
         return SPARSH_ESTATE;
@@ -108,8 +164,12 @@ int Engine::eigs_dev(int nev, double *X, long ldx, double tol, int max_iters, do
         error = why;
         return SPARSH_EINVAL;
     }
+    if (gen && !eb_set_) {
+        error = "sparsh_eig_set_b has not been called: the generalised problem needs its B";
+        return SPARSH_ESTATE;
+    }
     if (int rc = multi_reserve(nev); rc != SPARSH_OK) return rc;  // the cycle's own blocks
-    if (int rc = eig_reserve(nev); rc != SPARSH_OK) return rc;
+    if (int rc = gen ? eig_reserve_gen(nev) : eig_reserve(nev); rc != SPARSH_OK) return rc;
     if (max_iters <= 0) max_iters = prm_.max_iter;
     const int W = ew_, n = lev_[0].n, k = nev, ld = 3 * W;
     const size_t len = (size_t)n * W;
@@ -123,9 +183,12 @@ int Engine::eigs_dev(int nev, double *X, long ldx, double tol, int max_iters, do
         HIPCHK(hipEventRecord(e0, st_));
     }
     GramPairs prs;
-    eig_gram_pairs(prs);
+    eig_gram_pairs(prs, gen);
     double *norms = eG_ + 2 * ld * ld, *theta_dev = ecoef_ + 3 * W * W, *rpart = epart_ + (size_t)kEigPairs * W * W * kEigMaxGrid;
-    double theta[kMultiMax] = {0}, rn[kMultiMax] = {0};
+    // the generalised residual's second norm vector, ||B x_c||, travels in the first row of the (W, X) block of S^T B S: the Gram
+    // launch fills the upper block triangle only and the host reads nothing below it
+    double *bnorms = eG_ + (size_t)W * ld;
+    double theta[kMultiMax] = {0}, rn[kMultiMax] = {0}, bn[kMultiMax] = {0};
     bool active[kMultiMax] = {false};
     double GA[kEigSmallMax * kEigSmallMax], GB[kEigSmallMax * kEigSmallMax], C[kEigSmallMax * kMultiMax];
     int idx[kEigSmallMax];
@@ -177,8 +240,11 @@ int Engine::eigs_dev(int nev, double *X, long ldx, double tol, int max_iters, do
     for (int c = 0; c < k; ++c) iters[c] = 0, status[c] = SPARSH_OK;
     launch_interleave(n, k, W, X, ldx, eX_, st_);
     for (double *b : {eW_, eAW_, eP_, eAP_}) HIPCHK(hipMemsetAsync(b, 0, len * 8, st_));
+    if (gen)
+        for (double *b : {eBW_, eBP_}) HIPCHK(hipMemsetAsync(b, 0, len * 8, st_));
     HIPCHK(hipMemsetAsync(eG_, 0, (size_t)ndown * 8, st_));
     multi_spmv_dot(0, eX_, eAX_, mpart0_);
+    if (gen) eig_b_spmv(eX_, eBX_);
     launch_gram_multi(n, W, 2, prs, epart_, eG_, ld, st_);
     read_down(0, 2 * ld * ld);
     for (int c = 0; c < k; ++c) idx[c] = c;
@@ -186,31 +252,43 @@ int Engine::eigs_dev(int nev, double *X, long ldx, double tol, int max_iters, do
         stop_clock();
         return fault_;
     }
-    if (!finite(down, 2 * ld * ld)) return numeric("NaN in the start block or in A times the start block");
-    if (rayleigh_ritz(k) != 0) return numeric("Rayleigh-Ritz breakdown at the start: the start block is rank deficient");
-    launch_eig_update(n, W, k, eX_, eW_, eP_, eAX_, eAW_, eAP_, ecoef_, eX_, eP_, eAX_, eAP_, st_);  // (Cw = Cp = 0: P stays 0)
+    if (!finite(down, 2 * ld * ld))
+        return numeric(gen ? "NaN in the start block or in A or B times the start block" : "NaN in the start block or in A times the start block");
+    if (rayleigh_ritz(k) != 0)
+        return numeric(gen ? "Rayleigh-Ritz breakdown at the start: the start block is rank deficient or B is not positive definite"
+                           : "Rayleigh-Ritz breakdown at the start: the start block is rank deficient");
+    eig_update(gen, k);  // (Cw = Cp = 0: P stays 0)
 
     bool have_p = false, converged = false;
     for (int it = 0; fault_ == SPARSH_OK; ++it) {
         // 2. residual; at the cap only its norms are wanted
-        launch_eig_residual(n, W, eAX_, eX_, theta_dev, eR_, rpart, norms, st_);
+        if (gen) launch_eig_residual_gen(n, W, eAX_, eBX_, theta_dev, eR_, epart_, norms, bnorms, st_);  // (the Gram partials are free here)
+        else launch_eig_residual(n, W, eAX_, eX_, theta_dev, eR_, rpart, norms, st_);
         const bool last = it >= max_iters;
         if (!last) {
             // 3. W = M R, AW = A W ; 4. the Gram matrices of S = [X, W, P] and A S
             vcycle_multi(eR_);
             HIPCHK(hipMemcpyAsync(eW_, mlev_[0].x, len * 8, hipMemcpyDeviceToDevice, st_));
             multi_spmv_dot(0, eW_, eAW_, mpart0_);
+            if (gen) eig_b_spmv(eW_, eBW_);
             launch_gram_multi(n, W, kEigPairs, prs, epart_, eG_, ld, st_);
             read_down(0, ndown);
+        } else if (gen) {
+            read_down(0, ndown);  // (both norm vectors; the Gram matrices are stale and not looked at)
         } else {
             read_down(2 * ld * ld, W);
         }
         if (fault_ != SPARSH_OK) break;
         std::copy(down + 2 * ld * ld, down + 2 * ld * ld + k, rn);
         if (!finite(rn, k)) return numeric("NaN residual in the eigensolver");
+        if (gen) {
+            std::copy(down + W * ld, down + W * ld + k, bn);
+            if (!finite(bn, k)) return numeric("NaN in B times the Ritz vectors");
+        }
         int nact = 0;
         for (int c = 0; c < k; ++c) {
-            active[c] = rn[c] > tol * std::fabs(theta[c]);  // re-evaluated every iteration: soft locking
+            // re-evaluated every iteration: soft locking
+            active[c] = gen ? rn[c] > tol * std::fabs(theta[c]) * bn[c] : rn[c] > tol * std::fabs(theta[c]);
             nact += active[c];
             if (hist && it < hist_cap) hist[(size_t)c * hist_cap + it] = rn[c];
         }
@@ -236,7 +314,7 @@ int Engine::eigs_dev(int nev, double *X, long ldx, double tol, int max_iters, do
         }
         for (int c = 0; c < k; ++c) iters[c] += active[c];
         // 6. update
-        launch_eig_update(n, W, k, eX_, eW_, eP_, eAX_, eAW_, eAP_, ecoef_, eX_, eP_, eAX_, eAP_, st_);
+        eig_update(gen, k);
         have_p = true;
     }
     launch_deinterleave(n, k, W, eX_, X, ldx, st_);
@@ -247,7 +325,8 @@ int Engine::eigs_dev(int nev, double *X, long ldx, double tol, int max_iters, do
     std::copy(theta, theta + k, lambda);
     if (converged) return SPARSH_OK;
     for (int c = 0; c < k; ++c) status[c] = active[c] ? SPARSH_ENOCONV : SPARSH_OK;
-    error = "iteration cap reached before ||A x - lambda x|| <= tol |lambda| for every eigenpair";
+    error = gen ? "iteration cap reached before ||A x - lambda B x|| <= tol |lambda| ||B x|| for every eigenpair"
+                : "iteration cap reached before ||A x - lambda x|| <= tol |lambda| for every eigenpair";
     return SPARSH_ENOCONV;
 }
 
@@ -258,10 +337,34 @@ int Engine::bench_eig_launch(int op)
         GramPairs prs;
         eig_gram_pairs(prs);
         launch_gram_multi(n, ew_, kEigPairs, prs, epart_, eG_, 3 * ew_, st_);
+    } else if (op == 4) {
+        eig_update(true, ew_);
+    } else if (op == 5) {
+        eig_b_spmv(eX_, eBX_);
     } else {
         launch_eig_update(n, ew_, ew_, eX_, eW_, eP_, eAX_, eAW_, eAP_, ecoef_, eX_, eP_, eAX_, eAP_, st_);
     }
     return SPARSH_OK;
+}
+
+int Engine::op_eig_b_multi(int nrhs, const double *X, double *Y)
+{
+    const int n = lev_[0].n, W = multi_width(nrhs);
+    const size_t bytes = (size_t)n * W * 8;
+    double *bx = static_cast<double *>(dalloc(bytes)), *by = static_cast<double *>(dalloc(bytes));
+    if (bx && by) {
+        launch_interleave(n, nrhs, W, X, n, bx, st_);
+        MultiArgs a;
+        a.x = bx;
+        a.y = by;
+        launch_csr_multi(eB_, W, OP_SPMV, a, st_, cfg_);
+        launch_deinterleave(n, nrhs, W, by, Y, n, st_);
+        HIPCHK(hipStreamSynchronize(st_));
+    }
+    dfree(bx);
+    dfree(by);
+    if (!bx || !by) return SPARSH_ENODEV;
+    return fault_;
 }
 
 }  // namespace sparsh

@@ -486,4 +486,12 @@ void launch_eig_residual(int n, int W, const double *AX, const double *X, const 
 void launch_eig_update(int n, int W, int k, const double *X, const double *Wb, const double *P, const double *AX, const double *AW,
                        const double *AP, const double *coef, double *Xo, double *Po, double *AXo, double *APo, hipStream_t st);
 
+// the pencil (A, B): R = AX - BX * theta_c, rnorms[c] = ||R_c||_2 and bnorms[c] = ||BX_c||_2 from one pass (partial: 2 W * eig_grid(n, W)
+// doubles).  rnorms has the bits launch_eig_residual gives for the same R.
+void launch_eig_residual_gen(int n, int W, const double *AX, const double *BX, const double *theta, double *R, double *partial, double *rnorms,
+                             double *bnorms, hipStream_t st);
+// launch_eig_update with B S carried along.  in = X, W, P, AX, AW, AP, BX, BW, BP; out = X', P', AX', AP', BX', BP' with BP' = BW Cw + BP Cp
+// and BX' = BX Cx + BP'.  An output may be the block it replaces.
+void launch_eig_update_gen(int n, int W, int k, const double *const in[9], const double *coef, double *const out[6], hipStream_t st);
+
 }  // namespace sparsh

@@ -75,15 +75,8 @@ def _morton_order(pts):
     return np.argsort(spread(q[:, 0]) | (spread(q[:, 1]) << 1), kind="stable")
 
 
-def fem_unstructured(npts: int = 525825, seed: int = 20240607, dt: float = 1e-2, ordering: str = "morton"):
-    """P1-FEM  M + dt*K  on a Delaunay triangulation of random points in the unit square:
-    SPD, irregular 3..12+ nnz/row.  Stand-in for SuiteSparse parabolic_fem (configs[4]),
-    which cannot be fetched offline.
-
-    ordering="morton" numbers the nodes along a space-filling curve, the kind of locality a mesh
-    generator's numbering has (neighbouring nodes get nearby indices); ordering="random" keeps the
-    random point order: every x-gather of a row lands on an unrelated cache line -- a worst case
-    no mesh file exhibits, kept as a gather stress."""
+def _fem_assemble(npts, seed, dt, ordering, with_mass_only):
+    """The assembly of fem_unstructured; with_mass_only: also the mass matrix alone on the same stored pattern."""
     from scipy.spatial import Delaunay
     import scipy.sparse as sp
 
@@ -106,7 +99,7 @@ def fem_unstructured(npts: int = 525825, seed: int = 20240607, dt: float = 1e-2,
     g[:, 1, 1] = (p0[:, 0] - p2[:, 0]) / area2
     g[:, 2, 0] = (p0[:, 1] - p1[:, 1]) / area2
     g[:, 2, 1] = (p1[:, 0] - p0[:, 0]) / area2
-    rows, cols, vals = [], [], []
+    rows, cols, vals, mass = [], [], [], []
     for a in range(3):
         for b in range(3):
             k = area * (g[:, a, 0] * g[:, b, 0] + g[:, a, 1] * g[:, b, 1])
@@ -114,10 +107,34 @@ def fem_unstructured(npts: int = 525825, seed: int = 20240607, dt: float = 1e-2,
             rows.append(tri[:, a])
             cols.append(tri[:, b])
             vals.append(m + dt * k)
-    A = sp.coo_matrix((np.concatenate(vals), (np.concatenate(rows), np.concatenate(cols))), shape=(npts, npts)).tocsr()
-    A.sum_duplicates()
-    A.sort_indices()
-    return A.indptr.astype(np.int32), A.indices.astype(np.int32), A.data.astype(np.float64)
+            mass.append(m)
+
+    def csr(v):
+        A = sp.coo_matrix((np.concatenate(v), (np.concatenate(rows), np.concatenate(cols))), shape=(npts, npts)).tocsr()
+        A.sum_duplicates()
+        A.sort_indices()
+        return A.indptr.astype(np.int32), A.indices.astype(np.int32), A.data.astype(np.float64)
+
+    return csr(vals), (csr(mass) if with_mass_only else None)
+
+
+def fem_unstructured(npts: int = 525825, seed: int = 20240607, dt: float = 1e-2, ordering: str = "morton"):
+    """P1-FEM  M + dt*K  on a Delaunay triangulation of random points in the unit square:
+    SPD, irregular 3..12+ nnz/row.  Stand-in for SuiteSparse parabolic_fem (configs[4]),
+    which cannot be fetched offline.
+
+    ordering="morton" numbers the nodes along a space-filling curve, the kind of locality a mesh
+    generator's numbering has (neighbouring nodes get nearby indices); ordering="random" keeps the
+    random point order: every x-gather of a row lands on an unrelated cache line -- a worst case
+    no mesh file exhibits, kept as a gather stress."""
+    return _fem_assemble(npts, seed, dt, ordering, False)[0]
+
+
+def fem_pencil(npts: int = 525825, seed: int = 20240607, dt: float = 1e-2, ordering: str = "morton"):
+    """(A, M) as CSR triples: A = M + dt*K of fem_unstructured, bit for bit, and the mass matrix M alone on the same stored pattern.
+    The pencil A x = lambda M x has the spectrum 1 + dt * (eigenvalues of the Neumann Laplacian): 1 for the constant vector, then
+    well separated values, where A alone has the tight cluster of M's eigenvalues at its low end."""
+    return _fem_assemble(npts, seed, dt, ordering, True)
 
 
 def random_spd(n: int, nnz_per_row: int = 7, seed: int = 0):

@@ -1,16 +1,24 @@
 """The LOBPCG eigensolver on the large inputs: iterations, ms per iteration, the eigensolver's own launches
 beside the block path's, and the rate of the new kernels against the copy rate DESIGN.md uses.
 
-    python tools/eig_ab.py [--out profiles/eig_lobpcg.txt] [--reps 20] [--step-seconds 420]
+    python tools/eig_ab.py [--out profiles/eig_lobpcg.txt] [--reps 20] [--step-seconds 420] [--max-iters 300]
+    python tools/eig_ab.py --generalised [--out profiles/eig_gen_lobpcg.txt]
 
 Cases: poisson3d(216) with k = 4 and k = 8 under set_kernel_config(kind=0), fem_unstructured() with k = 4.  Every case runs in a
 process of its own under `timeout`; the first case that fails stops the rest.  Per case one JSON line:
   iterations, ms_per_iteration                   one timed eigs_dev call (HIP-event time) after a warm-up call
+  final_rn_over_bound                            per column, the last residual norm over tol |lambda| ||B x|| (B = I in the standard
+                                                 problem): at most 1 when the column has converged
   gram_us, update_us                             sparsh_bench_op_multi ops 2 and 3 on the solver's resident blocks
   spmv_dot_us, jacobi_us                         ops 0 and 1 on level 0 of the block path, for scale
   gram_TBps, update_TBps, *_of_copy_rate         24 and 10 block passes of 8 n W bytes over the measured time, against 6.29 TB/s
   eig_kernels_share                              (gram + update + residual estimate) / ms_per_iteration, the residual taken as 3 / 10
                                                  of the update (3 block passes against 10)
+--generalised: the pencil fem_pencil() = (M + dt K, M) at full size with k = 4 and 8 through eigs_gen_dev (cases femgen:k), next to the
+standard solve of the same operator (cases fem:k, which end at the cap: DESIGN.md section 5i).  The femgen lines add
+  update_gen_us, b_spmv_us                       sparsh_bench_op_multi ops 4 and 5 on the solver's resident blocks
+  update_gen_TBps, update_gen_of_copy_rate       15 block passes (9 in, 6 out) over the measured time
+and their eig_kernels_share counts the Gram launch, the generalised update and the residual as 4 / 15 of that update.
 """
 import argparse
 import json
@@ -25,30 +33,44 @@ sys.path.insert(0, ROOT)
 
 COPY_BYTES_PER_S = 6.29e12  # the device-to-device copy rate DESIGN.md measures kernels against
 CASES = ["p216:4", "p216:8", "fem:4"]
+CASES_GENERALISED = ["fem:4", "femgen:4", "fem:8", "femgen:8"]
 
 
-def run_case(case, reps):
+def run_case(case, reps, max_iters):
+    import scipy.sparse as sp
+
     import sparsh_amg_amd as sa
     from sparsh_amg_amd import problems
 
     name, k = case.split(":")
     k = int(k)
-    rp, ci, v = problems.poisson3d(216) if name == "p216" else problems.fem_unstructured()
+    gen = name == "femgen"
+    if gen:
+        (rp, ci, v), M = problems.fem_pencil()
+    else:
+        rp, ci, v = problems.poisson3d(216) if name == "p216" else problems.fem_unstructured()
     n = len(rp) - 1
     A = sa.sp_matrix_mg(rp, ci, v)
     if name == "p216":
         A.set_kernel_config(kind=0)
     A.setup(sa.default_params(print_setup=0, print_solve=0))
+    if gen:
+        A.set_eig_b(*M)
     W = 2 if k <= 2 else (4 if k <= 4 else 8)
     X0 = np.ascontiguousarray(np.random.default_rng(0).standard_normal((n, k)).T)  # (k, n) row-major = column-major (n, k)
     xd = A.dev_alloc(8 * n * k)
     rec = {"case": case, "rows": n, "nnz": int(rp[-1]), "k": k, "width": W, "levels": A.nlevels}
     for _ in range(2):  # the first call reserves the blocks
         A.h2d(xd, X0)
-        lam, iters, hist, status, sec, rc = A.eigs_dev(k, xd, n, max_iters=300)
+        lam, iters, hist, status, sec, rc = (A.eigs_gen_dev if gen else A.eigs_dev)(k, xd, n, max_iters=max_iters, hist_cap=max_iters + 1)
     its = hist.shape[1] - 1
     rec.update(rc=int(rc), iterations=its, seconds=round(sec, 4), ms_per_iteration=round(sec * 1e3 / max(its, 1), 4),
                lam=[float(x) for x in lam], restarts=A.eig_info()["restarts"], eig_bytes=A.eig_info()["bytes"])
+    # how far the last evaluation is from the stopping rule: rn_c / (tol |lam_c| ||B x_c||), B = I in the standard problem
+    X = np.zeros((k, n))
+    A.d2h(X, xd)
+    bn = np.linalg.norm(sp.csr_matrix((M[2], M[1], M[0]), shape=(n, n)) @ X.T, axis=0) if gen else np.linalg.norm(X, axis=1)
+    rec["final_rn_over_bound"] = [float(x) for x in hist[:, -1] / (1e-8 * np.abs(lam) * bn)]
     t = {op: A.bench_op_multi(op, 0, nrhs=k, reps=reps) for op in ("eig_gram", "eig_update", "spmv_dot", "jacobi_pingpong_resident")}
     block = 8.0 * n * W
     rec.update(gram_us=round(t["eig_gram"] * 1e6, 2), update_us=round(t["eig_update"] * 1e6, 2),
@@ -58,6 +80,13 @@ def run_case(case, reps):
     rec["gram_of_copy_rate"] = round(24 * block / t["eig_gram"] / COPY_BYTES_PER_S, 3)
     rec["update_of_copy_rate"] = round(10 * block / t["eig_update"] / COPY_BYTES_PER_S, 3)
     rec["eig_kernels_share"] = round((t["eig_gram"] + 1.3 * t["eig_update"]) / (sec / max(its, 1)), 3)
+    if gen:
+        tg = {op: A.bench_op_multi(op, 0, nrhs=k, reps=reps) for op in ("eig_update_gen", "eig_b_spmv")}
+        rec.update(update_gen_us=round(tg["eig_update_gen"] * 1e6, 2), b_spmv_us=round(tg["eig_b_spmv"] * 1e6, 2),
+                   b_nnz=A.eig_b_info()["nnz"], b_bytes=A.eig_b_info()["bytes"])
+        rec["update_gen_TBps"] = round(15 * block / tg["eig_update_gen"] / 1e12, 3)
+        rec["update_gen_of_copy_rate"] = round(15 * block / tg["eig_update_gen"] / COPY_BYTES_PER_S, 3)
+        rec["eig_kernels_share"] = round((t["eig_gram"] + (1.0 + 4.0 / 15.0) * tg["eig_update_gen"]) / (sec / max(its, 1)), 3)
     A.dev_free(xd)
     A.close()
     print(json.dumps(rec), flush=True)
@@ -68,17 +97,22 @@ def main():
     ap.add_argument("--case", default=None, help="run one case in this process (used by the driver)")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--step-seconds", type=int, default=420)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "eig_lobpcg.txt"))
+    ap.add_argument("--max-iters", type=int, default=300, help="the iteration cap of every solve")
+    ap.add_argument("--generalised", action="store_true", help="the FEM pencil against its mass matrix, next to the standard solve")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "eig_gen_lobpcg.txt" if args.generalised else "eig_lobpcg.txt")
     if args.case:
-        run_case(args.case, args.reps)
+        run_case(args.case, args.reps, args.max_iters)
         return 0
     lines = []
-    for case in CASES:  # the driver itself never opens the GPU
-        cmd = ["timeout", "-k", "10", str(args.step_seconds), sys.executable, os.path.abspath(__file__), "--case", case, "--reps", str(args.reps)]
+    for case in (CASES_GENERALISED if args.generalised else CASES):  # the driver itself never opens the GPU
+        cmd = ["timeout", "-k", "10", str(args.step_seconds), sys.executable, os.path.abspath(__file__), "--case", case, "--reps", str(args.reps),
+               "--max-iters", str(args.max_iters)]
         p = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
         sys.stdout.write(p.stdout)
-        if p.returncode != 0:
+        if p.returncode != 0:  # (a solve that ends at the cap is a result, SPARSH_ENOCONV in "rc", not a failure)
             print(f"{case}: exit status {p.returncode}; the remaining cases are not run", flush=True)
             return p.returncode
         lines += [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
