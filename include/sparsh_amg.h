@@ -710,12 +710,14 @@ int sparsh_op_precond_multi(sparsh_handle h, int nrhs, const double *R, double *
  * sweeps ping-ponging (the counterpart of sparsh_bench_op 10); on the eigensolver's resident blocks of width multi_width(nrhs)
  * (level 0 whatever `level` says; reserved by the call): op 2 = the twelve-pair Gram launch with its finalise, 3 = one update;
  * with the generalised solver's blocks beside them (reserved by the call; SPARSH_ESTATE without a B): 4 = the generalised update,
- * 5 = the block SpMV with B */
+ * 5 = the block SpMV with B; 7 = one projection of the constrained eigensolver (the Gram launch with its finalise, then the apply kernel) of the resident W block with the
+ * constraints the last constrained solve left resident (SPARSH_ESTATE unless one of this width has run).  6 is not assigned. */
 int sparsh_bench_op_multi(sparsh_handle h, int op, int level, int nrhs, int reps, double *avg_seconds);
 
 /* ---- the lowest eigenpairs of the SPD level-0 operator by LOBPCG on the block path ----
  * nev <= SPARSH_MAX_RHS eigenpairs A x = lambda x with the smallest lambda, the block V-cycle as preconditioner.  The standard
- * problem here, the generalised one A x = lambda B x in sparsh_eigs_gen below; SPD operators only, no null-space handles.  X is column-major, column c at X + c * ldx, ldx >= n: the
+ * problem here, the generalised one A x = lambda B x in sparsh_eigs_gen below; SPD operators only, no null-space handles (those, and
+ * constraints, in sparsh_eigs_con further below).  X is column-major, column c at X + c * ldx, ldx >= n: the
  * start block on entry (it must have full rank), the Ritz vectors on return, orthonormal and ordered by ascending lambda[c].
  * Notation: k = nev, W = the block width 2, 4 or 8 (k rounded up; padding columns hold zeros and are never active).
  *  1. start: AX = A X; Rayleigh-Ritz on the pencil (X^T AX, X^T X) gives theta and C; X <- X C, AX <- AX C; there is no P yet.
@@ -791,6 +793,64 @@ int sparsh_eigs_gen(sparsh_handle h, int nev, double *X, long ldx, double tol, i
                     int *iters, int *status);
 int sparsh_eigs_gen_dev(sparsh_handle h, int nev, double *X_dev, long ldx, double tol, int max_iters, double *lambda, double *hist,
                         int hist_cap, int *iters, int *status, double *seconds);
+
+/* ---- eigenpairs under constraints: singular operators, more than SPARSH_MAX_RHS pairs ----
+ * sparsh_eigs_con / sparsh_eigs_con_dev: the nev <= 8 lowest pairs of A x = lambda B x subject to (B y_j)^T x = 0 for every constraint
+ * y_j, X B-orthonormal and ascending in lambda: LOBPCG with constraints (the Y of scipy.sparse.linalg.lobpcg).  gen = 0: the standard
+ * problem (B = I, Euclidean orthogonality); gen = 1: the pencil (A, B) of sparsh_eig_set_b (on a null-space handle: of
+ * sparsh_eig_con_set_b below), SPARSH_ESTATE without a B.  Y is
+ * column-major, n x ncon, ldy >= n; NULL is allowed when ncon == 0.  All other arguments, results, codes and memory rules are those
+ * of sparsh_eigs.  Uses: the converged vectors of a first call as Y give the pairs 9..16, and so on (the constraints are only as
+ * good as those vectors: eigenvalues shift by the order of their tolerance).
+ * Null-space handles: these calls are the eigensolver of a handle set up under SPARSH_NULLSPACE_CONSTANT (a graph Laplacian, a
+ * pure-Neumann problem, a floating subdomain).  The constant vector is appended to the constraints implicitly, the pairs returned are
+ * the lowest nonzero ones and column 0 is the Fiedler pair.  A is positive semidefinite then, and positive definite on the
+ * constrained subspace, which is all the method needs; the block V-cycle runs on the pinned coarsest operator of such a handle.
+ * sparsh_eigs, sparsh_eigs_gen, sparsh_solve_multi and sparsh_op_precond_multi keep refusing null-space handles: without the
+ * constraint their iterates drift along the null space, which the block cycle does not project out.
+ * Notation: mt = ncon (+ 1 on a null-space handle), Pi V = V - Y G^-1 (BY)^T V with G = Y^T (BY).
+ *  At entry: Y is interleaved into ceil(mt / W) blocks of the solve's width W (zero padding columns; the column of ones last),
+ *  BY = B Y by the block SpMV per block when gen = 1 (BY is Y when gen = 0), G comes from the Gram launch of step 4 and is inverted
+ *  on the host (the scaling and Cholesky of step 5, two triangular solves) and uploaded: one extra host read per call.
+ *  Step 1: X <- Pi X before AX and BX are formed.  Step 3: W <- Pi (M R) before AW and BW are formed; the projection writes the
+ *  cycle's output straight into W and so replaces the copy of the unconstrained loop.  P and R are not projected (P is a
+ *  combination of projected blocks) and X is not projected again at return: X^T B X = I holds to the accuracy of sparsh_eigs, the
+ *  constraint holds to rounding noise.  Everything else is the loop above.
+ *  One projection is the Gram launch with its finalise (two kernels: C = (BY)^T V in a fixed summation order) and then one kernel,
+ *  without a host read or atomics: a pass in which every workgroup forms coef = G^-1 C (coef_jc = sum_i Ginv_ji C_ic, i ascending, every product and sum rounded
+ *  on its own) and streams dst_ic = src_ic - sum_j Y_ij coef_jc, j ascending from the product of j = 0, one subtraction at the end.
+ *  It costs O(n mt) per iteration: the blocks of Y and BY are read once each.
+ * With mt == 0 (no constraints, ordinary handle) the call issues the launches of sparsh_eigs / sparsh_eigs_gen, takes no constraint
+ * memory and returns their bits.
+ * SPARSH_EINVAL (with or without a device): everything sparsh_eigs refuses except a null-space handle; gen outside {0, 1}; ncon
+ * outside 0 .. SPARSH_MAX_CON; Y == NULL with ncon > 0; ldy < n; nev + mt > n.  SPARSH_ENUMERIC with "the constraints are rank
+ * deficient" when Y^T B Y fails the Cholesky test of step 5 (this includes a caller's constant vector on a null-space handle); the
+ * constraint blocks of such a call are freed again and sparsh_eig_con_info reports zeros.
+ * Memory: the blocks of Y, those of BY when gen = 1, G (padded order), G^-1 and C are the solver's own, reserved per call shape
+ * (width, mt, gen), replaced by a call of another shape, freed by sparsh_setup, sparsh_destroy and a change of width.  They are
+ * counted by sparsh_eig_con_info (the constraints in force, whether the constant vector is among them, the bytes; zeros until a
+ * constrained call), never by sparsh_eig_info: sparsh_eigs and sparsh_eigs_gen keep their bits, launches and byte counts whatever
+ * was called before.
+ * The constraints are meant to span an invariant subspace of the pencil, to the accuracy wanted: converged eigenvectors, a null
+ * vector.  The stopping rule looks at the unprojected residual A x - lambda B x (R is not projected), which at the solution of a
+ * problem constrained by other vectors is a combination of B Y and not zero: such a solve finds the right Ritz values and ends at the
+ * iteration cap with SPARSH_ENOCONV.
+ * Limits: one GPU, fp64, the Jacobi V-cycle, the constant null space only. */
+#define SPARSH_MAX_CON 16
+int sparsh_eigs_con(sparsh_handle h, int gen, int nev, double *X, long ldx, int ncon, const double *Y, long ldy, double tol, int max_iters,
+                    double *lambda, double *hist, int hist_cap, int *iters, int *status);
+int sparsh_eigs_con_dev(sparsh_handle h, int gen, int nev, double *X_dev, long ldx, int ncon, const double *Y_dev, long ldy, double tol,
+                        int max_iters, double *lambda, double *hist, int hist_cap, int *iters, int *status, double *seconds);
+int sparsh_eig_con_info(sparsh_handle h, int *ncon_total, int *implicit_constant, long *bytes);
+/* sparsh_eig_set_b for the constrained calls: the same B, checks and lifetime, but a null-space handle is accepted (L x = lambda D x
+ * on a graph Laplacian).  sparsh_eig_set_b itself keeps refusing such a handle, as sparsh_eigs_gen does. */
+int sparsh_eig_con_set_b(sparsh_handle h, const int *rowptr, const int *colindex, const double *val);
+/* hook of the projection (any n > 0; k in 1..8; m in 1..17; a ready handle lends its stream): Y, BY (n x m) and V (n x k) column-major,
+ * Ginv m x m row-major.  C returns (BY)^T V (m x k, row-major), Vout the projected block; V == Vout means in place on the device.
+ * SPARSH_ENUMERIC if a padding column of the device block comes back nonzero. */
+int sparsh_op_eig_con_project(sparsh_handle h, int n, int k, int m, const double *Y, const double *BY, const double *Ginv, const double *V,
+                              double *Vout, double *C);
+
 /* step 5 alone on a compacted pencil of order m <= 24 (row-major, upper triangles read): theta[k], C (m x k, row-major).  Returns
  * 0, or 1 for a breakdown.  Needs no handle and no device. */
 int sparsh_debug_eig_small(int m, int k, const double *GA, const double *GB, double *theta, double *C);

@@ -264,9 +264,16 @@ def _load():
         "sparsh_op_eig_update": (C.c_int, [H, C.c_int, C.c_int] + [c_dbl_p] * 13),
         "sparsh_eig_set_b": (C.c_int, [H, c_int_p, c_int_p, c_dbl_p]),
         "sparsh_eig_b_info": (C.c_int, [H, c_int_p, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
+        "sparsh_eig_con_set_b": (C.c_int, [H, c_int_p, c_int_p, c_dbl_p]),
         "sparsh_eigs_gen": (C.c_int, [H, C.c_int, c_dbl_p, C.c_long, C.c_double, C.c_int, c_dbl_p, c_dbl_p, C.c_int, c_int_p, c_int_p]),
         "sparsh_eigs_gen_dev": (C.c_int, [H, C.c_int, C.c_void_p, C.c_long, C.c_double, C.c_int, c_dbl_p, c_dbl_p, C.c_int, c_int_p, c_int_p,
                                           c_dbl_p]),
+        "sparsh_eigs_con": (C.c_int, [H, C.c_int, C.c_int, c_dbl_p, C.c_long, C.c_int, c_dbl_p, C.c_long, C.c_double, C.c_int, c_dbl_p,
+                                      c_dbl_p, C.c_int, c_int_p, c_int_p]),
+        "sparsh_eigs_con_dev": (C.c_int, [H, C.c_int, C.c_int, C.c_void_p, C.c_long, C.c_int, C.c_void_p, C.c_long, C.c_double, C.c_int,
+                                          c_dbl_p, c_dbl_p, C.c_int, c_int_p, c_int_p, c_dbl_p]),
+        "sparsh_eig_con_info": (C.c_int, [H, c_int_p, c_int_p, C.POINTER(C.c_long)]),
+        "sparsh_op_eig_con_project": (C.c_int, [H, C.c_int, C.c_int, C.c_int] + [c_dbl_p] * 6),
         "sparsh_op_eig_b_multi": (C.c_int, [H, C.c_int, c_dbl_p, c_dbl_p]),
         "sparsh_op_eig_residual_gen": (C.c_int, [H, C.c_int, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p]),
         "sparsh_op_eig_update_gen": (C.c_int, [H, C.c_int, C.c_int, C.POINTER(c_dbl_p), c_dbl_p, c_dbl_p, c_dbl_p, C.POINTER(c_dbl_p)]),
@@ -1363,19 +1370,21 @@ class sp_matrix_mg:
         return dict(width=w.value, bytes=b.value, restarts=r.value)
 
     # -- the generalised problem A x = lambda B x ---------------------------------------------------------------
-    def set_eig_b(self, rowptr, col=None, val=None):
+    def set_eig_b(self, rowptr, col=None, val=None, con=False):
         """The SPD matrix B of the generalised problem as 0-based CSR with sorted columns (copied to the device); None drops it.  B lives
-        until the next setup, close or set_eig_b."""
+        until the next setup, close or set_eig_b.  con: for eigs_con only, which lets a handle set up with a null space through (eigs_gen
+        refuses such a handle, and so does this call without con)."""
+        fn = lib.sparsh_eig_con_set_b if con else lib.sparsh_eig_set_b
         if rowptr is None:
-            _check(lib.sparsh_eig_set_b(self._h, None, None, None))
+            _check(fn(self._h, None, None, None))
             return self
         rp = np.ascontiguousarray(rowptr, dtype=np.int32)
         if col is None or val is None:  # (the library's refusal and its message)
-            _check(lib.sparsh_eig_set_b(self._h, _ip(rp), None, None))
+            _check(fn(self._h, _ip(rp), None, None))
         ci, v = np.ascontiguousarray(col, dtype=np.int32), np.ascontiguousarray(val, dtype=np.float64)
         if len(rp) != self.nrow + 1 or len(ci) != len(v) or (len(rp) and rp[-1] > len(ci)):
             raise ValueError("B must have the handle's number of rows, and rowptr[-1] entries in col and val")
-        _check(lib.sparsh_eig_set_b(self._h, _ip(rp), _ip(ci), _dp(v)))
+        _check(fn(self._h, _ip(rp), _ip(ci), _dp(v)))
         return self
 
     def eig_b_info(self):
@@ -1392,6 +1401,49 @@ class sp_matrix_mg:
     def eigs_gen_dev(self, k, X_dev, ldx, tol=1e-8, max_iters=0, hist_cap=1024):
         """eigs_dev for the generalised problem."""
         return self._eigs_dev(lib.sparsh_eigs_gen_dev, k, X_dev, ldx, tol, max_iters, hist_cap)
+
+    # -- eigenpairs under constraints: null-space handles, more than 8 pairs ---------------------------------------
+    def eigs_con(self, k, Y=None, gen=False, X0=None, tol=1e-8, max_iters=0, seed=0, hist_cap=1024):
+        """The k <= 8 lowest eigenpairs of A x = lam x (gen: of A x = lam B x with the B of set_eig_b) in the B-orthogonal complement of
+        the columns of Y (n, ncon <= 16; None: no constraints).  On a handle set up with set_nullspace("constant") the constant vector
+        is a constraint of its own accord: the pairs are the lowest nonzero ones, column 0 the Fiedler pair.  Returns what eigs
+        returns."""
+        Yf, ncon = self._constraints(Y)
+        fn = lambda h, kk, X, ldx, *rest: lib.sparsh_eigs_con(h, int(bool(gen)), kk, X, ldx, ncon, None if Yf is None else _dp(Yf),
+                                                             max(self.nrow, 1), *rest)
+        return self._eigs(fn, k, X0, tol, max_iters, seed, hist_cap)
+
+    def eigs_con_dev(self, k, X_dev, ldx, ncon=0, Y_dev=None, ldy=0, gen=False, tol=1e-8, max_iters=0, hist_cap=1024):
+        """eigs_dev under constraints: Y_dev a column-major device array of ncon columns.  Returns what eigs_dev returns."""
+        fn = lambda h, kk, X, ld, *rest: lib.sparsh_eigs_con_dev(h, int(bool(gen)), kk, X, ld, int(ncon), Y_dev, int(ldy), *rest)
+        return self._eigs_dev(fn, k, X_dev, ldx, tol, max_iters, hist_cap)
+
+    def _constraints(self, Y):
+        if Y is None:
+            return None, 0
+        Yf = self._block(Y, self.nrow)
+        return (Yf, Yf.shape[1]) if Yf.shape[1] > 0 else (None, 0)
+
+    def eig_con_info(self):
+        """Constraints in force in the eigensolver's constraint blocks (the implicit constant vector of a null-space handle included),
+        whether that vector is among them, and the device bytes the blocks hold: zeros until the first constrained call."""
+        m, c, b = C.c_int(), C.c_int(), C.c_long()
+        _check(lib.sparsh_eig_con_info(self._h, C.byref(m), C.byref(c), C.byref(b)))
+        return dict(ncon_total=m.value, implicit_constant=c.value, bytes=b.value)
+
+    def op_eig_con_project(self, Y, BY, Ginv, V, in_place=False):
+        """(Vout, C): C = BY^T V (m, k) through the Gram launch and Vout = V - Y (Ginv C) through the projection kernel of the
+        constrained eigensolver; Y, BY (n, m <= 17), V (n, k <= 8), any n > 0.  in_place: the block is projected in place on the device."""
+        n = np.shape(V)[0]
+        Vf, Yf, BYf = self._block(V), self._block(Y, n), self._block(BY, n)
+        m, k = Yf.shape[1], Vf.shape[1]
+        G = np.ascontiguousarray(Ginv, dtype=np.float64)
+        if BYf.shape != Yf.shape or G.shape != (m, m):
+            raise ValueError("Y and BY are n x m, Ginv m x m")
+        out = Vf if in_place else np.zeros_like(Vf, order="F")
+        Cm = np.zeros((m, k))
+        _check(lib.sparsh_op_eig_con_project(self._h, n, k, m, _dp(Yf), _dp(BYf), _dp(G), _dp(Vf), _dp(out), _dp(Cm)))
+        return out, Cm
 
     def op_eig_b_multi(self, X):
         """Y = B X through the block SpMV on the stored B."""
@@ -1454,8 +1506,10 @@ class sp_matrix_mg:
     def bench_op_multi(self, op, level=0, nrhs=8, reps=20):
         """Average seconds of one block launch on the level's resident block buffers: "spmv_dot" (0) or "jacobi_pingpong_resident" (1);
         on the eigensolver's resident blocks: "eig_gram" (2, the twelve-pair Gram launch with its finalise) or "eig_update" (3); with
-        the generalised solver's blocks and a B set: "eig_update_gen" (4) or "eig_b_spmv" (5)."""
-        ops = {"spmv_dot": 0, "jacobi_pingpong_resident": 1, "eig_gram": 2, "eig_update": 3, "eig_update_gen": 4, "eig_b_spmv": 5}
+        the generalised solver's blocks and a B set: "eig_update_gen" (4) or "eig_b_spmv" (5); after a constrained eigen solve of this
+        width: "eig_con_project" (7), one projection with the constraints that solve left resident."""
+        ops = {"spmv_dot": 0, "jacobi_pingpong_resident": 1, "eig_gram": 2, "eig_update": 3, "eig_update_gen": 4, "eig_b_spmv": 5,
+               "eig_con_project": 7}
         sec = C.c_double()
         _check(lib.sparsh_bench_op_multi(self._h, ops[op] if isinstance(op, str) else op, int(level), int(nrhs), int(reps), C.byref(sec)))
         return sec.value

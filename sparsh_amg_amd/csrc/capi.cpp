@@ -2212,18 +2212,24 @@ int sparsh_op_precond_multi(sparsh_handle h, int nrhs, const double *R, double *
 int sparsh_bench_op_multi(sparsh_handle h, int op, int level, int nrhs, int reps, double *avg_seconds)
 {
     REQUIRE_MULTI_ARGS(h, nrhs);
-    if (op < 0 || op > 5) return fail(SPARSH_EINVAL, "unknown op");
+    if (op < 0 || op > 7 || op == 6) return fail(SPARSH_EINVAL, "unknown op");  // (6 is not assigned)
     if (reps <= 0 || !avg_seconds) return fail(SPARSH_EINVAL, "bad reps");
     REQUIRE_READY(h);
     REQUIRE_SINGLE(h);
     REQUIRE_LEVEL(h, level);
     Engine &E = *h->eng;
+    const bool con = op == 7;  // the projection of the constrained eigensolver: only on what a constrained solve has left resident
     const bool eig = op >= 2;  // the eigensolver's launches run on its own resident blocks (level 0)
-    const bool gen = op >= 4;  // 4, 5: the generalised solver's blocks beside them, and its B
+    const bool gen = op >= 4 && !con;  // 4, 5: the generalised solver's blocks beside them, and its B
     if (gen && !E.eig_b_set()) return fail(SPARSH_ESTATE, "sparsh_eig_set_b has not been called");
-    if (int rc = gen ? E.eig_reserve_gen(nrhs) : (eig ? E.eig_reserve(nrhs) : E.multi_reserve(nrhs)); rc != SPARSH_OK) return fail(rc, E.error);
+    if (con) {
+        if (E.eig_con_total() == 0 || E.eig_width_now() != multi_width(nrhs))
+            return fail(SPARSH_ESTATE, "no constrained eigen solve of this width has reserved the constraint blocks");
+    } else if (int rc = gen ? E.eig_reserve_gen(nrhs) : (eig ? E.eig_reserve(nrhs) : E.multi_reserve(nrhs)); rc != SPARSH_OK) {
+        return fail(rc, E.error);
+    }
     hipStream_t st = E.stream();
-    auto launch = [&]() { return eig ? E.bench_eig_launch(op) : E.bench_multi_launch(op, level); };
+    auto launch = [&]() { return con ? E.bench_eig_con_launch() : (eig ? E.bench_eig_launch(op) : E.bench_multi_launch(op, level)); };
     for (int i = 0; i < 3; ++i) launch();
     hipEvent_t e0, e1;
     (void)hipEventCreate(&e0);
@@ -2334,7 +2340,10 @@ const char *eig_b_defect(int n, const int *rp, const int *ci, const double *v)
 
 }  // namespace
 
-int sparsh_eig_set_b(sparsh_handle h, const int *rowptr, const int *colindex, const double *val)
+namespace {
+
+// sparsh_eig_set_b and sparsh_eig_con_set_b: con lets a null-space handle through
+int eig_set_b_checked(sparsh_handle h, const int *rowptr, const int *colindex, const double *val, bool con)
 {
     if (!h || !h->eng) return fail(SPARSH_EINVAL, "null handle");
     Engine &E = *h->eng;
@@ -2344,10 +2353,22 @@ int sparsh_eig_set_b(sparsh_handle h, const int *rowptr, const int *colindex, co
     }
     if (!colindex || !val) return fail(SPARSH_EINVAL, "B: NULL colindex or val with a rowptr");
     if (const char *why = eig_b_defect(E.n0(), rowptr, colindex, val)) return fail(SPARSH_EINVAL, why);
-    REQUIRE_MULTI_FITS(h);
+    if (const char *why = con ? E.eig_con_refusal() : E.multi_refusal()) return fail(SPARSH_EINVAL, why);
     REQUIRE_READY(h);
     if (int rc = E.eig_set_b(rowptr, colindex, val); rc != SPARSH_OK) return fail(rc, E.error);
     return SPARSH_OK;
+}
+
+}  // namespace
+
+int sparsh_eig_set_b(sparsh_handle h, const int *rowptr, const int *colindex, const double *val)
+{
+    return eig_set_b_checked(h, rowptr, colindex, val, false);
+}
+
+int sparsh_eig_con_set_b(sparsh_handle h, const int *rowptr, const int *colindex, const double *val)
+{
+    return eig_set_b_checked(h, rowptr, colindex, val, true);
 }
 
 int sparsh_eig_b_info(sparsh_handle h, int *is_set, long *nnz, long *bytes)
@@ -2382,6 +2403,112 @@ int sparsh_eig_info(sparsh_handle h, int *width, long *bytes, int *restarts)
     if (bytes) *bytes = (long)h->eng->eig_bytes();
     if (restarts) *restarts = h->eng->eig_restarts();
     return SPARSH_OK;
+}
+
+// ---- eigenpairs under constraints ----
+
+// REQUIRE_EIG_ARGS with a null-space handle let through (it gets the constant vector as one more constraint), then the constraints
+#define REQUIRE_EIG_CON_ARGS(h, gen, nev, X, ldx, ncon, Y, ldy, tol, lambda, hist, hist_cap, iters, status)                               \
+    if (!(h) || !(h)->eng) return fail(SPARSH_EINVAL, "null handle");                                                                  \
+    if ((nev) < 1 || (nev) > SPARSH_MAX_RHS) return fail(SPARSH_EINVAL, "nev must be 1 .. SPARSH_MAX_RHS (8)");                          \
+    if ((nev) > (h)->eng->n0()) return fail(SPARSH_EINVAL, "nev exceeds the number of rows");                                           \
+    if (!(X) || !(lambda) || !(iters) || !(status) || ((hist_cap) > 0 && !(hist))) return fail(SPARSH_EINVAL, "NULL array");          \
+    if ((hist_cap) < 0) return fail(SPARSH_EINVAL, "hist_cap < 0");                                                                    \
+    if ((ldx) < (h)->eng->n0()) return fail(SPARSH_EINVAL, "ldx must be at least the number of rows");                                  \
+    if (!std::isfinite(tol) || !((tol) > 0.0)) return fail(SPARSH_EINVAL, "tol must be finite and positive");                          \
+    if (const char *why_ = (h)->eng->eig_con_refusal()) return fail(SPARSH_EINVAL, why_);                                              \
+    if ((gen) != 0 && (gen) != 1) return fail(SPARSH_EINVAL, "gen must be 0 (A x = lambda x) or 1 (A x = lambda B x)");                \
+    if ((ncon) < 0 || (ncon) > SPARSH_MAX_CON) return fail(SPARSH_EINVAL, "ncon must be 0 .. SPARSH_MAX_CON (16)");                     \
+    if ((ncon) > 0 && !(Y)) return fail(SPARSH_EINVAL, "NULL array: Y with ncon > 0");                                                 \
+    if ((ncon) > 0 && (ldy) < (h)->eng->n0()) return fail(SPARSH_EINVAL, "ldy must be at least the number of rows");                    \
+    if ((nev) + (ncon) + ((h)->eng->ns_on() ? 1 : 0) > (h)->eng->n0())                                                                 \
+    return fail(SPARSH_EINVAL, "nev and the constraints (the constant vector of a null-space handle included) exceed the number of rows")
+
+int sparsh_eigs_con_dev(sparsh_handle h, int gen, int nev, double *X_dev, long ldx, int ncon, const double *Y_dev, long ldy, double tol,
+                        int max_iters, double *lambda, double *hist, int hist_cap, int *iters, int *status, double *seconds)
+{
+    REQUIRE_EIG_CON_ARGS(h, gen, nev, X_dev, ldx, ncon, Y_dev, ldy, tol, lambda, hist, hist_cap, iters, status);
+    REQUIRE_READY(h);
+    int rc = h->eng->eigs_con_dev(gen != 0, nev, X_dev, ldx, ncon, Y_dev, ldy, tol, max_iters, lambda, hist, hist_cap, iters, status, seconds);
+    if (rc != SPARSH_OK) return fail(rc, h->eng->error);
+    return rc;
+}
+
+int sparsh_eigs_con(sparsh_handle h, int gen, int nev, double *X, long ldx, int ncon, const double *Y, long ldy, double tol, int max_iters,
+                    double *lambda, double *hist, int hist_cap, int *iters, int *status)
+{
+    REQUIRE_EIG_CON_ARGS(h, gen, nev, X, ldx, ncon, Y, ldy, tol, lambda, hist, hist_cap, iters, status);
+    REQUIRE_READY(h);
+    Engine &E = *h->eng;
+    if (gen && !E.eig_b_set()) return fail(SPARSH_ESTATE, "sparsh_eig_set_b has not been called: the generalised problem needs its B");
+    const size_t n = (size_t)E.n0();
+    DBuf dx(E, n * nev), dy(E, n * std::max(ncon, 1));  // packed (leading dimension n)
+    if (!dx.p || !dy.p) return fail(SPARSH_ENODEV, E.error);
+    for (int c = 0; c < nev; ++c) (void)hipMemcpy(dx.p + (size_t)c * n, X + (size_t)c * ldx, n * 8, hipMemcpyHostToDevice);
+    for (int c = 0; c < ncon; ++c) (void)hipMemcpy(dy.p + (size_t)c * n, Y + (size_t)c * ldy, n * 8, hipMemcpyHostToDevice);
+    int rc = E.eigs_con_dev(gen != 0, nev, dx.p, (long)n, ncon, ncon > 0 ? dy.p : nullptr, (long)n, tol, max_iters, lambda, hist, hist_cap, iters,
+                            status, nullptr);
+    (void)hipStreamSynchronize(E.stream());
+    if (rc == SPARSH_OK || rc == SPARSH_ENOCONV)
+        for (int c = 0; c < nev; ++c) (void)hipMemcpy(X + (size_t)c * ldx, dx.p + (size_t)c * n, n * 8, hipMemcpyDeviceToHost);
+    if (rc != SPARSH_OK) return fail(rc, E.error);
+    return rc;
+}
+
+int sparsh_eig_con_info(sparsh_handle h, int *ncon_total, int *implicit_constant, long *bytes)
+{
+    if (!h || !h->eng) return fail(SPARSH_EINVAL, "null handle");
+    const int mt = h->eng->eig_con_total();
+    if (ncon_total) *ncon_total = mt;
+    if (implicit_constant) *implicit_constant = (mt > 0 && h->eng->ns_on()) ? 1 : 0;
+    if (bytes) *bytes = (long)h->eng->eig_con_bytes();
+    return SPARSH_OK;
+}
+
+int sparsh_op_eig_con_project(sparsh_handle h, int n, int k, int m, const double *Y, const double *BY, const double *Ginv, const double *V,
+                              double *Vout, double *C)
+{
+    if (!h || !h->eng) return fail(SPARSH_EINVAL, "null handle");
+    if (n <= 0) return fail(SPARSH_EINVAL, "n <= 0");
+    REQUIRE_READY(h);
+    REQUIRE_SINGLE(h);
+    if (k < 1 || k > SPARSH_MAX_RHS) return fail(SPARSH_EINVAL, "k must be 1 .. SPARSH_MAX_RHS (8)");
+    if (m < 1 || m > kEigConMax) return fail(SPARSH_EINVAL, "m must be 1 .. 17");
+    if (!Y || !BY || !Ginv || !V || !Vout || !C) return fail(SPARSH_EINVAL, "NULL array");
+    Engine &E = *h->eng;
+    const int W = multi_width(k), nblk = (m + W - 1) / W;
+    const size_t len = (size_t)n * W;
+    DBuf stage(E, (size_t)n * W), by(E, len * nblk), bby(E, len * nblk), bv(E, len), bo(E, len), dg(E, (size_t)m * m, Ginv),
+        dc(E, (size_t)nblk * W * W), part(E, (size_t)nblk * W * W * eig_grid(n, W));
+    if (!stage.p || !by.p || !bby.p || !bv.p || !bo.p || !dg.p || !dc.p || !part.p) return fail(SPARSH_ENODEV, "device allocation or H2D copy failed");
+    bool ok = true;
+    auto put = [&](const double *src, int first, int cols, double *blk) {  // columns first .. first + cols - 1 of a host array -> a block
+        ok = ok && hipMemcpy(stage.p, src + (size_t)first * n, (size_t)n * cols * 8, hipMemcpyHostToDevice) == hipSuccess;
+        if (ok) launch_interleave(n, cols, W, stage.p, n, blk, E.stream());
+        ok = ok && hipStreamSynchronize(E.stream()) == hipSuccess;
+    };
+    for (int b = 0; b < nblk; ++b) {
+        put(Y, b * W, std::min(W, m - b * W), by.p + b * len);
+        put(BY, b * W, std::min(W, m - b * W), bby.p + b * len);
+    }
+    put(V, 0, k, bv.p);
+    if (!ok) return fail(SPARSH_ENODEV, "device allocation or H2D copy failed");
+    double *dst = Vout == V ? bv.p : bo.p;  // V == Vout on the host: in place on the device too
+    launch_eig_con_project(n, W, m, by.p, bby.p, dg.p, bv.p, dst, dc.p, part.p, E.stream());
+    // the padding columns of the block that comes back must still hold zeros (a lane stores both columns of its pair, so they cannot
+    // carry a sentinel through the launch)
+    std::vector<double> full(len), cfull((size_t)nblk * W * W);
+    (void)hipStreamSynchronize(E.stream());
+    ok = hipMemcpy(full.data(), dst, len * 8, hipMemcpyDeviceToHost) == hipSuccess && dc.get(cfull.data());
+    if (!ok) return done(E, false);
+    for (size_t i = 0; i < (size_t)n; ++i) {
+        for (int c = 0; c < k; ++c) Vout[(size_t)c * n + i] = full[i * W + c];
+        for (int c = k; c < W; ++c)
+            if (full[i * W + c] != 0.0) return fail(SPARSH_ENUMERIC, "a padding column of the projected block is not zero");
+    }
+    for (int j = 0; j < m; ++j)
+        for (int c = 0; c < k; ++c) C[j * k + c] = cfull[(size_t)j * W + c];
+    return done(E, true);
 }
 
 int sparsh_debug_eig_small(int m, int k, const double *GA, const double *GB, double *theta, double *C)

@@ -104,4 +104,46 @@ int eig_small(int m, int k, const double *GA, const double *GB, double *theta, d
     return 0;
 }
 
+int eig_spd_inverse(int m, const double *G, double *Ginv)
+{
+    constexpr int M = kEigSmallMax;
+    if (m < 1 || m > M) return 1;
+    double d[M], L[M][M], Z[M][M];
+    auto up = [m](const double *A, int i, int j) { return i <= j ? A[i * m + j] : A[j * m + i]; };
+    for (int i = 0; i < m; ++i) {
+        const double g = G[i * m + i];
+        if (!(g > 0.0) || !std::isfinite(g)) return 1;
+        d[i] = 1.0 / std::sqrt(g);
+    }
+    for (int i = 0; i < m; ++i)  // the Cholesky factor and breakdown rule of eig_small
+        for (int j = 0; j <= i; ++j) {
+            double s = d[i] * up(G, i, j) * d[j];
+            for (int p = 0; p < j; ++p) s -= L[i][p] * L[j][p];
+            if (i == j) {
+                const double piv = s > 0.0 ? std::sqrt(s) : 0.0;
+                if (!(piv >= kEigBreakdownPivot)) return 1;
+                L[i][i] = piv;
+            } else {
+                L[i][j] = s / L[j][j];
+            }
+        }
+    // L Z' = I forward, then L^T Z = Z' backward, column by column
+    for (int j = 0; j < m; ++j) {
+        double z[M];
+        for (int i = 0; i < m; ++i) {
+            double s = i == j ? 1.0 : 0.0;
+            for (int p = 0; p < i; ++p) s -= L[i][p] * z[p];
+            z[i] = s / L[i][i];
+        }
+        for (int i = m - 1; i >= 0; --i) {
+            double s = z[i];
+            for (int p = i + 1; p < m; ++p) s -= L[p][i] * Z[p][j];
+            Z[i][j] = s / L[i][i];
+        }
+    }
+    for (int i = 0; i < m; ++i)
+        for (int j = 0; j < m; ++j) Ginv[i * m + j] = d[i] * (0.5 * (Z[i][j] + Z[j][i])) * d[j];
+    return 0;
+}
+
 }  // namespace sparsh

@@ -14,4 +14,9 @@ constexpr double kEigBreakdownPivot = 1e-7;   // a Cholesky pivot of the scaled 
 // (a condition number near 1e14 of the scaled Gram matrix: past it the Ritz values carry no digits).  Nothing is written then.
 int eig_small(int m, int k, const double *GA, const double *GB, double *theta, double *C);
 
+// The inverse of the symmetric positive definite G of order m <= 24 (row-major; only the upper triangle is read) by the scaling and
+// Cholesky factorisation above and two triangular solves per column: Ginv = D L^-T L^-1 D, symmetrised.  Returns 0, or 1 under the
+// breakdown rule above (G is then numerically rank deficient); nothing is written then.
+int eig_spd_inverse(int m, const double *G, double *Ginv);
+
 }  // namespace sparsh

@@ -423,6 +423,18 @@ public:
                      int *status, double *seconds);
     // hook: Y = B X on column-major device arrays through the block SpMV on the stored B
     int op_eig_b_multi(int nrhs, const double *X, double *Y);
+    // ---- eigenpairs under constraints: the nev lowest pairs in the B-orthogonal complement of the ncon columns of Y (column-major
+    // device array, ldy >= n0(); nullptr with ncon = 0), gen as in eigs_dev / eigs_gen_dev.  A null-space handle is accepted and gets
+    // the constant vector as one more constraint.  Without any constraint the call is eigs_dev / eigs_gen_dev.  The constraint blocks
+    // (Y, B Y when gen, the small matrices) are the solver's own, reserved per (width, count, gen) on top of eig_reserve's, dropped with
+    // them and never counted in eig_bytes().
+    int eigs_con_dev(bool gen, int nev, double *X, long ldx, int ncon, const double *Y, long ldy, double tol, int max_iters, double *lambda,
+                     double *hist, int hist_cap, int *iters, int *status, double *seconds);
+    const char *eig_con_refusal() const;  // multi_refusal() without its refusal of null-space handles
+    int eig_con_total() const { return con_mt_; }
+    size_t eig_con_bytes() const { return con_bytes_; }
+    // bench: one projection (the Gram launch with its finalise, then the apply kernel) of the resident W block with the constraints the last constrained solve left
+    int bench_eig_con_launch();
 
     // device memory helpers
     void *dalloc(size_t bytes);
@@ -586,8 +598,23 @@ private:
     // G = [S^T S, S^T A S, residual norms] and coef = [Cx, Cw, Cp, theta]
     void eig_forget();  // the buffers went with allocs_ (setup): drop the pointers
     void eig_gram_pairs(GramPairs &prs, bool gen = false) const;
+    struct EigCon {  // the caller's constraints of one solve (device, column-major)
+        int ncon = 0;
+        const double *Y = nullptr;
+        long ldy = 0;
+    };
     int eigs_run(bool gen, int nev, double *X, long ldx, double tol, int max_iters, double *lambda, double *hist, int hist_cap, int *iters,
-                 int *status, double *seconds);
+                 int *status, double *seconds, const EigCon *con = nullptr);
+    int eig_con_reserve(int mt, bool gen);  // after eig_reserve: the constraint blocks for mt constraints at width ew_
+    void eig_con_release();
+    void eig_con_forget();  // the constraint blocks went with allocs_ (setup) or were freed: drop the pointers
+    void eig_con_project(const double *src, double *dst);  // dst = Pi src on blocks of width ew_ (dst may be src)
+    int con_mt_ = 0;        // constraints the blocks below were reserved for (0: none)
+    bool con_gen_ = false;  // with B Y blocks of their own
+    size_t con_bytes_ = 0;
+    double *cY_ = nullptr, *cBY_ = nullptr;  // ceil(mt / W) interleaved blocks each; cBY_ == cY_ for the standard problem
+    double *cG_ = nullptr, *cGinv_ = nullptr, *cC_ = nullptr;  // Y^T B Y (padded order), its inverse (order mt), (BY)^T V
+    std::vector<void *> con_allocs_;
     void eig_b_spmv(const double *x, double *y);  // y = B x on interleaved blocks of width ew_
     void eig_b_forget();                          // B went with allocs_ (setup): drop the pointers
     void eig_update(bool gen, int k);             // step 6 in place on the resident blocks

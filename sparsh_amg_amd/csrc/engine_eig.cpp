@@ -32,13 +32,72 @@ void Engine::eig_forget()
     eig_allocs_.clear();
     eX_ = eAX_ = eW_ = eAW_ = eP_ = eAP_ = eR_ = epart_ = eG_ = ecoef_ = nullptr;
     eBX_ = eBW_ = eBP_ = nullptr;
+    eig_con_forget();
+}
+
+void Engine::eig_con_forget()
+{
+    con_mt_ = 0;
+    con_gen_ = false;
+    con_bytes_ = 0;
+    con_allocs_.clear();
+    cY_ = cBY_ = cG_ = cGinv_ = cC_ = nullptr;
 }
 
 void Engine::eig_release()
 {
-    if (st_ && !eig_allocs_.empty()) (void)hipStreamSynchronize(st_);
+    if (st_ && !(eig_allocs_.empty() && con_allocs_.empty())) (void)hipStreamSynchronize(st_);
     for (void *p : eig_allocs_) dfree(p);
+    for (void *p : con_allocs_) dfree(p);
     eig_forget();
+}
+
+void Engine::eig_con_release()
+{
+    if (st_ && !con_allocs_.empty()) (void)hipStreamSynchronize(st_);
+    for (void *p : con_allocs_) dfree(p);
+    eig_con_forget();
+}
+
+// the constraint blocks of one call shape (width ew_, mt constraints, B Y beside Y or not); another shape replaces them
+int Engine::eig_con_reserve(int mt, bool gen)
+{
+    if (mt == con_mt_ && gen == con_gen_) return SPARSH_OK;
+    eig_con_release();
+    const int W = ew_, nblk = (mt + W - 1) / W, mpad = nblk * W;
+    bool ok = true;
+    auto take = [&](size_t doubles) -> double * {
+        if (!ok) return nullptr;
+        const size_t bytes = doubles * 8;
+        double *p = static_cast<double *>(dalloc(bytes));
+        if (!p || !check(hipMemsetAsync(p, 0, bytes, st_), "hipMemsetAsync")) {
+            if (p) dfree(p);
+            ok = false;
+            return nullptr;
+        }
+        con_allocs_.push_back(p);
+        con_bytes_ += bytes;
+        return p;
+    };
+    const size_t len = (size_t)lev_[0].n * W;
+    cY_ = take(len * nblk);
+    cBY_ = gen ? take(len * nblk) : cY_;
+    cG_ = take((size_t)mpad * mpad);
+    cGinv_ = take((size_t)mt * mt);
+    cC_ = take((size_t)mpad * W);
+    if (!ok) {
+        eig_con_release();
+        return SPARSH_ENODEV;
+    }
+    con_mt_ = mt;
+    con_gen_ = gen;
+    return SPARSH_OK;
+}
+
+// (the Gram partials are free wherever the loop projects: the launches that filled them last have been read out on the stream)
+void Engine::eig_con_project(const double *src, double *dst)
+{
+    launch_eig_con_project(lev_[0].n, ew_, con_mt_, cY_, cBY_, cGinv_, src, dst, cC_, epart_, st_);
 }
 
 int Engine::eig_reserve(int nev)
@@ -138,6 +197,16 @@ int Engine::eigs_gen_dev(int nev, double *X, long ldx, double tol, int max_iters
     return eigs_run(true, nev, X, ldx, tol, max_iters, lambda, hist, hist_cap, iters, status, seconds);
 }
 
+int Engine::eigs_con_dev(bool gen, int nev, double *X, long ldx, int ncon, const double *Y, long ldy, double tol, int max_iters, double *lambda,
+                         double *hist, int hist_cap, int *iters, int *status, double *seconds)
+{
+    EigCon con;
+    con.ncon = ncon;
+    con.Y = Y;
+    con.ldy = ldy;
+    return eigs_run(gen, nev, X, ldx, tol, max_iters, lambda, hist, hist_cap, iters, status, seconds, &con);
+}
+
 // step 6 in place on the resident blocks
 void Engine::eig_update(bool gen, int k)
 {
@@ -151,17 +220,25 @@ void Engine::eig_update(bool gen, int k)
     launch_eig_update_gen(n, ew_, k, in, ecoef_, out, st_);
 }
 
-// the loop of both solvers.  gen: the pencil (A, B) with B S carried beside A S; the standard solve's launches are those it always had
+// the loop of both solvers.  gen: the pencil (A, B) with B S carried beside A S; the standard solve's launches are those it always had.
+// con: the constrained entry points, which take null-space handles (the constant vector is then one more constraint); with no
+// constraint at all the launches are those of con == nullptr
 int Engine::eigs_run(bool gen, int nev, double *X, long ldx, double tol, int max_iters, double *lambda, double *hist, int hist_cap, int *iters,
-                     int *status, double *seconds)
+                     int *status, double *seconds, const EigCon *con)
 {
     if (!ready_) {
         error = "sparsh_setup has not been called";
         return SPARSH_ESTATE;
     }
     if (fault_ != SPARSH_OK) return fault_;
-    if (const char *why = multi_refusal()) {
+    if (const char *why = con ? eig_con_refusal() : multi_refusal()) {
         error = why;
+        return SPARSH_EINVAL;
+    }
+    const int ncon = con ? con->ncon : 0;
+    const int mt = con ? ncon + (ns_on() ? 1 : 0) : 0;  // constraints in all
+    if (ncon < 0 || mt > kEigConMax || nev + mt > lev_[0].n || (ncon > 0 && (!con->Y || con->ldy < lev_[0].n))) {
+        error = "bad constraints: at most SPARSH_MAX_CON columns of n rows, and nev + their number must not exceed n";
         return SPARSH_EINVAL;
     }
     if (gen && !eb_set_) {
@@ -170,6 +247,8 @@ int Engine::eigs_run(bool gen, int nev, double *X, long ldx, double tol, int max
     }
     if (int rc = multi_reserve(nev); rc != SPARSH_OK) return rc;  // the cycle's own blocks
     if (int rc = gen ? eig_reserve_gen(nev) : eig_reserve(nev); rc != SPARSH_OK) return rc;
+    if (mt > 0)
+        if (int rc = eig_con_reserve(mt, gen); rc != SPARSH_OK) return rc;
     if (max_iters <= 0) max_iters = prm_.max_iter;
     const int W = ew_, n = lev_[0].n, k = nev, ld = 3 * W;
     const size_t len = (size_t)n * W;
@@ -238,7 +317,55 @@ int Engine::eigs_run(bool gen, int nev, double *X, long ldx, double tol, int max
 
     // 1. start: AX = A X, Rayleigh-Ritz on (X^T AX, X^T X), X <- X C, AX <- AX C; no P yet
     for (int c = 0; c < k; ++c) iters[c] = 0, status[c] = SPARSH_OK;
+    if (mt > 0) {
+        // the constraints: Y in blocks of width W (a null-space handle's column of ones last), BY = B Y, G = Y^T (BY) from the Gram
+        // launch, its inverse from the host: the one extra host read of a constrained call
+        const int nblk = (mt + W - 1) / W, mpad = nblk * W;
+        for (int b = 0; b < nblk; ++b) {
+            const int cols = std::min(W, ncon - b * W);
+            if (cols > 0) launch_interleave(n, cols, W, con->Y + (size_t)b * W * con->ldy, con->ldy, cY_ + b * len, st_);
+            else HIPCHK(hipMemsetAsync(cY_ + b * len, 0, len * 8, st_));
+        }
+        if (mt > ncon) launch_eig_con_fill_column(n, W, ncon % W, 1.0, cY_ + (size_t)(ncon / W) * len, st_);
+        if (gen)
+            for (int b = 0; b < nblk; ++b) eig_b_spmv(cY_ + b * len, cBY_ + b * len);
+        GramPairs cp{};
+        int np = 0;
+        auto flush = [&]() {
+            if (np > 0) launch_gram_multi(n, W, np, cp, epart_, cG_, mpad, st_);
+            np = 0;
+        };
+        for (int bi = 0; bi < nblk; ++bi)
+            for (int bj = bi; bj < nblk; ++bj) {  // the upper block triangle, at most kEigPairs pairs per launch
+                cp.u[np] = cY_ + bi * len;
+                cp.v[np] = cBY_ + bj * len;
+                cp.dst[np] = bi * W * mpad + bj * W;
+                if (++np == kEigPairs) flush();
+            }
+        flush();
+        HIPCHK(hipMemcpyAsync(down, cG_, (size_t)mpad * mpad * 8, hipMemcpyDeviceToHost, st_));
+        HIPCHK(hipStreamSynchronize(st_));
+        if (fault_ != SPARSH_OK) {
+            stop_clock();
+            return fault_;
+        }
+        double Gc[kEigConMax * kEigConMax], Gi[kEigConMax * kEigConMax];
+        for (int i = 0; i < mt; ++i)
+            for (int j = 0; j < mt; ++j) Gc[i * mt + j] = down[std::min(i, j) * mpad + std::max(i, j)];
+        // constraints that cannot be used are not left in force: sparsh_eig_con_info reports zeros again
+        if (!finite(Gc, mt * mt)) {
+            eig_con_release();
+            return numeric(gen ? "NaN in the constraints or in B times the constraints" : "NaN in the constraints");
+        }
+        if (eig_spd_inverse(mt, Gc, Gi) != 0) {
+            eig_con_release();
+            return numeric("the constraints are rank deficient");
+        }
+        std::copy(Gi, Gi + mt * mt, down);  // (the next device write to `down` follows this upload on the stream)
+        HIPCHK(hipMemcpyAsync(cGinv_, down, (size_t)mt * mt * 8, hipMemcpyHostToDevice, st_));
+    }
     launch_interleave(n, k, W, X, ldx, eX_, st_);
+    if (mt > 0) eig_con_project(eX_, eX_);  // X <- Pi X before AX and BX are formed
     for (double *b : {eW_, eAW_, eP_, eAP_}) HIPCHK(hipMemsetAsync(b, 0, len * 8, st_));
     if (gen)
         for (double *b : {eBW_, eBP_}) HIPCHK(hipMemsetAsync(b, 0, len * 8, st_));
@@ -268,7 +395,8 @@ int Engine::eigs_run(bool gen, int nev, double *X, long ldx, double tol, int max
         if (!last) {
             // 3. W = M R, AW = A W ; 4. the Gram matrices of S = [X, W, P] and A S
             vcycle_multi(eR_);
-            HIPCHK(hipMemcpyAsync(eW_, mlev_[0].x, len * 8, hipMemcpyDeviceToDevice, st_));
+            if (mt > 0) eig_con_project(mlev_[0].x, eW_);  // W <- Pi (M R): the projection stands in for the copy
+            else HIPCHK(hipMemcpyAsync(eW_, mlev_[0].x, len * 8, hipMemcpyDeviceToDevice, st_));
             multi_spmv_dot(0, eW_, eAW_, mpart0_);
             if (gen) eig_b_spmv(eW_, eBW_);
             launch_gram_multi(n, W, kEigPairs, prs, epart_, eG_, ld, st_);
@@ -344,6 +472,12 @@ int Engine::bench_eig_launch(int op)
     } else {
         launch_eig_update(n, ew_, ew_, eX_, eW_, eP_, eAX_, eAW_, eAP_, ecoef_, eX_, eP_, eAX_, eAP_, st_);
     }
+    return SPARSH_OK;
+}
+
+int Engine::bench_eig_con_launch()
+{
+    eig_con_project(eW_, eW_);
     return SPARSH_OK;
 }
 

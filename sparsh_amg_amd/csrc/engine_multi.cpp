@@ -14,13 +14,21 @@ namespace sparsh {
 
 #define HIPCHK(call) note_hip((call), #call)
 
-const char *Engine::multi_refusal() const
+const char *Engine::eig_con_refusal() const
 {
     if (dist_ || (comm_ && comm_->size > 1)) return "block solves are not available on a partitioned (multi-GPU) handle";
     if (prm_.precond_fp32) return "block solves run the fp64 cycle only: params.precond_fp32 is not supported";
     if (cycle_kind_ != SPARSH_CYCLE_V) return "block solves run the V-cycle only: select SPARSH_CYCLE_V (sparsh_set_cycle)";
     if (!jacobi_on()) return "block solves run the Jacobi cycle only: select SPARSH_SMOOTH_JACOBI";
-    if (ns_on()) return "block solves are not available on a handle set up with a null space (SPARSH_NULLSPACE_CONSTANT)";
+    return nullptr;
+}
+
+const char *Engine::multi_refusal() const
+{
+    if (const char *why = eig_con_refusal()) return why;
+    if (ns_on())
+        return "block solves are not available on a handle set up with a null space (SPARSH_NULLSPACE_CONSTANT); its eigenpairs: "
+               "sparsh_eigs_con";
     return nullptr;
 }
 

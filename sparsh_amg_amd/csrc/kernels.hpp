@@ -421,6 +421,7 @@ void launch_gmres_solve(int k, const GmresState &s, hipStream_t st);
 // element (row i, column c) at v[i * W + c].  Per column the arithmetic is that of the single-vector kernels above; reducing launches
 // write one partial per column and workgroup to partial[c * nblk + workgroup] and return nblk.
 constexpr int kMultiMax = 8;  // SPARSH_MAX_RHS
+constexpr int kMultiGridMax = 2048;  // workgroups of a grid-stride elementwise block kernel: ~8 per CU
 inline int multi_width(int nrhs) { return nrhs <= 2 ? 2 : (nrhs <= 4 ? 4 : 8); }
 struct MultiArgs {
     const double *x = nullptr;  // input block (gathered)
@@ -493,5 +494,16 @@ void launch_eig_residual_gen(int n, int W, const double *AX, const double *BX, c
 // launch_eig_update with B S carried along.  in = X, W, P, AX, AW, AP, BX, BW, BP; out = X', P', AX', AP', BX', BP' with BP' = BW Cw + BP Cp
 // and BX' = BX Cx + BP'.  An output may be the block it replaces.
 void launch_eig_update_gen(int n, int W, int k, const double *const in[9], const double *coef, double *const out[6], hipStream_t st);
+
+// ---- constraints of the LOBPCG eigensolver (eig_con_kernels.hip).  The mt <= kEigConMax constraints are ceil(mt / W) interleaved
+// blocks of width W, block b at Y + b * n * W, constraint j in column j % W of block j / W, zeros past mt.
+constexpr int kEigConMax = 17;  // SPARSH_MAX_CON and the implicit constant of a null-space handle
+// dst = src - Y Ginv (BY)^T src by the Gram launch with its finalise and one more kernel: C = (BY)^T src (mt x W row-major; room for ceil(mt / W) * W * W doubles) by the Gram
+// launch (partial: ceil(mt / W) * W * W * eig_grid(n, W) doubles), then the apply with coef = Ginv C (Ginv mt x mt row-major, device)
+// formed by every workgroup, sums over j ascending.  dst may be src; BY may be Y.
+void launch_eig_con_project(int n, int W, int mt, const double *Y, const double *BY, const double *Ginv, const double *src, double *dst,
+                            double *C, double *partial, hipStream_t st);
+// column col of the interleaved block v <- value
+void launch_eig_con_fill_column(int n, int W, int col, double value, double *v, hipStream_t st);
 
 }  // namespace sparsh

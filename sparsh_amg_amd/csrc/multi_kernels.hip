@@ -18,8 +18,6 @@ namespace sparsh {
 
 namespace {
 
-constexpr int kMultiGridMax = 2048;  // grid-stride elementwise kernels: ~8 workgroups per CU
-
 inline int multi_grid(size_t elements)
 {
     size_t g = (elements + kBlock * 2 - 1) / (kBlock * 2);

@@ -61,6 +61,32 @@ def poisson3d_neumann(nx: int, ny: int | None = None, nz: int | None = None):
     return rp, ci, v
 
 
+def dumbbell_laplacian(a: int, bridge: int):
+    """Graph Laplacian (off-diagonal entries -1, the diagonal the degree) of two a x a x a grid cubes joined by a corridor of
+    ``bridge`` points, one point wide, which runs from the last point of cube 1 to the first point of cube 2.  Order: cube 1
+    lexicographic (x fastest), the corridor, cube 2 lexicographic.  Returns ``(rowptr, col, val, degrees)``.  Singular: the constant
+    vector spans the null space, and the sign of the Fiedler vector separates the cubes."""
+    a, bridge = int(a), int(bridge)
+    if a < 1 or bridge < 0:
+        raise ValueError("a >= 1 and bridge >= 0")
+    m = a ** 3
+    n = 2 * m + bridge
+    rp, ci, _ = _stencil_csr((a, a, a), 0.0)
+    rows = np.repeat(np.arange(m, dtype=np.int64), np.diff(rp))
+    off = ci != rows
+    r1, c1 = rows[off], ci[off].astype(np.int64)
+    chain = np.concatenate([[m - 1], m + np.arange(bridge, dtype=np.int64), [m + bridge]])  # last of cube 1 .. first of cube 2
+    er = np.concatenate([r1, r1 + m + bridge, chain[:-1], chain[1:]])
+    ec = np.concatenate([c1, c1 + m + bridge, chain[1:], chain[:-1]])
+    deg = np.bincount(er, minlength=n).astype(np.float64)
+    er, ec = np.concatenate([er, np.arange(n)]), np.concatenate([ec, np.arange(n)])
+    ev = np.concatenate([np.full(len(er) - n, -1.0), deg])
+    order = np.lexsort((ec, er))
+    rowptr = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(np.bincount(er, minlength=n), out=rowptr[1:])
+    return rowptr.astype(np.int32), ec[order].astype(np.int32), ev[order], deg
+
+
 def _morton_order(pts):
     """Z-order (Morton) rank of 2D points in the unit square, 16 bits per axis."""
     q = np.minimum((pts * 65536.0).astype(np.uint64), 65535)

@@ -3,6 +3,7 @@ beside the block path's, and the rate of the new kernels against the copy rate D
 
     python tools/eig_ab.py [--out profiles/eig_lobpcg.txt] [--reps 20] [--step-seconds 420] [--max-iters 300]
     python tools/eig_ab.py --generalised [--out profiles/eig_gen_lobpcg.txt]
+    python tools/eig_ab.py --constrained [--out profiles/eig_con_lobpcg.txt]
 
 Cases: poisson3d(216) with k = 4 and k = 8 under set_kernel_config(kind=0), fem_unstructured() with k = 4.  Every case runs in a
 process of its own under `timeout`; the first case that fails stops the rest.  Per case one JSON line:
@@ -19,6 +20,16 @@ standard solve of the same operator (cases fem:k, which end at the cap: DESIGN.m
   update_gen_us, b_spmv_us                       sparsh_bench_op_multi ops 4 and 5 on the solver's resident blocks
   update_gen_TBps, update_gen_of_copy_rate       15 block passes (9 in, 6 out) over the measured time
 and their eig_kernels_share counts the Gram launch, the generalised update and the residual as 4 / 15 of that update.
+--constrained: eigs_con_dev (constraints).  Case femcon:8: the full-size FEM pencil, eigs_gen_dev(8) and then
+eigs_con_dev(8) with its eight vectors as constraints (pairs 9..16).  Case neu216:8: poisson3d_neumann(216) set up with the constant
+null space, eigs_con_dev(8) with the implicit constant vector alone.  Per case:
+  first_iterations, first_rc                     femcon only: the unconstrained first solve
+  iterations, ms_per_iteration, rc               the constrained solve (the second of two calls)
+  mt, mpad, con_bytes                            constraints in all, rounded up to the width, the bytes sparsh_eig_con_info counts
+  project_us                                     sparsh_bench_op_multi op 7: one projection (Gram launch, its finalise, apply kernel) on the resident blocks
+  project_model_us, project_over_model           the byte model: the Gram launch reads n (mpad + W) 8 B, the apply reads the same and
+                                                 writes n W 8 B, at 6.29 TB/s; gen reads Y and BY, the model counts mpad once per launch
+  project_share                                  project_us over one iteration of the constrained solve
 """
 import argparse
 import json
@@ -34,6 +45,56 @@ sys.path.insert(0, ROOT)
 COPY_BYTES_PER_S = 6.29e12  # the device-to-device copy rate DESIGN.md measures kernels against
 CASES = ["p216:4", "p216:8", "fem:4"]
 CASES_GENERALISED = ["fem:4", "femgen:4", "fem:8", "femgen:8"]
+CASES_CONSTRAINED = ["femcon:8", "neu216:8"]
+
+
+def run_case_constrained(case, reps, max_iters):
+    import sparsh_amg_amd as sa
+    from sparsh_amg_amd import problems
+
+    name, k = case.split(":")
+    k = int(k)
+    gen = name == "femcon"
+    if gen:
+        (rp, ci, v), M = problems.fem_pencil()
+    else:
+        rp, ci, v = problems.poisson3d_neumann(216)
+    n = len(rp) - 1
+    A = sa.sp_matrix_mg(rp, ci, v)
+    if not gen:
+        A.set_nullspace("constant")
+    A.setup(sa.default_params(print_setup=0, print_solve=0))
+    if gen:
+        A.set_eig_b(*M)
+    W = 2 if k <= 2 else (4 if k <= 4 else 8)
+    X0 = np.ascontiguousarray(np.random.default_rng(0).standard_normal((n, k)).T)  # (k, n) row-major = column-major (n, k)
+    xd, yd = A.dev_alloc(8 * n * k), A.dev_alloc(8 * n * k)
+    rec = {"case": case, "rows": n, "nnz": int(rp[-1]), "k": k, "width": W, "levels": A.nlevels}
+    ncon = 0
+    if gen:  # the first block of pairs, left on the device as the constraints of the second
+        A.h2d(yd, X0)
+        lam1, _, hist1, _, sec1, rc1 = A.eigs_gen_dev(k, yd, n, max_iters=max_iters, hist_cap=max_iters + 1)
+        rec.update(first_rc=int(rc1), first_iterations=hist1.shape[1] - 1, first_seconds=round(sec1, 4), first_lam=[float(x) for x in lam1])
+        ncon = k
+    for _ in range(2):  # the first call reserves the blocks
+        A.h2d(xd, X0)
+        lam, iters, hist, status, sec, rc = A.eigs_con_dev(k, xd, n, ncon=ncon, Y_dev=yd if ncon else None, ldy=n, gen=gen,
+                                                          max_iters=max_iters, hist_cap=max_iters + 1)
+    its = hist.shape[1] - 1
+    info = A.eig_con_info()
+    mt = info["ncon_total"]
+    mpad = -(-mt // W) * W
+    rec.update(rc=int(rc), iterations=its, seconds=round(sec, 4), ms_per_iteration=round(sec * 1e3 / max(its, 1), 4),
+               lam=[float(x) for x in lam], restarts=A.eig_info()["restarts"], mt=mt, mpad=mpad, implicit_constant=info["implicit_constant"],
+               con_bytes=info["bytes"], eig_bytes=A.eig_info()["bytes"])
+    t = A.bench_op_multi("eig_con_project", 0, nrhs=k, reps=reps)
+    model = (2 * 8.0 * n * (mpad + W) + 8.0 * n * W) / COPY_BYTES_PER_S
+    rec.update(project_us=round(t * 1e6, 2), project_model_us=round(model * 1e6, 2), project_over_model=round(t / model, 3),
+               project_share=round(t / (sec / max(its, 1)), 4))
+    A.dev_free(xd)
+    A.dev_free(yd)
+    A.close()
+    print(json.dumps(rec), flush=True)
 
 
 def run_case(case, reps, max_iters):
@@ -99,17 +160,19 @@ def main():
     ap.add_argument("--step-seconds", type=int, default=420)
     ap.add_argument("--max-iters", type=int, default=300, help="the iteration cap of every solve")
     ap.add_argument("--generalised", action="store_true", help="the FEM pencil against its mass matrix, next to the standard solve")
+    ap.add_argument("--constrained", action="store_true", help="eigs_con_dev: deflation on the FEM pencil, the singular Neumann box")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "eig_gen_lobpcg.txt" if args.generalised else "eig_lobpcg.txt")
+        args.out = os.path.join(ROOT, "profiles", "eig_con_lobpcg.txt" if args.constrained else
+                                ("eig_gen_lobpcg.txt" if args.generalised else "eig_lobpcg.txt"))
     if args.case:
-        run_case(args.case, args.reps, args.max_iters)
+        (run_case_constrained if args.constrained else run_case)(args.case, args.reps, args.max_iters)
         return 0
     lines = []
-    for case in (CASES_GENERALISED if args.generalised else CASES):  # the driver itself never opens the GPU
+    for case in (CASES_CONSTRAINED if args.constrained else (CASES_GENERALISED if args.generalised else CASES)):  # the driver itself never opens the GPU
         cmd = ["timeout", "-k", "10", str(args.step_seconds), sys.executable, os.path.abspath(__file__), "--case", case, "--reps", str(args.reps),
-               "--max-iters", str(args.max_iters)]
+               "--max-iters", str(args.max_iters)] + (["--constrained"] if args.constrained else [])
         p = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
         sys.stdout.write(p.stdout)
         if p.returncode != 0:  # (a solve that ends at the cap is a result, SPARSH_ENOCONV in "rc", not a failure)
