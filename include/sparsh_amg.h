@@ -39,6 +39,7 @@ extern "C" {
 #define SPARSH_GMRES 5  /* restarted GMRES without a preconditioner (sparsh_set_gmres) */
 #define SPARSH_PGMRES 6 /* restarted GMRES, right-preconditioned with one V-cycle from a zero guess: the z = M v of SPARSH_PBICG */
 #define SPARSH_FCG 7    /* flexible preconditioned CG (Notay's FCG(1)): the Krylov method that takes the K-cycle; see "W- and K-cycles" below */
+#define SPARSH_BCG 8    /* block conjugate gradients: sparsh_solve_multi / sparsh_solve_multi_dev only; see "block CG" below */
 
 /* Smoother of the V-cycle (sparsh_set_smoother). */
 #define SPARSH_SMOOTH_JACOBI 0  /* weighted Jacobi, parallel::jacobi_smoother (default) */
@@ -674,7 +675,7 @@ int sparsh_op_project_dev(sparsh_handle h, int n, double *x_dev, const double *r
  * (row sums in stored order, the epilogues of the Jacobi cycle, the recurrences of SPARSH_PCG); the cycle is the plain Jacobi
  * V(nu,nu) cycle from a zero guess with nothing fused, so column c follows sparsh_solve(SPARSH_PCG) of the same right-hand side up to
  * the last bits of the reductions and of the box-grid kernels' fused launches.
- * method: SPARSH_PCG only.  X: initial guesses in, solutions out.  hist[c * hist_cap + k] = column c's residual after iteration
+ * method: SPARSH_PCG here (SPARSH_BCG: the coupled loop described further below).  X: initial guesses in, solutions out.  hist[c * hist_cap + k] = column c's residual after iteration
  * k + 1; entries from iters[c] on are left untouched.  iters / status: nrhs ints each.  All scalars stay on the device, one set per
  * column; a column whose residual is <= tol (at the start or after an iteration) is frozen there and then: its x and r are never
  * written again (predicated writes) and its iteration count stands, so it ends with the iterate a single solve with check_every = 1
@@ -713,6 +714,47 @@ int sparsh_op_precond_multi(sparsh_handle h, int nrhs, const double *R, double *
  * 5 = the block SpMV with B; 7 = one projection of the constrained eigensolver (the Gram launch with its finalise, then the apply kernel) of the resident W block with the
  * constraints the last constrained solve left resident (SPARSH_ESTATE unless one of this width has run).  6 is not assigned. */
 int sparsh_bench_op_multi(sparsh_handle h, int op, int level, int nrhs, int reps, double *avg_seconds);
+
+/* ---- block CG: the columns of a block share one search space ----
+ * sparsh_solve_multi / sparsh_solve_multi_dev with method SPARSH_BCG: O'Leary's block conjugate gradients with the block V-cycle as
+ * preconditioner.  Every column minimises over the union of all columns' search directions, which buys iterations where the
+ * preconditioner is weak (the unstructured FEM problem) and little where it is good (box grids).  Arguments, refusals, memory rules
+ * and the column-major interface are those of the block PCG call; SPARSH_PCG through those calls keeps its bits, launches and bytes.
+ * Notation: W = the block width, k = nrhs, padding columns are zero.  Every product and sum is rounded on its own; sums over columns
+ * run with c ascending.
+ *   R = B - A X ; Z = M R ; P = Z ; then per iteration
+ *   Q = A P (block SpMV) ; G = P^T Q and C1 = P^T R (one Gram launch, two pairs) ; alpha = pinv(G) C1 (one wavefront) ;
+ *   X += P alpha ; R -= Q alpha ; rn_c = ||R_c|| (one pass; partial sums added in a fixed order by the finalise, no atomics) ;
+ *   hist, done = all rn_c <= tol ; Z = M R ; C2 = Q^T Z (Gram launch, one pair) ; beta = -pinv(G) C2 (the factor kept) ;
+ *   P = Z + P beta (one pass).
+ * pinv: LDL^T of G (upper triangle read) without square roots and with dropped directions: d_j = g_jj - sum_{m<j, kept} l_jm^2 d_m;
+ * column j is kept iff g_jj > 0 and d_j > 1e-14 g_jj, else its row of the coefficient matrix is zero and it takes no part in later
+ * steps; l_ij = (g_ij - sum_{m<j, kept} l_im l_jm d_m) / d_j; forward, diagonal and backward substitution on the kept set.  A block
+ * with equal, dependent, zero or converged columns therefore loses rank, not the solve.
+ * Nothing is frozen: the loop ends at the first iteration whose recurrence residuals are all <= tol (read back every
+ * params.check_every iterations; the kernels of iterations queued past that point leave at once).  iters[c]: the iterations run, the
+ * same for every column, 0 if every column starts <= tol.  hist[c * hist_cap + it]: column c's residual after iteration it + 1.
+ * status[c] and the return code: SPARSH_OK, SPARSH_ENOCONV at the cap (X updated), SPARSH_ENUMERIC on a NaN residual or a Gram matrix
+ * of rank 0 while a residual is above tol.
+ * Memory: P and Q are the block PCG's p and Ap.  Three Gram results, two coefficient matrices, the factor, the flags and the Gram
+ * launch's partial sums (2 W^2 * 512 doubles) are the solver's own, reserved at the first SPARSH_BCG call for a width and released
+ * with the block vectors; they are counted by sparsh_bcg_info, never by sparsh_multi_info.
+ * sparsh_bcg_info: the iterations, the smallest rank and the dropped directions (all iterations together) of the last SPARSH_BCG solve
+ * and those bytes; zeros before the first.  Any pointer may be NULL. */
+int sparsh_bcg_info(sparsh_handle h, int *iterations, int *min_rank, int *dropped, long *bytes);
+/* pinv alone, on the host: coef = sign * pinv(G) C for k x k row-major G (upper triangle read) and C, keep[j] = 1 for a kept column.
+ * Returns the rank, or SPARSH_EINVAL (k outside 1..8, a NULL array).  Needs no handle and no device. */
+int sparsh_debug_bcg_small(int k, const double *G, const double *C, double sign, double *coef, int *keep);
+/* Operator-level hooks of block CG's kernels: host arrays, any n > 0, a ready handle lends its stream only.  Blocks are column-major
+ * n x k (ld = n), coefficient matrices k x k row-major; the device runs them at width W (bcg_small: the W given, 2, 4 or 8, k <= W;
+ * the others: k rounded up).  bcg_small: the device kernel, run twice (factorising, then with the kept factor; SPARSH_ENUMERIC if the
+ * two differ); returns the rank like sparsh_debug_bcg_small.  bcg_update: Xo = X + P alpha, Ro = R - Q alpha, norms[c] = ||Ro_c||;
+ * bcg_dir: Po = Z + P beta.  An output that is the array it replaces (Xo == X, Ro == R, Po == P) is updated in place on the device
+ * too.  SPARSH_ENUMERIC if a padding entry comes back nonzero. */
+int sparsh_op_bcg_small(sparsh_handle h, int W, int k, const double *G, const double *C, double sign, double *coef, int *keep);
+int sparsh_op_bcg_update(sparsh_handle h, int n, int k, const double *X, const double *R, const double *P, const double *Q,
+                         const double *alpha, double *Xo, double *Ro, double *norms);
+int sparsh_op_bcg_dir(sparsh_handle h, int n, int k, const double *Z, const double *P, const double *beta, double *Po);
 
 /* ---- the lowest eigenpairs of the SPD level-0 operator by LOBPCG on the block path ----
  * nev <= SPARSH_MAX_RHS eigenpairs A x = lambda x with the smallest lambda, the block V-cycle as preconditioner.  The standard

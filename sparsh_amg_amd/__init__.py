@@ -27,6 +27,8 @@ SPARSH_GMRES, SPARSH_PGMRES = 5, 6
 SPARSH_FCG = 7
 METHODS = {"amg": SPARSH_AMG, "cg": SPARSH_CG, "pcg": SPARSH_PCG, "bicg": SPARSH_BICG, "pbicg": SPARSH_PBICG,
            "gmres": SPARSH_GMRES, "pgmres": SPARSH_PGMRES}
+SPARSH_BCG = 8
+BLOCK_METHODS = {"bcg": SPARSH_BCG}  # methods of solve_multi only: the columns of a block share one search space
 FLEXIBLE_METHODS = {"fcg": SPARSH_FCG}  # methods whose preconditioner may change between applications (the K-cycle)
 SPARSH_CYCLE_V, SPARSH_CYCLE_W, SPARSH_CYCLE_K = 0, 1, 2
 CYCLES = {"v": SPARSH_CYCLE_V, "w": SPARSH_CYCLE_W, "k": SPARSH_CYCLE_K}
@@ -45,6 +47,8 @@ SPARSH_OK, SPARSH_EINVAL, SPARSH_ENODEV, SPARSH_ESTATE, SPARSH_ENUMERIC, SPARSH_
 def _method(method):
     """method code of a name ("pcg", "fcg", ...) or the code itself"""
     if isinstance(method, str):
+        if method in BLOCK_METHODS:
+            return BLOCK_METHODS[method]
         return METHODS[method] if method in METHODS else FLEXIBLE_METHODS[method]
     return method
 
@@ -246,6 +250,11 @@ def _load():
         "sparsh_solve_multi_dev": (C.c_int, [H, C.c_int, C.c_int, C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_int, c_dbl_p, C.c_int,
                                              c_int_p, c_int_p, c_dbl_p]),
         "sparsh_multi_info": (C.c_int, [H, c_int_p, C.POINTER(C.c_long)]),
+        "sparsh_bcg_info": (C.c_int, [H, c_int_p, c_int_p, c_int_p, C.POINTER(C.c_long)]),
+        "sparsh_debug_bcg_small": (C.c_int, [C.c_int, c_dbl_p, c_dbl_p, C.c_double, c_dbl_p, c_int_p]),
+        "sparsh_op_bcg_small": (C.c_int, [H, C.c_int, C.c_int, c_dbl_p, c_dbl_p, C.c_double, c_dbl_p, c_int_p]),
+        "sparsh_op_bcg_update": (C.c_int, [H, C.c_int, C.c_int] + [c_dbl_p] * 8),
+        "sparsh_op_bcg_dir": (C.c_int, [H, C.c_int, C.c_int] + [c_dbl_p] * 4),
         "sparsh_op_spmv_dot_multi": (C.c_int, [H, C.c_int, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p]),
         "sparsh_op_residual_multi": (C.c_int, [H, C.c_int, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p]),
         "sparsh_op_jacobi_multi": (C.c_int, [H, C.c_int, C.c_int, c_dbl_p, c_dbl_p, C.c_int, C.c_int]),
@@ -394,6 +403,20 @@ def eig_small(GA, GB, k):
     theta, Cm = np.zeros(max(int(k), 1)), np.zeros((m, max(int(k), 1)))
     rc = _check(lib.sparsh_debug_eig_small(m, int(k), _dp(GA), _dp(GB), _dp(theta), _dp(Cm)), allow=(1,))
     return rc, theta, Cm
+
+
+def bcg_small(G, C, sign=1.0):
+    """Debug hook (host only): block CG's small solve coef = sign * pinv(G) C by LDL^T with dropped directions, G and C of order
+    k <= 8.  Returns (coef (k, k), keep (k,), rank)."""
+    G, Cm = np.ascontiguousarray(G, dtype=np.float64), np.ascontiguousarray(C, dtype=np.float64)
+    k = G.shape[0]
+    if G.shape != (k, k) or Cm.shape != (k, k):
+        raise ValueError("G and C are square matrices of one order")
+    coef, keep = np.zeros((max(k, 1), max(k, 1))), np.zeros(max(k, 1), dtype=np.int32)
+    rank = lib.sparsh_debug_bcg_small(k, _dp(G), _dp(Cm), float(sign), _dp(coef), _ip(keep))
+    if rank < 0:
+        _check(rank)
+    return coef, keep, rank
 
 
 def device_count() -> int:
@@ -1251,7 +1274,8 @@ class sp_matrix_mg:
         return np.array(a, dtype=np.float64, order="F")  # a column-major copy of the caller's array
 
     def solve_multi(self, method, B, X, hist_cap=8192, allow=()):
-        """Block AMG-PCG: X (n, nrhs) holds the initial guesses on entry and the solutions on return.  Returns (histories, iters,
+        """Block AMG-PCG ("pcg") or block CG ("bcg": the columns share one search space, one iteration count for all; bcg_info()
+        has the ranks): X (n, nrhs) holds the initial guesses on entry and the solutions on return.  Returns (histories, iters,
         status, rc): histories[c] = column c's residual after every iteration it ran; SPARSH_ENOCONV / SPARSH_ENUMERIC are handed
         back in rc and per column in status, other codes raise."""
         Bf, Xf = self._block(B), self._block(X)
@@ -1279,6 +1303,42 @@ class sp_matrix_mg:
         w, b = C.c_int(), C.c_long()
         _check(lib.sparsh_multi_info(self._h, C.byref(w), C.byref(b)))
         return dict(width=w.value, bytes=b.value)
+
+    def bcg_info(self):
+        """The last solve_multi("bcg", ...): iterations, the smallest rank of its Gram matrices, the directions dropped (all
+        iterations together) and the device bytes of the solver's own small arrays (zeros before the first such solve)."""
+        it, mr, dr, b = C.c_int(), C.c_int(), C.c_int(), C.c_long()
+        _check(lib.sparsh_bcg_info(self._h, C.byref(it), C.byref(mr), C.byref(dr), C.byref(b)))
+        return dict(iterations=it.value, min_rank=mr.value, dropped=dr.value, bytes=b.value)
+
+    def op_bcg_small(self, W, G, Cm, sign=1.0):
+        """Block CG's small-solve kernel at width W on k x k matrices (k <= W).  Returns (coef (k, k), keep (k,), rank)."""
+        G, Cm = np.ascontiguousarray(G, dtype=np.float64), np.ascontiguousarray(Cm, dtype=np.float64)
+        k = G.shape[0]
+        coef, keep = np.zeros((max(k, 1), max(k, 1))), np.zeros(max(k, 1), dtype=np.int32)
+        rank = lib.sparsh_op_bcg_small(self._h, int(W), k, _dp(G), _dp(Cm), float(sign), _dp(coef), _ip(keep))
+        if rank < 0:
+            _check(rank)
+        return coef, keep, rank
+
+    def op_bcg_update(self, X, R, P, Q, alpha, in_place=False):
+        """Block CG's update kernel: (X + P alpha, R - Q alpha, [||R'_c||]); in_place: the outputs replace X and R on the device too."""
+        Xf, Rf, Pf, Qf = (self._block(a) for a in (X, R, P, Q))
+        n, k = Xf.shape
+        al = np.ascontiguousarray(alpha, dtype=np.float64)
+        Xo, Ro = (Xf, Rf) if in_place else (np.zeros_like(Xf, order="F"), np.zeros_like(Rf, order="F"))
+        norms = np.zeros(k)
+        _check(lib.sparsh_op_bcg_update(self._h, n, k, _dp(Xf), _dp(Rf), _dp(Pf), _dp(Qf), _dp(al), _dp(Xo), _dp(Ro), _dp(norms)))
+        return Xo, Ro, norms
+
+    def op_bcg_dir(self, Z, P, beta, in_place=False):
+        """Block CG's direction kernel: Z + P beta; in_place: the output replaces P on the device too."""
+        Zf, Pf = self._block(Z), self._block(P)
+        n, k = Zf.shape
+        be = np.ascontiguousarray(beta, dtype=np.float64)
+        Po = Pf if in_place else np.zeros_like(Pf, order="F")
+        _check(lib.sparsh_op_bcg_dir(self._h, n, k, _dp(Zf), _dp(Pf), _dp(be), _dp(Po)))
+        return Po
 
     def op_spmv_dot_multi(self, level, X):
         """(A_l X, [x_c . (A_l x_c)]) through the block launch PCG uses for A p and p.Ap."""

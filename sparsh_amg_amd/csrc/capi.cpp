@@ -11,6 +11,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include "../../include/sparsh_amg.h"
+#include "bcg_small.hpp"
 #include "eig_small.hpp"
 #include "engine.hpp"
 
@@ -2078,13 +2079,14 @@ int sparsh_solve_multi_dev(sparsh_handle h, int method, int nrhs, const double *
                            double *hist, int hist_cap, int *iters, int *status, double *seconds)
 {
     REQUIRE_MULTI_ARGS(h, nrhs);
-    if (method != SPARSH_PCG) return fail(SPARSH_EINVAL, "block solves take SPARSH_PCG only");
+    if (method != SPARSH_PCG && method != SPARSH_BCG) return fail(SPARSH_EINVAL, "block solves take SPARSH_PCG or SPARSH_BCG only");
     if (!B_dev || !X_dev || !iters || !status || (hist_cap > 0 && !hist)) return fail(SPARSH_EINVAL, "NULL array");
     if (hist_cap < 0) return fail(SPARSH_EINVAL, "hist_cap < 0");
     if (ldb < h->eng->n0() || ldx < h->eng->n0()) return fail(SPARSH_EINVAL, "ldb and ldx must be at least the number of rows");
     REQUIRE_MULTI_FITS(h);
     REQUIRE_READY(h);
-    int rc = h->eng->solve_multi_dev(nrhs, B_dev, ldb, X_dev, ldx, max_iters, hist, hist_cap, iters, status, seconds);
+    int rc = method == SPARSH_BCG ? h->eng->solve_bcg_dev(nrhs, B_dev, ldb, X_dev, ldx, max_iters, hist, hist_cap, iters, status, seconds)
+                                  : h->eng->solve_multi_dev(nrhs, B_dev, ldb, X_dev, ldx, max_iters, hist, hist_cap, iters, status, seconds);
     if (rc != SPARSH_OK) return fail(rc, h->eng->error);
     return rc;
 }
@@ -2093,7 +2095,7 @@ int sparsh_solve_multi(sparsh_handle h, int method, int nrhs, const double *B, l
                        int *iters, int *status)
 {
     REQUIRE_MULTI_ARGS(h, nrhs);
-    if (method != SPARSH_PCG) return fail(SPARSH_EINVAL, "block solves take SPARSH_PCG only");
+    if (method != SPARSH_PCG && method != SPARSH_BCG) return fail(SPARSH_EINVAL, "block solves take SPARSH_PCG or SPARSH_BCG only");
     if (!B || !X || !iters || !status || (hist_cap > 0 && !hist)) return fail(SPARSH_EINVAL, "NULL array");
     if (hist_cap < 0) return fail(SPARSH_EINVAL, "hist_cap < 0");
     if (ldb < h->eng->n0() || ldx < h->eng->n0()) return fail(SPARSH_EINVAL, "ldb and ldx must be at least the number of rows");
@@ -2108,7 +2110,8 @@ int sparsh_solve_multi(sparsh_handle h, int method, int nrhs, const double *B, l
         (void)hipMemcpy(db.p + (size_t)c * n, B + (size_t)c * ldb, n * 8, hipMemcpyHostToDevice);
         (void)hipMemcpy(dx.p + (size_t)c * n, X + (size_t)c * ldx, n * 8, hipMemcpyHostToDevice);
     }
-    int rc = E.solve_multi_dev(nrhs, db.p, (long)n, dx.p, (long)n, 0, hist, hist_cap, iters, status, nullptr);
+    int rc = method == SPARSH_BCG ? E.solve_bcg_dev(nrhs, db.p, (long)n, dx.p, (long)n, 0, hist, hist_cap, iters, status, nullptr)
+                                  : E.solve_multi_dev(nrhs, db.p, (long)n, dx.p, (long)n, 0, hist, hist_cap, iters, status, nullptr);
     (void)hipStreamSynchronize(E.stream());
     for (int c = 0; c < nrhs; ++c) (void)hipMemcpy(X + (size_t)c * ldx, dx.p + (size_t)c * n, n * 8, hipMemcpyDeviceToHost);
     if (rc != SPARSH_OK) return fail(rc, E.error);
@@ -2706,6 +2709,169 @@ int sparsh_op_eig_update_gen(sparsh_handle h, int n, int k, const double *const 
         ok = stage.get(out[o]);
     }
     return done(E, ok);
+}
+
+// ---- block CG (engine_bcg.cpp, bcg_kernels.hip, bcg_small.hpp) ----
+
+int sparsh_bcg_info(sparsh_handle h, int *iterations, int *min_rank, int *dropped, long *bytes)
+{
+    if (!h || !h->eng) return fail(SPARSH_EINVAL, "null handle");
+    if (iterations) *iterations = h->eng->bcg_iterations();
+    if (min_rank) *min_rank = h->eng->bcg_min_rank();
+    if (dropped) *dropped = h->eng->bcg_dropped();
+    if (bytes) *bytes = (long)h->eng->bcg_bytes();
+    return SPARSH_OK;
+}
+
+int sparsh_debug_bcg_small(int k, const double *G, const double *C, double sign, double *coef, int *keep)
+{
+    if (k < 1 || k > SPARSH_MAX_RHS) return fail(SPARSH_EINVAL, "k must be 1 .. SPARSH_MAX_RHS (8)");
+    if (!G || !C || !coef || !keep) return fail(SPARSH_EINVAL, "NULL array");
+    double L[kBcgMax * kBcgMax] = {0.0}, d[kBcgMax] = {0.0}, y[kBcgMax];
+    int kp[kBcgMax] = {0};
+    const int rank = bcg_factor(k, G, k, L, d, kp);
+    for (int c = 0; c < k; ++c) bcg_solve_column(k, L, d, kp, C, k, c, sign, coef, k, y);
+    std::copy(kp, kp + k, keep);
+    return rank;
+}
+
+int sparsh_op_bcg_small(sparsh_handle h, int W, int k, const double *G, const double *C, double sign, double *coef, int *keep)
+{
+    REQUIRE_EIG_OP(h, 1);
+    if (W != 2 && W != 4 && W != 8) return fail(SPARSH_EINVAL, "W must be 2, 4 or 8");
+    if (k < 1 || k > W) return fail(SPARSH_EINVAL, "k must be 1 .. W");
+    if (!G || !C || !coef || !keep) return fail(SPARSH_EINVAL, "NULL array");
+    Engine &E = *h->eng;
+    std::vector<double> g((size_t)W * W, 0.0), c((size_t)W * W, 0.0), zeros((size_t)kBcgMax * kBcgMax, 0.0);
+    for (int a = 0; a < k; ++a)
+        for (int b = 0; b < k; ++b) {
+            g[(size_t)a * W + b] = G[a * k + b];
+            c[(size_t)a * W + b] = C[a * k + b];
+        }
+    DBuf dg(E, g.size(), g.data()), dc(E, c.size(), c.data()), o1(E, g.size(), zeros.data()), o2(E, g.size(), zeros.data()),
+        dl(E, zeros.size(), zeros.data()), dd(E, kBcgMax, zeros.data()), dres(E, kBcgMax, zeros.data()), dfl(E, BF_COUNT / 2, zeros.data());
+    if (!dg.p || !dc.p || !o1.p || !o2.p || !dl.p || !dd.p || !dres.p || !dfl.p) return fail(SPARSH_ENODEV, "device allocation or H2D copy failed");
+    BcgState s;
+    s.L = dl.p;
+    s.d = dd.p;
+    s.res = dres.p;
+    s.flags = reinterpret_cast<int *>(dfl.p);
+    // the solve of an iteration's first call, then the second call's: the same G with the factor kept on the device
+    launch_bcg_small(W, k, true, dg.p, dc.p, sign, s, o1.p, 0, E.stream());
+    int flags[BF_COUNT];
+    (void)hipStreamSynchronize(E.stream());
+    bool ok = hipMemcpy(flags, dfl.p, sizeof(flags), hipMemcpyDeviceToHost) == hipSuccess;
+    if (ok && flags[BF_DONE]) {  // rank 0 ends a solve: lift the flag so that the second launch runs
+        const int zero = 0;
+        ok = hipMemcpy(s.flags + BF_DONE, &zero, sizeof(int), hipMemcpyHostToDevice) == hipSuccess;
+    }
+    launch_bcg_small(W, k, false, dg.p, dc.p, sign, s, o2.p, 0, E.stream());
+    std::vector<double> f1(g.size()), f2(g.size());
+    ok = ok && o1.get(f1.data()) && o2.get(f2.data());
+    if (!ok) return done(E, false);
+    if (std::memcmp(f1.data(), f2.data(), f1.size() * 8) != 0) return fail(SPARSH_ENUMERIC, "the kept factor gives other coefficients");
+    for (int a = 0; a < W; ++a)
+        for (int b = 0; b < W; ++b) {
+            if (a < k && b < k) coef[a * k + b] = f1[(size_t)a * W + b];
+            else if (f1[(size_t)a * W + b] != 0.0) return fail(SPARSH_ENUMERIC, "a padding entry of the coefficient matrix is not zero");
+        }
+    std::copy(flags + BF_KEEP, flags + BF_KEEP + k, keep);
+    if (int rc = done(E, true); rc != SPARSH_OK) return rc;
+    return flags[BF_RANK];
+}
+
+}  // extern "C"
+
+namespace {
+
+// host blocks (column-major, n x k) to interleaved device blocks of width W and back, through one staging buffer
+bool bcg_put(Engine &E, int n, int k, int W, const double *src, DBuf &stage, double *blk)
+{
+    if (hipMemcpy(stage.p, src, (size_t)n * k * 8, hipMemcpyHostToDevice) != hipSuccess) return false;
+    launch_interleave(n, k, W, stage.p, n, blk, E.stream());
+    return hipStreamSynchronize(E.stream()) == hipSuccess;
+}
+
+// ... and back; a padding column that is not zero makes *padding_clean false
+bool bcg_get(Engine &E, int n, int k, int W, const double *blk, double *dst, bool *padding_clean)
+{
+    std::vector<double> full((size_t)n * W);
+    if (hipStreamSynchronize(E.stream()) != hipSuccess) return false;
+    if (hipMemcpy(full.data(), blk, full.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) return false;
+    for (size_t i = 0; i < (size_t)n; ++i) {
+        for (int c = 0; c < k; ++c) dst[(size_t)c * n + i] = full[i * W + c];
+        for (int c = k; c < W; ++c)
+            if (full[i * W + c] != 0.0) *padding_clean = false;
+    }
+    return true;
+}
+
+std::vector<double> bcg_pad_coef(int k, int W, const double *coef)
+{
+    std::vector<double> out((size_t)W * W, 0.0);
+    for (int a = 0; a < k; ++a)
+        for (int b = 0; b < k; ++b) out[(size_t)a * W + b] = coef[a * k + b];
+    return out;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sparsh_op_bcg_update(sparsh_handle h, int n, int k, const double *X, const double *R, const double *P, const double *Q,
+                         const double *alpha, double *Xo, double *Ro, double *norms)
+{
+    REQUIRE_EIG_OP(h, n);
+    if (k < 1 || k > SPARSH_MAX_RHS) return fail(SPARSH_EINVAL, "k must be 1 .. SPARSH_MAX_RHS (8)");
+    if (!X || !R || !P || !Q || !alpha || !Xo || !Ro || !norms) return fail(SPARSH_EINVAL, "NULL array");
+    Engine &E = *h->eng;
+    const int W = multi_width(k);
+    const size_t len = (size_t)n * W;
+    const std::vector<double> coef = bcg_pad_coef(k, W, alpha), zeros(kBcgMax * kBcgMax, 0.0);
+    DBuf stage(E, (size_t)n * k), bx(E, len), br(E, len), bp(E, len), bq(E, len), bxo(E, len), bro(E, len), dcoef(E, coef.size(), coef.data()),
+        part(E, (size_t)W * bcg_grid(n, W)), dl(E, zeros.size(), zeros.data()), dd(E, kBcgMax, zeros.data()), dres(E, kBcgMax, zeros.data()),
+        dfl(E, BF_COUNT / 2, zeros.data());
+    bool ok = stage.p && bx.p && br.p && bp.p && bq.p && bxo.p && bro.p && dcoef.p && part.p && dl.p && dd.p && dres.p && dfl.p;
+    ok = ok && bcg_put(E, n, k, W, X, stage, bx.p) && bcg_put(E, n, k, W, R, stage, br.p) && bcg_put(E, n, k, W, P, stage, bp.p) &&
+         bcg_put(E, n, k, W, Q, stage, bq.p);
+    if (!ok) return fail(SPARSH_ENODEV, "device allocation or H2D copy failed");
+    // an output that is the array it replaces (Xo == X, Ro == R) is updated in place on the device as well
+    double *dxo = Xo == X ? bx.p : bxo.p, *dro = Ro == R ? br.p : bro.p;
+    BcgState s;
+    s.L = dl.p;
+    s.d = dd.p;
+    s.res = dres.p;
+    s.flags = reinterpret_cast<int *>(dfl.p);
+    const int nb = launch_bcg_update(n, W, k, s.flags + BF_DONE, bx.p, br.p, bp.p, bq.p, dcoef.p, dxo, dro, part.p, E.stream());
+    launch_bcg_finalize(W, k, part.p, nb, s, 0.0, nullptr, 0, 0, E.stream());
+    bool clean = true;
+    double res[kBcgMax];
+    ok = bcg_get(E, n, k, W, dxo, Xo, &clean) && bcg_get(E, n, k, W, dro, Ro, &clean) && dres.get(res);
+    if (!ok) return done(E, false);
+    if (!clean) return fail(SPARSH_ENUMERIC, "a padding column of an updated block is not zero");
+    std::copy(res, res + k, norms);
+    return done(E, true);
+}
+
+int sparsh_op_bcg_dir(sparsh_handle h, int n, int k, const double *Z, const double *P, const double *beta, double *Po)
+{
+    REQUIRE_EIG_OP(h, n);
+    if (k < 1 || k > SPARSH_MAX_RHS) return fail(SPARSH_EINVAL, "k must be 1 .. SPARSH_MAX_RHS (8)");
+    if (!Z || !P || !beta || !Po) return fail(SPARSH_EINVAL, "NULL array");
+    Engine &E = *h->eng;
+    const int W = multi_width(k);
+    const size_t len = (size_t)n * W;
+    const std::vector<double> coef = bcg_pad_coef(k, W, beta);
+    DBuf stage(E, (size_t)n * k), bz(E, len), bp(E, len), bpo(E, len), dcoef(E, coef.size(), coef.data());
+    bool ok = stage.p && bz.p && bp.p && bpo.p && dcoef.p;
+    ok = ok && bcg_put(E, n, k, W, Z, stage, bz.p) && bcg_put(E, n, k, W, P, stage, bp.p);
+    if (!ok) return fail(SPARSH_ENODEV, "device allocation or H2D copy failed");
+    double *dpo = Po == P ? bp.p : bpo.p;  // in place on the device too
+    launch_bcg_dir(n, W, k, nullptr, bz.p, bp.p, dcoef.p, dpo, E.stream());
+    bool clean = true;
+    if (!bcg_get(E, n, k, W, dpo, Po, &clean)) return done(E, false);
+    if (!clean) return fail(SPARSH_ENUMERIC, "a padding column of the new direction block is not zero");
+    return done(E, true);
 }
 
 }  // extern "C"

@@ -389,6 +389,16 @@ public:
     // block PCG on column-major device arrays: X = initial guesses in, solutions out; hist[c * hist_cap + k], iters[c], status[c]
     int solve_multi_dev(int nrhs, const double *B, long ldb, double *X, long ldx, int max_iters, double *hist, int hist_cap, int *iters,
                         int *status, double *seconds);
+    // block CG with the arguments of solve_multi_dev: the columns share one search space, so iters is the
+    // same for every column and status is per solve.  P and Q are the block PCG's p and Ap; the Gram results, coefficient matrices,
+    // factor, flags and the Gram launch's partial sums are the solver's own, reserved at the first block CG call for a width and
+    // counted in bcg_bytes(), never in multi_bytes().
+    int solve_bcg_dev(int nrhs, const double *B, long ldb, double *X, long ldx, int max_iters, double *hist, int hist_cap, int *iters,
+                      int *status, double *seconds);
+    size_t bcg_bytes() const { return bcg_bytes_; }
+    int bcg_iterations() const { return bcg_last_[0]; }
+    int bcg_min_rank() const { return bcg_last_[1]; }
+    int bcg_dropped() const { return bcg_last_[2]; }
     // operator-level hooks on column-major device arrays (ld = rows of the level): each interleaves, runs the block launch and
     // de-interleaves.  which: 0 Y = A X with dots, 1 residual, 2 Jacobi leg (sweeps, x_is_zero), 3 restriction, 4 prolongation
     // (X = coarse block, Y = fine block in/out), 5 coarse solve, 6 one vcycle_multi from a zero guess (level 0)
@@ -593,6 +603,13 @@ private:
     MultiState ms_;
     int mflip_ = 0;  // bench_multi_launch
     std::vector<void *> multi_allocs_;
+    // block CG: gm = [G, C1, C2] and coef = [alpha, beta] (W x W each), the factor and flags, the Gram launch's partial sums; in
+    // multi_allocs_ (they go with the block vectors) but counted on their own
+    int bcg_reserve();
+    BcgState bcg_;
+    double *bcg_gm_ = nullptr, *bcg_coef_ = nullptr, *bcg_part_ = nullptr;
+    size_t bcg_bytes_ = 0;
+    int bcg_last_[3] = {0, 0, 0};  // iterations, minimum rank and dropped directions of the last solve
 
     // LOBPCG (engine_eig.cpp): seven interleaved blocks of n * width doubles, the partial sums of the Gram and residual launches,
     // G = [S^T S, S^T A S, residual norms] and coef = [Cx, Cw, Cp, theta]

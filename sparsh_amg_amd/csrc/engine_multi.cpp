@@ -41,6 +41,9 @@ void Engine::multi_forget()
     mx_ = mr_ = mp_ = mAp_ = mpart0_ = mpart1_ = mcs_in_ = mcs_out_ = mhist_ = nullptr;
     mflags_ = nullptr;
     ms_ = MultiState();
+    bcg_ = BcgState();  // block CG's small arrays are in multi_allocs_ too (engine_bcg.cpp)
+    bcg_gm_ = bcg_coef_ = bcg_part_ = nullptr;
+    bcg_bytes_ = 0;
 }
 
 void Engine::multi_release()

@@ -506,4 +506,38 @@ void launch_eig_con_project(int n, int W, int mt, const double *Y, const double 
 // column col of the interleaved block v <- value
 void launch_eig_con_fill_column(int n, int W, int col, double value, double *v, hipStream_t st);
 
+// ---- block CG on interleaved blocks (bcg_kernels.hip).  The columns of a block share one search space: the
+// scalars of block PCG become W x W matrices (row-major, device memory), solved for by bcg_small.hpp's LDL^T with dropped directions.
+constexpr int kBcgMaxGrid = 2048;  // workgroups of the two streaming kernels: one per 512 / W rows, capped at ~8 per CU
+int bcg_grid(int n, int W);
+enum BcgFlag : int {
+    BF_KEEP = 0,       // 8 ints: the keep mask of the last factorisation
+    BF_RANK = 8,       // its rank
+    BF_MIN_RANK = 9,   // the smallest rank of the solve so far
+    BF_DROPPED = 10,   // directions dropped, all iterations together
+    BF_DONE = 11,      // the solve is over: every kernel of the loop leaves at once
+    BF_NUMERIC = 12,   // ... because of a NaN residual or a Gram matrix of rank 0
+    BF_ITERS = 13,     // iterations completed
+    BF_COUNT = 16
+};
+struct BcgState {
+    double *L = nullptr;    // 64: the unit lower factor (8 x 8 row-major whatever W)
+    double *d = nullptr;    // 8: its pivots
+    double *res = nullptr;  // 8: the last residual norms
+    int *flags = nullptr;   // BF_COUNT
+};
+// coef (W x W) = sign * pinv(G) C for the k columns in use.  factor: factorise G and keep the factor in s; else reuse the kept one.
+void launch_bcg_small(int W, int k, bool factor, const double *G, const double *C, double sign, const BcgState &s, double *coef, int it,
+                      hipStream_t st);
+// X' = X + P alpha ; R' = R - Q alpha ; partial[c * grid + workgroup] = shares of ||R'_c||^2 (W * bcg_grid(n, W) doubles).  Xo may be X,
+// Ro may be R.  done (may be nullptr): device flag that turns the launch into a no-op.  Returns the partials per column.
+int launch_bcg_update(int n, int W, int k, const int *done, const double *X, const double *R, const double *P, const double *Q,
+                      const double *alpha, double *Xo, double *Ro, double *partial, hipStream_t st);
+// P' = Z + P beta; Po may be P
+void launch_bcg_dir(int n, int W, int k, const int *done, const double *Z, const double *P, const double *beta, double *Po, hipStream_t st);
+// res_c = sqrt of the sum of column c's partials; it < 0: start of a solve (flags reset), else the end of iteration it + 1 with
+// hist[c * hist_cap + it] = res_c; done when every res_c <= tol, numeric on a NaN
+void launch_bcg_finalize(int W, int nrhs, const double *partial, int nblk, const BcgState &s, double tol, double *hist, int hist_cap, int it,
+                         hipStream_t st);
+
 }  // namespace sparsh
