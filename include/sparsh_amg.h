@@ -712,7 +712,9 @@ int sparsh_op_precond_multi(sparsh_handle h, int nrhs, const double *R, double *
  * (level 0 whatever `level` says; reserved by the call): op 2 = the twelve-pair Gram launch with its finalise, 3 = one update;
  * with the generalised solver's blocks beside them (reserved by the call; SPARSH_ESTATE without a B): 4 = the generalised update,
  * 5 = the block SpMV with B; 7 = one projection of the constrained eigensolver (the Gram launch with its finalise, then the apply kernel) of the resident W block with the
- * constraints the last constrained solve left resident (SPARSH_ESTATE unless one of this width has run).  6 is not assigned. */
+ * constraints the last constrained solve left resident (SPARSH_ESTATE unless one of this width has run).  6 is not assigned.
+ * Under SPARSH_EIG_BASIS_ORTHO (SPARSH_ESTATE otherwise, and without a B), on the generalised solver's blocks and the mode's small
+ * arrays: 8 = the transform of three blocks in place, 9 = the masked subtraction W <- W - X C. */
 int sparsh_bench_op_multi(sparsh_handle h, int op, int level, int nrhs, int reps, double *avg_seconds);
 
 /* ---- block CG: the columns of a block share one search space ----
@@ -914,6 +916,58 @@ int sparsh_op_eig_residual_gen(sparsh_handle h, int n, int k, const double *AX, 
                                double *rnorms, double *bnorms);
 int sparsh_op_eig_update_gen(sparsh_handle h, int n, int k, const double *const in[9], const double *Cx, const double *Cw, const double *Cp,
                              double *const out[6]);
+
+/* ---- LOBPCG for clustered spectra: an orthonormalised basis and guard vectors ----
+ * sparsh_set_eig_options: two settings of the handle for sparsh_eigs, sparsh_eigs_gen, sparsh_eigs_con and their _dev forms.  Callable
+ * before or after sparsh_setup, with or without a device; both survive sparsh_setup.  SPARSH_EINVAL for an unknown basis or a wanted
+ * outside 0 .. 8.  With the defaults (PLAIN, 0) every bit, launch and byte count of those calls is what it was without this call.
+ *
+ * wanted (guard vectors): 0 = all nev columns are wanted.  With 1 <= wanted < nev a solve stops as soon as the columns 0 .. wanted - 1
+ * (the lowest Ritz pairs) are inactive and returns SPARSH_OK; the other columns are guard vectors, returned as they stand, with
+ * status[c] = SPARSH_ENOCONV where they are still active.  wanted > nev at the time of a solve is SPARSH_EINVAL in that solve.  Guard
+ * vectors keep the last wanted column away from the edge of the block, where it converges at the rate of the gap to the next
+ * eigenvalue; the padding columns of a block of width 4 or 8 are paid for anyway.  Works under both bases.
+ *
+ * basis = SPARSH_EIG_BASIS_ORTHO changes steps 2-5 of sparsh_eigs (and of the generalised and constrained loops alike):
+ *  2. the active mask is decided on the device, by a small kernel after the residual's finalise, with the rule of step 2 on the norms
+ *     the finalise wrote; the host reads it in the iteration's one pinned read, with the Gram matrices, and does not decide it again.
+ *  P. if there is a P: G = P^T (B P) by the Gram launch on one pair; a one-wavefront kernel forms, on the rows and columns of the
+ *     active columns, D = diag(G)^-1/2, the Cholesky factor D G D = L L^T (sums over p ascending, one rounding per product and sum, as
+ *     step 5) and T = D L^-T, an upper-triangular W x W matrix whose rows and columns of all other columns are zero.  An active
+ *     column whose diagonal is not finite and positive or whose pivot is below the 1e-7 of step 5 is dropped for this iteration: its
+ *     column of T is zero and its bit in the mask "P in the basis" is cleared.  Then P, AP (and BP) <- . T in place, every row on its
+ *     own, sums over c ascending, every product and sum rounded on its own.
+ *  3. W0 = M R (in a constrained solve: Pi M R); C = (B X)^T W0 by the Gram launch on one pair; W <- W0 - X C on the active columns
+ *     and exact zeros on the others (sum over j ascending, one subtraction; this launch stands in for the copy); if there is a P,
+ *     the same pair of launches once more against the orthonormalised P: C = (B P)^T W, W <- W - P C in place (without this W and P
+ *     grow parallel near convergence and the small pencil loses its accuracy just above the breakdown rule); B W by the block
+ *     SpMV (W itself in the standard problem); then twice: G = W^T (B W), T as above with the mask "W in the basis", W and B W <- . T.
+ *     B W follows W by the same transforms, so B is applied once.  Then AW = A W.
+ *  5. Rayleigh-Ritz on [all k of X, the W columns of the W mask, the P columns of the P mask]; the breakdown rule and the restart
+ *     without P stay as the last resort.
+ * One host synchronisation per iteration, as before.  The mode's own device memory -- three masks of W doubles and two W x W
+ * matrices -- is reserved at the first ortho solve for a width, freed with the solver's blocks and by a change of basis, and
+ * counted by sparsh_eig_ortho_info (with the columns of W and of P dropped in the last solve), never by sparsh_eig_info.
+ * Refusals are those of sparsh_eigs; sparsh_solve_multi and block CG do not look at either setting. */
+#define SPARSH_EIG_BASIS_PLAIN 0   /* default: the loop as documented above */
+#define SPARSH_EIG_BASIS_ORTHO 1   /* W and P B-orthonormalised every iteration */
+int sparsh_set_eig_options(sparsh_handle h, int basis, int wanted);
+int sparsh_eig_options(sparsh_handle h, int *basis, int *wanted);
+int sparsh_eig_ortho_info(sparsh_handle h, int *dropped_w, int *dropped_p, long *bytes);
+/* The small Cholesky step on the host (no handle, no device): G of order m <= 8 row-major (only the upper triangle, and only the rows
+ * and columns of mask_in, are read), T m x m row-major, mask_out[i] = 1 for the kept columns.  sparsh_op_eig_chol_small: the same
+ * through the one-wavefront kernel at width W = 2, 4 or 8, bit for bit. */
+int sparsh_debug_eig_chol(int m, const double *G, const int *mask_in, double *T, int *mask_out);
+int sparsh_op_eig_chol_small(sparsh_handle h, int W, const double *G, const int *mask_in, double *T, int *mask_out);
+/* Operator-level hooks of the other three kernels, in the style of sparsh_op_eig_update (column-major host arrays of any n > 0 rows,
+ * k x k row-major small matrices, masks of k ints).  eig_transform: V[b] <- V[b] T in place for b < nb <= 3.  eig_ortho_apply:
+ * Wout = W0 - X C on the columns of the mask, zeros elsewhere; Wout == W0 runs in place on the device too.  eig_active_mask: the rule
+ * of step 2 (gen: with bn) on given norms.  All return SPARSH_ENUMERIC if a padding column of a device block came back nonzero. */
+int sparsh_op_eig_transform(sparsh_handle h, int n, int k, int nb, double *const V[3], const double *T);
+int sparsh_op_eig_ortho_apply(sparsh_handle h, int n, int k, const double *X, const double *C, const int *mask, const double *W0,
+                              double *Wout);
+int sparsh_op_eig_active_mask(sparsh_handle h, int k, int gen, double tol, const double *theta, const double *rn, const double *bn,
+                              int *mask);
 
 /* device memory helpers so a host language needs no HIP binding of its own */
 int sparsh_dev_alloc(sparsh_handle h, long nbytes, void **out);

@@ -41,6 +41,8 @@ GMRES_BASES = {"fp64": SPARSH_BASIS_FP64, "fp32": SPARSH_BASIS_FP32}
 SMOOTHERS = {"jacobi": SPARSH_SMOOTH_JACOBI, "sor": SPARSH_SMOOTH_SOR, "chebyshev": SPARSH_SMOOTH_CHEBYSHEV}
 SOR_ORDERS = {"forward": SPARSH_SOR_FORWARD, "symmetric": SPARSH_SOR_SYMMETRIC}
 SPARSH_OK, SPARSH_EINVAL, SPARSH_ENODEV, SPARSH_ESTATE, SPARSH_ENUMERIC, SPARSH_ENOCONV, SPARSH_ECOMM = 0, -1, -2, -3, -4, -5, -6
+SPARSH_EIG_BASIS_PLAIN, SPARSH_EIG_BASIS_ORTHO = 0, 1
+SPARSH_MAX_RHS = 8
 
 
 
@@ -286,6 +288,14 @@ def _load():
         "sparsh_op_eig_b_multi": (C.c_int, [H, C.c_int, c_dbl_p, c_dbl_p]),
         "sparsh_op_eig_residual_gen": (C.c_int, [H, C.c_int, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p]),
         "sparsh_op_eig_update_gen": (C.c_int, [H, C.c_int, C.c_int, C.POINTER(c_dbl_p), c_dbl_p, c_dbl_p, c_dbl_p, C.POINTER(c_dbl_p)]),
+        "sparsh_set_eig_options": (C.c_int, [H, C.c_int, C.c_int]),
+        "sparsh_eig_options": (C.c_int, [H, c_int_p, c_int_p]),
+        "sparsh_eig_ortho_info": (C.c_int, [H, c_int_p, c_int_p, C.POINTER(C.c_long)]),
+        "sparsh_debug_eig_chol": (C.c_int, [C.c_int, c_dbl_p, c_int_p, c_dbl_p, c_int_p]),
+        "sparsh_op_eig_chol_small": (C.c_int, [H, C.c_int, c_dbl_p, c_int_p, c_dbl_p, c_int_p]),
+        "sparsh_op_eig_transform": (C.c_int, [H, C.c_int, C.c_int, C.c_int, C.POINTER(c_dbl_p), c_dbl_p]),
+        "sparsh_op_eig_ortho_apply": (C.c_int, [H, C.c_int, C.c_int, c_dbl_p, c_dbl_p, c_int_p, c_dbl_p, c_dbl_p]),
+        "sparsh_op_eig_active_mask": (C.c_int, [H, C.c_int, C.c_int, C.c_double, c_dbl_p, c_dbl_p, c_dbl_p, c_int_p]),
         "sparsh_op_gs_dot": (C.c_int, [H, C.c_int, C.c_int, C.c_int, c_dbl_p, c_dbl_p, C.c_int, c_dbl_p]),
         "sparsh_op_gs_update": (C.c_int, [H, C.c_int, C.c_int, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p, C.c_int, C.c_int, C.c_int, C.c_double,
                                           c_dbl_p, c_dbl_p, c_dbl_p, c_int_p]),
@@ -403,6 +413,21 @@ def eig_small(GA, GB, k):
     theta, Cm = np.zeros(max(int(k), 1)), np.zeros((m, max(int(k), 1)))
     rc = _check(lib.sparsh_debug_eig_small(m, int(k), _dp(GA), _dp(GB), _dp(theta), _dp(Cm)), allow=(1,))
     return rc, theta, Cm
+
+
+def eig_chol(G, mask=None):
+    """Debug hook (host only): the small Cholesky step of the eigensolver's ortho basis on G = V^T (B V) of order m <= 8 (upper
+    triangle) over the columns of the mask (None: all).  Returns (T (m, m), mask_out (m,)): V T is B-orthonormal on the kept columns."""
+    G = np.ascontiguousarray(G, dtype=np.float64)
+    m = G.shape[0]
+    if G.shape != (m, m):
+        raise ValueError("G is a square matrix")
+    mi = np.ones(m, dtype=np.int32) if mask is None else np.ascontiguousarray(mask, dtype=np.int32)
+    if mi.shape != (m,):
+        raise ValueError("the mask has one entry per column")
+    T, mo = np.zeros((max(m, 1), max(m, 1))), np.zeros(max(m, 1), dtype=np.int32)
+    _check(lib.sparsh_debug_eig_chol(m, _dp(G), _ip(mi), _dp(T), _ip(mo)))
+    return T, mo
 
 
 def bcg_small(G, C, sign=1.0):
@@ -1385,15 +1410,27 @@ class sp_matrix_mg:
         return Z
 
     # -- lowest eigenpairs by AMG-preconditioned LOBPCG on the block path -----------------------------------------
-    def eigs(self, k, X0=None, tol=1e-8, max_iters=0, seed=0, hist_cap=1024):
+    def eigs(self, k, X0=None, tol=1e-8, max_iters=0, seed=0, hist_cap=1024, guard=0):
         """The k <= 8 lowest eigenpairs of the SPD level-0 operator.  X0 (n, k): the start block (None: default_rng(seed)
         .standard_normal((n, k))).  Returns (lam, X, iters, hist, status): lam ascending, X (n, k) orthonormal Ritz vectors, iters[c] the
         iterations column c was active in, hist (k, evaluations) with hist[c, it] = ||A x_c - lam_c x_c|| at the start of iteration
-        it, status[c] SPARSH_OK or SPARSH_ENOCONV (the cap; the code of the call is kept in last_eigs_rc).  Other codes raise."""
-        return self._eigs(lib.sparsh_eigs, k, X0, tol, max_iters, seed, hist_cap)
+        it, status[c] SPARSH_OK or SPARSH_ENOCONV (the cap; the code of the call is kept in last_eigs_rc).  Other codes raise.
+        guard = g: the solve runs k + g <= 8 columns (X0, if given, has that many) with wanted = k for this call (set_eig), the handle's
+        setting is restored afterwards, and the first k columns come back: the g guard vectors keep column k - 1 off the block's edge."""
+        return self._eigs(lib.sparsh_eigs, k, X0, tol, max_iters, seed, hist_cap, guard)
 
-    def _eigs(self, fn, k, X0, tol, max_iters, seed, hist_cap):
-        k = int(k)
+    def _eigs(self, fn, k, X0, tol, max_iters, seed, hist_cap, guard=0):
+        k, guard = int(k), int(guard)
+        if guard:
+            if guard < 0 or k < 1 or k + guard > SPARSH_MAX_RHS:
+                raise ValueError(f"guard = {guard} with k = {k}: k >= 1, guard >= 0 and k + guard <= {SPARSH_MAX_RHS}")
+            before = self.eig_options()
+            self.set_eig(before["basis"], wanted=k)
+            try:
+                lam, X, iters, hist, status = self._eigs(fn, k + guard, X0, tol, max_iters, seed, hist_cap)
+            finally:
+                self.set_eig(before["basis"], wanted=before["wanted"])
+            return lam[:k].copy(), np.asfortranarray(X[:, :k]), iters[:k].copy(), hist[:k].copy(), status[:k].copy()
         if X0 is None:
             X0 = np.random.default_rng(seed).standard_normal((self.nrow, max(k, 0)))
         Xf = self._block(X0)
@@ -1421,6 +1458,72 @@ class sp_matrix_mg:
                        C.byref(sec)), allow=(SPARSH_ENOCONV,))
         nev = int(np.count_nonzero(~np.isnan(hist[0])))
         return lam[:k].copy(), iters[:k].copy(), hist[:k, :nev].copy(), status[:k].copy(), sec.value, rc
+
+    # -- the orthonormalised basis and the guard vectors -----------------------------------------------------------
+    def set_eig(self, basis="plain", wanted=0):
+        """Options of eigs, eigs_gen, eigs_con and their _dev forms, kept by the handle through setup.  basis "plain" (the default loop)
+        or "ortho" (W and P B-orthonormalised every iteration, the active mask decided on the device: for clustered spectra, where the
+        plain loop ends at the cap).  wanted: 0 for all columns, else a solve ends once the lowest `wanted` columns have converged and
+        the others come back as guard vectors.  No device needed."""
+        names = {"plain": SPARSH_EIG_BASIS_PLAIN, "ortho": SPARSH_EIG_BASIS_ORTHO}
+        _check(lib.sparsh_set_eig_options(self._h, names[basis] if isinstance(basis, str) else int(basis), int(wanted)))
+        return self
+
+    def eig_options(self):
+        b, w = C.c_int(), C.c_int()
+        _check(lib.sparsh_eig_options(self._h, C.byref(b), C.byref(w)))
+        return dict(basis={SPARSH_EIG_BASIS_PLAIN: "plain", SPARSH_EIG_BASIS_ORTHO: "ortho"}[b.value], wanted=w.value)
+
+    def eig_ortho_info(self):
+        """Columns of W and of P dropped in the last solve under the ortho basis, and the device bytes the mode holds (0 under "plain")."""
+        dw, dp_, b = C.c_int(), C.c_int(), C.c_long()
+        _check(lib.sparsh_eig_ortho_info(self._h, C.byref(dw), C.byref(dp_), C.byref(b)))
+        return dict(dropped_w=dw.value, dropped_p=dp_.value, bytes=b.value)
+
+    def op_eig_chol_small(self, G, mask=None):
+        """eig_chol through the one-wavefront kernel; G of order 2, 4 or 8."""
+        G = np.ascontiguousarray(G, dtype=np.float64)
+        W = G.shape[0]
+        mi = np.ones(W, dtype=np.int32) if mask is None else np.ascontiguousarray(mask, dtype=np.int32)
+        if G.shape != (W, W) or mi.shape != (W,):
+            raise ValueError("G is W x W and the mask has W entries")
+        T, mo = np.zeros((W, W)), np.zeros(W, dtype=np.int32)
+        _check(lib.sparsh_op_eig_chol_small(self._h, W, _dp(G), _ip(mi), _dp(T), _ip(mo)))
+        return T, mo
+
+    def op_eig_transform(self, blocks, T):
+        """[V T for V in blocks] through the transform kernel, all in place in one launch; one to three (n, k) blocks, T (k, k)."""
+        n = np.shape(blocks[0])[0]
+        blocks = [np.array(self._block(b, n), order="F") for b in blocks]
+        k = blocks[0].shape[1]
+        Tm = np.ascontiguousarray(T, dtype=np.float64)
+        if not 1 <= len(blocks) <= 3 or Tm.shape != (k, k):
+            raise ValueError("one to three blocks of k columns and a k x k matrix")
+        ptrs = (c_dbl_p * 3)(*([_dp(b) for b in blocks] + [None] * (3 - len(blocks))))
+        _check(lib.sparsh_op_eig_transform(self._h, n, k, len(blocks), ptrs, _dp(Tm)))
+        return blocks
+
+    def op_eig_ortho_apply(self, X, Cm, mask, W0, in_place=False):
+        """W0 - X Cm on the columns of the mask, zeros elsewhere, through the masked subtraction kernel; in_place: W0 is replaced on the
+        device."""
+        n = np.shape(X)[0]
+        Xf, Wf = self._block(X), np.array(self._block(W0, n), order="F")
+        k = Xf.shape[1]
+        Cf, mk = np.ascontiguousarray(Cm, dtype=np.float64), np.ascontiguousarray(mask, dtype=np.int32)
+        if Cf.shape != (k, k) or mk.shape != (k,) or Wf.shape != Xf.shape:
+            raise ValueError("X and W0 are n x k, Cm k x k, the mask k entries")
+        out = Wf if in_place else np.zeros_like(Wf, order="F")
+        _check(lib.sparsh_op_eig_ortho_apply(self._h, n, k, _dp(Xf), _dp(Cf), _ip(mk), _dp(Wf), _dp(out)))
+        return out
+
+    def op_eig_active_mask(self, theta, rn, tol, bn=None):
+        """The active mask of step 2 as the device decides it from given norms (bn: the generalised form)."""
+        th, r = np.ascontiguousarray(theta, dtype=np.float64), np.ascontiguousarray(rn, dtype=np.float64)
+        b = None if bn is None else np.ascontiguousarray(bn, dtype=np.float64)
+        mask = np.zeros(len(th), dtype=np.int32)
+        _check(lib.sparsh_op_eig_active_mask(self._h, len(th), int(b is not None), float(tol), _dp(th), _dp(r), None if b is None else _dp(b),
+                                             _ip(mask)))
+        return mask
 
     def eig_info(self):
         """Width in force and device bytes held by the eigensolver's own blocks (both 0 until the first eigs call), and the
@@ -1453,17 +1556,17 @@ class sp_matrix_mg:
         _check(lib.sparsh_eig_b_info(self._h, C.byref(s), C.byref(nnz), C.byref(b)))
         return dict(is_set=bool(s.value), nnz=nnz.value, bytes=b.value)
 
-    def eigs_gen(self, k, X0=None, tol=1e-8, max_iters=0, seed=0, hist_cap=1024):
+    def eigs_gen(self, k, X0=None, tol=1e-8, max_iters=0, seed=0, hist_cap=1024, guard=0):
         """The k <= 8 lowest eigenpairs of A x = lam B x with the B of set_eig_b.  Arguments and results are those of eigs; X is
         B-orthonormal and hist[c, it] = ||A x_c - lam_c B x_c||."""
-        return self._eigs(lib.sparsh_eigs_gen, k, X0, tol, max_iters, seed, hist_cap)
+        return self._eigs(lib.sparsh_eigs_gen, k, X0, tol, max_iters, seed, hist_cap, guard)
 
     def eigs_gen_dev(self, k, X_dev, ldx, tol=1e-8, max_iters=0, hist_cap=1024):
         """eigs_dev for the generalised problem."""
         return self._eigs_dev(lib.sparsh_eigs_gen_dev, k, X_dev, ldx, tol, max_iters, hist_cap)
 
     # -- eigenpairs under constraints: null-space handles, more than 8 pairs ---------------------------------------
-    def eigs_con(self, k, Y=None, gen=False, X0=None, tol=1e-8, max_iters=0, seed=0, hist_cap=1024):
+    def eigs_con(self, k, Y=None, gen=False, X0=None, tol=1e-8, max_iters=0, seed=0, hist_cap=1024, guard=0):
         """The k <= 8 lowest eigenpairs of A x = lam x (gen: of A x = lam B x with the B of set_eig_b) in the B-orthogonal complement of
         the columns of Y (n, ncon <= 16; None: no constraints).  On a handle set up with set_nullspace("constant") the constant vector
         is a constraint of its own accord: the pairs are the lowest nonzero ones, column 0 the Fiedler pair.  Returns what eigs
@@ -1471,7 +1574,7 @@ class sp_matrix_mg:
         Yf, ncon = self._constraints(Y)
         fn = lambda h, kk, X, ldx, *rest: lib.sparsh_eigs_con(h, int(bool(gen)), kk, X, ldx, ncon, None if Yf is None else _dp(Yf),
                                                              max(self.nrow, 1), *rest)
-        return self._eigs(fn, k, X0, tol, max_iters, seed, hist_cap)
+        return self._eigs(fn, k, X0, tol, max_iters, seed, hist_cap, guard)
 
     def eigs_con_dev(self, k, X_dev, ldx, ncon=0, Y_dev=None, ldy=0, gen=False, tol=1e-8, max_iters=0, hist_cap=1024):
         """eigs_dev under constraints: Y_dev a column-major device array of ncon columns.  Returns what eigs_dev returns."""
@@ -1567,9 +1670,10 @@ class sp_matrix_mg:
         """Average seconds of one block launch on the level's resident block buffers: "spmv_dot" (0) or "jacobi_pingpong_resident" (1);
         on the eigensolver's resident blocks: "eig_gram" (2, the twelve-pair Gram launch with its finalise) or "eig_update" (3); with
         the generalised solver's blocks and a B set: "eig_update_gen" (4) or "eig_b_spmv" (5); after a constrained eigen solve of this
-        width: "eig_con_project" (7), one projection with the constraints that solve left resident."""
+        width: "eig_con_project" (7), one projection with the constraints that solve left resident; under set_eig("ortho") with a B
+        set: "eig_transform" (8, three blocks in place) or "eig_ortho_apply" (9, the masked subtraction)."""
         ops = {"spmv_dot": 0, "jacobi_pingpong_resident": 1, "eig_gram": 2, "eig_update": 3, "eig_update_gen": 4, "eig_b_spmv": 5,
-               "eig_con_project": 7}
+               "eig_con_project": 7, "eig_transform": 8, "eig_ortho_apply": 9}
         sec = C.c_double()
         _check(lib.sparsh_bench_op_multi(self._h, ops[op] if isinstance(op, str) else op, int(level), int(nrhs), int(reps), C.byref(sec)))
         return sec.value

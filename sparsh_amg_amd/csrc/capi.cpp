@@ -12,6 +12,7 @@
 
 #include "../../include/sparsh_amg.h"
 #include "bcg_small.hpp"
+#include "eig_chol.hpp"
 #include "eig_small.hpp"
 #include "engine.hpp"
 
@@ -2215,7 +2216,7 @@ int sparsh_op_precond_multi(sparsh_handle h, int nrhs, const double *R, double *
 int sparsh_bench_op_multi(sparsh_handle h, int op, int level, int nrhs, int reps, double *avg_seconds)
 {
     REQUIRE_MULTI_ARGS(h, nrhs);
-    if (op < 0 || op > 7 || op == 6) return fail(SPARSH_EINVAL, "unknown op");  // (6 is not assigned)
+    if (op < 0 || op > 9 || op == 6) return fail(SPARSH_EINVAL, "unknown op");  // (6 is not assigned)
     if (reps <= 0 || !avg_seconds) return fail(SPARSH_EINVAL, "bad reps");
     REQUIRE_READY(h);
     REQUIRE_SINGLE(h);
@@ -2223,16 +2224,23 @@ int sparsh_bench_op_multi(sparsh_handle h, int op, int level, int nrhs, int reps
     Engine &E = *h->eng;
     const bool con = op == 7;  // the projection of the constrained eigensolver: only on what a constrained solve has left resident
     const bool eig = op >= 2;  // the eigensolver's launches run on its own resident blocks (level 0)
-    const bool gen = op >= 4 && !con;  // 4, 5: the generalised solver's blocks beside them, and its B
+    const bool ortho = op >= 8;        // 8, 9: the transform and the masked subtraction of the ortho basis, on the generalised solver's blocks
+    const bool gen = op >= 4 && !con;  // 4, 5, 8, 9: the generalised solver's blocks beside them, and its B
     if (gen && !E.eig_b_set()) return fail(SPARSH_ESTATE, "sparsh_eig_set_b has not been called");
+    if (ortho && E.eig_basis() != SPARSH_EIG_BASIS_ORTHO) return fail(SPARSH_ESTATE, "sparsh_set_eig_options has not selected SPARSH_EIG_BASIS_ORTHO");
     if (con) {
         if (E.eig_con_total() == 0 || E.eig_width_now() != multi_width(nrhs))
             return fail(SPARSH_ESTATE, "no constrained eigen solve of this width has reserved the constraint blocks");
     } else if (int rc = gen ? E.eig_reserve_gen(nrhs) : (eig ? E.eig_reserve(nrhs) : E.multi_reserve(nrhs)); rc != SPARSH_OK) {
         return fail(rc, E.error);
     }
+    if (ortho)
+        if (int rc = E.eig_ortho_reserve(); rc != SPARSH_OK) return fail(rc, E.error);
     hipStream_t st = E.stream();
-    auto launch = [&]() { return con ? E.bench_eig_con_launch() : (eig ? E.bench_eig_launch(op) : E.bench_multi_launch(op, level)); };
+    auto launch = [&]() {
+        if (ortho) return E.bench_eig_ortho_launch(op);
+        return con ? E.bench_eig_con_launch() : (eig ? E.bench_eig_launch(op) : E.bench_multi_launch(op, level));
+    };
     for (int i = 0; i < 3; ++i) launch();
     hipEvent_t e0, e1;
     (void)hipEventCreate(&e0);
@@ -2256,6 +2264,7 @@ int sparsh_bench_op_multi(sparsh_handle h, int op, int level, int nrhs, int reps
     if (!(h) || !(h)->eng) return fail(SPARSH_EINVAL, "null handle");                                                         \
     if ((nev) < 1 || (nev) > SPARSH_MAX_RHS) return fail(SPARSH_EINVAL, "nev must be 1 .. SPARSH_MAX_RHS (8)");                 \
     if ((nev) > (h)->eng->n0()) return fail(SPARSH_EINVAL, "nev exceeds the number of rows");                                  \
+    if ((h)->eng->eig_wanted() > (nev)) return fail(SPARSH_EINVAL, "wanted (sparsh_set_eig_options) exceeds nev"); \
     if (!(X) || !(lambda) || !(iters) || !(status) || ((hist_cap) > 0 && !(hist))) return fail(SPARSH_EINVAL, "NULL array"); \
     if ((hist_cap) < 0) return fail(SPARSH_EINVAL, "hist_cap < 0");                                                           \
     if ((ldx) < (h)->eng->n0()) return fail(SPARSH_EINVAL, "ldx must be at least the number of rows");                         \
@@ -2415,6 +2424,7 @@ int sparsh_eig_info(sparsh_handle h, int *width, long *bytes, int *restarts)
     if (!(h) || !(h)->eng) return fail(SPARSH_EINVAL, "null handle");                                                                  \
     if ((nev) < 1 || (nev) > SPARSH_MAX_RHS) return fail(SPARSH_EINVAL, "nev must be 1 .. SPARSH_MAX_RHS (8)");                          \
     if ((nev) > (h)->eng->n0()) return fail(SPARSH_EINVAL, "nev exceeds the number of rows");                                           \
+    if ((h)->eng->eig_wanted() > (nev)) return fail(SPARSH_EINVAL, "wanted (sparsh_set_eig_options) exceeds nev"); \
     if (!(X) || !(lambda) || !(iters) || !(status) || ((hist_cap) > 0 && !(hist))) return fail(SPARSH_EINVAL, "NULL array");          \
     if ((hist_cap) < 0) return fail(SPARSH_EINVAL, "hist_cap < 0");                                                                    \
     if ((ldx) < (h)->eng->n0()) return fail(SPARSH_EINVAL, "ldx must be at least the number of rows");                                  \
@@ -2709,6 +2719,153 @@ int sparsh_op_eig_update_gen(sparsh_handle h, int n, int k, const double *const 
         ok = stage.get(out[o]);
     }
     return done(E, ok);
+}
+
+// ---- the orthonormalised basis and the guard vectors of the eigensolver (SPARSH_EIG_BASIS_ORTHO; eig_ortho_kernels.hip, eig_chol.hpp) ----
+
+int sparsh_set_eig_options(sparsh_handle h, int basis, int wanted)
+{
+    if (!h || !h->eng) return fail(SPARSH_EINVAL, "null handle");
+    if (basis != SPARSH_EIG_BASIS_PLAIN && basis != SPARSH_EIG_BASIS_ORTHO)
+        return fail(SPARSH_EINVAL, "basis must be SPARSH_EIG_BASIS_PLAIN (0) or SPARSH_EIG_BASIS_ORTHO (1)");
+    if (wanted < 0 || wanted > SPARSH_MAX_RHS) return fail(SPARSH_EINVAL, "wanted must be 0 .. SPARSH_MAX_RHS (8)");
+    return h->eng->set_eig_options(basis, wanted);
+}
+
+int sparsh_eig_options(sparsh_handle h, int *basis, int *wanted)
+{
+    if (!h || !h->eng) return fail(SPARSH_EINVAL, "null handle");
+    if (basis) *basis = h->eng->eig_basis();
+    if (wanted) *wanted = h->eng->eig_wanted();
+    return SPARSH_OK;
+}
+
+int sparsh_eig_ortho_info(sparsh_handle h, int *dropped_w, int *dropped_p, long *bytes)
+{
+    if (!h || !h->eng) return fail(SPARSH_EINVAL, "null handle");
+    if (dropped_w) *dropped_w = h->eng->eig_dropped_w();
+    if (dropped_p) *dropped_p = h->eng->eig_dropped_p();
+    if (bytes) *bytes = (long)h->eng->eig_ortho_bytes();
+    return SPARSH_OK;
+}
+
+int sparsh_debug_eig_chol(int m, const double *G, const int *mask_in, double *T, int *mask_out)
+{
+    if (m < 1 || m > kEigCholMax) return fail(SPARSH_EINVAL, "m must be 1 .. 8");
+    if (!G || !mask_in || !T || !mask_out) return fail(SPARSH_EINVAL, "NULL array");
+    double mi[kEigCholMax], mo[kEigCholMax], L[kEigCholMax * kEigCholMax] = {0.0}, d[kEigCholMax] = {0.0}, z[kEigCholMax] = {0.0};
+    for (int i = 0; i < m; ++i) mi[i] = mask_in[i] ? 1.0 : 0.0;
+    (void)eig_chol(m, G, m, mi, T, m, mo, L, d, z);
+    for (int i = 0; i < m; ++i) mask_out[i] = mo[i] != 0.0 ? 1 : 0;
+    return SPARSH_OK;
+}
+
+int sparsh_op_eig_chol_small(sparsh_handle h, int W, const double *G, const int *mask_in, double *T, int *mask_out)
+{
+    REQUIRE_EIG_OP(h, 1);
+    if (W != 2 && W != 4 && W != 8) return fail(SPARSH_EINVAL, "W must be 2, 4 or 8");
+    if (!G || !mask_in || !T || !mask_out) return fail(SPARSH_EINVAL, "NULL array");
+    Engine &E = *h->eng;
+    double m[kEigCholMax];
+    for (int i = 0; i < W; ++i) m[i] = mask_in[i] ? 1.0 : 0.0;
+    DBuf dg(E, (size_t)W * W, G), dm(E, (size_t)W, m), dt(E, (size_t)W * W);
+    if (!dg.p || !dm.p || !dt.p) return fail(SPARSH_ENODEV, "device allocation or H2D copy failed");
+    launch_eig_chol_small(W, dg.p, dm.p, dt.p, dm.p, E.stream());  // the mask is replaced in place, as the second pass over W does
+    if (!dt.get(T) || !dm.get(m)) return done(E, false);
+    for (int i = 0; i < W; ++i) mask_out[i] = m[i] != 0.0 ? 1 : 0;
+    return done(E, true);
+}
+
+int sparsh_op_eig_active_mask(sparsh_handle h, int k, int gen, double tol, const double *theta, const double *rn, const double *bn, int *mask)
+{
+    REQUIRE_EIG_OP(h, 1);
+    if (k < 1 || k > SPARSH_MAX_RHS) return fail(SPARSH_EINVAL, "k must be 1 .. SPARSH_MAX_RHS (8)");
+    if (!theta || !rn || !mask || (gen && !bn)) return fail(SPARSH_EINVAL, "NULL array");
+    Engine &E = *h->eng;
+    const int W = multi_width(k);
+    std::vector<double> th(W, 0.0), r(W, 0.0), b(W, 0.0), m(3 * (size_t)W, -1.0);
+    std::copy(theta, theta + k, th.begin());
+    std::copy(rn, rn + k, r.begin());
+    if (gen) std::copy(bn, bn + k, b.begin());
+    DBuf dth(E, (size_t)W, th.data()), dr(E, (size_t)W, r.data()), db(E, (size_t)W, b.data()), dm(E, 3 * (size_t)W, m.data());
+    if (!dth.p || !dr.p || !db.p || !dm.p) return fail(SPARSH_ENODEV, "device allocation or H2D copy failed");
+    launch_eig_active_mask(W, k, gen != 0, tol, dth.p, dr.p, db.p, dm.p, E.stream());
+    if (!dm.get(m.data())) return done(E, false);
+    for (int c = W; c < 3 * W; ++c)
+        if (m[c] != 0.0) return fail(SPARSH_ENUMERIC, "the masks of W and P were not cleared");
+    for (int c = k; c < W; ++c)
+        if (m[c] != 0.0) return fail(SPARSH_ENUMERIC, "a padding column is active");
+    for (int c = 0; c < k; ++c) mask[c] = m[c] != 0.0 ? 1 : 0;
+    return done(E, true);
+}
+
+int sparsh_op_eig_transform(sparsh_handle h, int n, int k, int nb, double *const V[3], const double *T)
+{
+    REQUIRE_EIG_OP(h, n);
+    if (k < 1 || k > SPARSH_MAX_RHS) return fail(SPARSH_EINVAL, "k must be 1 .. SPARSH_MAX_RHS (8)");
+    if (nb < 1 || nb > 3) return fail(SPARSH_EINVAL, "nb must be 1 .. 3");
+    if (!V || !T) return fail(SPARSH_EINVAL, "NULL array");
+    for (int b = 0; b < nb; ++b)
+        if (!V[b]) return fail(SPARSH_EINVAL, "NULL array");
+    Engine &E = *h->eng;
+    const int W = multi_width(k);
+    const size_t len = (size_t)n * W, cm = (size_t)n * k;
+    std::vector<double> tp((size_t)W * W, 0.0);
+    for (int a = 0; a < k; ++a)
+        for (int b = 0; b < k; ++b) tp[(size_t)a * W + b] = T[a * k + b];
+    DBuf stage(E, cm), dt(E, tp.size(), tp.data());
+    std::vector<std::unique_ptr<DBuf>> blk;
+    bool ok = stage.p && dt.p;
+    double *dev[3] = {nullptr, nullptr, nullptr};
+    for (int b = 0; b < nb && ok; ++b) {
+        blk.emplace_back(new DBuf(E, len));
+        ok = blk.back()->p && hipMemcpy(stage.p, V[b], cm * 8, hipMemcpyHostToDevice) == hipSuccess;
+        if (ok) launch_interleave(n, k, W, stage.p, n, blk.back()->p, E.stream());
+        if (ok) ok = hipStreamSynchronize(E.stream()) == hipSuccess;
+        dev[b] = blk.back()->p;
+    }
+    if (!ok) return fail(SPARSH_ENODEV, "device allocation or H2D copy failed");
+    launch_eig_transform(n, W, k, nb, dev, dt.p, E.stream());
+    std::vector<double> full(len);
+    for (int b = 0; b < nb; ++b) {
+        (void)hipStreamSynchronize(E.stream());
+        if (hipMemcpy(full.data(), dev[b], len * 8, hipMemcpyDeviceToHost) != hipSuccess) return done(E, false);
+        for (size_t i = 0; i < (size_t)n; ++i) {
+            for (int c = 0; c < k; ++c) V[b][(size_t)c * n + i] = full[i * W + c];
+            for (int c = k; c < W; ++c)  // (bitwise: a -0.0 or a NaN in a padding column is caught too)
+                if (full[i * W + c] != 0.0 || std::signbit(full[i * W + c])) return fail(SPARSH_ENUMERIC, "a padding column of a transformed block is not zero");
+        }
+    }
+    return done(E, true);
+}
+
+int sparsh_op_eig_ortho_apply(sparsh_handle h, int n, int k, const double *X, const double *C, const int *mask, const double *W0, double *Wout)
+{
+    REQUIRE_EIG_OP(h, n);
+    if (k < 1 || k > SPARSH_MAX_RHS) return fail(SPARSH_EINVAL, "k must be 1 .. SPARSH_MAX_RHS (8)");
+    if (!X || !C || !mask || !W0 || !Wout) return fail(SPARSH_EINVAL, "NULL array");
+    Engine &E = *h->eng;
+    const int W = multi_width(k);
+    const size_t len = (size_t)n * W, cm = (size_t)n * k;
+    std::vector<double> cp((size_t)W * W, 0.0), mk(W, 0.0);
+    for (int a = 0; a < k; ++a)
+        for (int b = 0; b < k; ++b) cp[(size_t)a * W + b] = C[a * k + b];
+    for (int c = 0; c < k; ++c) mk[c] = mask[c] ? 1.0 : 0.0;
+    DBuf dx(E, cm, X), dw(E, cm, W0), bx(E, len), bw(E, len), bo(E, len), dc(E, cp.size(), cp.data()), dm(E, (size_t)W, mk.data());
+    if (!dx.p || !dw.p || !bx.p || !bw.p || !bo.p || !dc.p || !dm.p) return fail(SPARSH_ENODEV, "device allocation or H2D copy failed");
+    launch_interleave(n, k, W, dx.p, n, bx.p, E.stream());
+    launch_interleave(n, k, W, dw.p, n, bw.p, E.stream());
+    double *dst = Wout == W0 ? bw.p : bo.p;  // W0 == Wout on the host: in place on the device too
+    launch_eig_ortho_apply(n, W, k, bx.p, dc.p, dm.p, bw.p, dst, E.stream());
+    std::vector<double> full(len);
+    (void)hipStreamSynchronize(E.stream());
+    if (hipMemcpy(full.data(), dst, len * 8, hipMemcpyDeviceToHost) != hipSuccess) return done(E, false);
+    for (size_t i = 0; i < (size_t)n; ++i) {
+        for (int c = 0; c < k; ++c) Wout[(size_t)c * n + i] = full[i * W + c];
+        for (int c = k; c < W; ++c)
+            if (full[i * W + c] != 0.0 || std::signbit(full[i * W + c])) return fail(SPARSH_ENUMERIC, "a padding column of the block that came back is not zero");
+    }
+    return done(E, true);
 }
 
 // ---- block CG (engine_bcg.cpp, bcg_kernels.hip, bcg_small.hpp) ----

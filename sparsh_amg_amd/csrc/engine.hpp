@@ -445,6 +445,22 @@ public:
     size_t eig_con_bytes() const { return con_bytes_; }
     // bench: one projection (the Gram launch with its finalise, then the apply kernel) of the resident W block with the constraints the last constrained solve left
     int bench_eig_con_launch();
+    // ---- the orthonormalised basis and the guard vectors (SPARSH_EIG_BASIS_ORTHO, `wanted`; sparsh_set_eig_options).  Both settings
+    // are the handle's and survive setup; they need no device.  Under the ortho basis the active mask is decided on the device, W is
+    // made B-orthogonal to X and B-orthonormalised by Cholesky-QR twice and the active columns of P are B-orthonormalised, every
+    // iteration; the plain basis issues exactly the launches it always had.  The mode's own device memory (three masks and two W x W
+    // matrices at the width in force) is reserved at the first ortho solve for a width, freed with the solver's blocks or by a change
+    // of basis and counted by eig_ortho_bytes(), never by eig_bytes().
+    int set_eig_options(int basis, int wanted);
+    int eig_basis() const { return eig_basis_; }
+    int eig_wanted() const { return eig_wanted_; }
+    int eig_dropped_w() const { return eig_dropped_[0]; }
+    int eig_dropped_p() const { return eig_dropped_[1]; }
+    size_t eig_ortho_bytes() const { return ortho_bytes_; }
+    // bench: 8 = the transform of three blocks (P, AP, BP) with the resident T, 9 = the masked subtraction W <- W - X C, on the
+    // resident blocks of the generalised solver and the mode's small arrays
+    int bench_eig_ortho_launch(int op);
+    int eig_ortho_reserve();  // after eig_reserve: the masks and small matrices at width ew_
 
     // device memory helpers
     void *dalloc(size_t bytes);
@@ -635,6 +651,18 @@ private:
     void eig_b_spmv(const double *x, double *y);  // y = B x on interleaved blocks of width ew_
     void eig_b_forget();                          // B went with allocs_ (setup): drop the pointers
     void eig_update(bool gen, int k);             // step 6 in place on the resident blocks
+    // SPARSH_EIG_BASIS_ORTHO: masks = [active, W in basis, P in basis] (W doubles each), oG_ the Gram matrix or C of one pair, oT_ the
+    // transform; in ortho_allocs_
+    void eig_ortho_release();
+    void eig_ortho_forget();
+    // one orthonormalisation of the block V (B V = BV; nullptr: BV is V) on the columns of mask_in: the one-pair Gram launch, the small
+    // Cholesky step and the transform of V, BV and, when given, AV
+    void eig_ortho_pass(int k, double *V, double *BV, double *AV, const double *mask_in, double *mask_out);
+    int eig_basis_ = 0, eig_wanted_ = 0;
+    int eig_dropped_[2] = {0, 0};  // dropped columns of W and of P in the last solve
+    size_t ortho_bytes_ = 0;
+    double *oM_ = nullptr, *oG_ = nullptr, *oT_ = nullptr;
+    std::vector<void *> ortho_allocs_;
     int ew_ = 0;        // width in force (0: nothing allocated)
     size_t eig_bytes_ = 0;
     int eig_restarts_ = 0;

@@ -19,7 +19,8 @@ namespace sparsh {
 
 namespace {
 
-constexpr int kEigPinnedDown = 2 * kEigSmallMax * kEigSmallMax + kMultiMax;  // both Gram matrices and the residual norms
+// both Gram matrices and the residual norms, then the three masks of the ortho basis
+constexpr int kEigPinnedDown = 2 * kEigSmallMax * kEigSmallMax + kMultiMax + 3 * kMultiMax;
 constexpr int kEigPinnedUp = 3 * kMultiMax * kMultiMax + kMultiMax;          // Cx, Cw, Cp and theta
 
 }  // namespace
@@ -33,6 +34,76 @@ void Engine::eig_forget()
     eX_ = eAX_ = eW_ = eAW_ = eP_ = eAP_ = eR_ = epart_ = eG_ = ecoef_ = nullptr;
     eBX_ = eBW_ = eBP_ = nullptr;
     eig_con_forget();
+    eig_ortho_forget();
+}
+
+void Engine::eig_ortho_forget()
+{
+    ortho_bytes_ = 0;
+    ortho_allocs_.clear();
+    oM_ = oG_ = oT_ = nullptr;
+}
+
+void Engine::eig_ortho_release()
+{
+    if (st_ && !ortho_allocs_.empty()) (void)hipStreamSynchronize(st_);
+    for (void *p : ortho_allocs_) dfree(p);
+    eig_ortho_forget();
+}
+
+// the handle's settings; a change of basis gives the mode's own memory back
+int Engine::set_eig_options(int basis, int wanted)
+{
+    if (basis != eig_basis_) eig_ortho_release();
+    eig_basis_ = basis;
+    eig_wanted_ = wanted;
+    return SPARSH_OK;
+}
+
+// the masks and the two small matrices at the width in force (a change of width has dropped them with the blocks)
+int Engine::eig_ortho_reserve()
+{
+    if (oM_) return SPARSH_OK;
+    const int W = ew_;
+    bool ok = true;
+    auto take = [&](size_t doubles) -> double * {
+        if (!ok) return nullptr;
+        const size_t bytes = doubles * 8;
+        double *p = static_cast<double *>(dalloc(bytes));
+        if (!p || !check(hipMemsetAsync(p, 0, bytes, st_), "hipMemsetAsync")) {
+            if (p) dfree(p);
+            ok = false;
+            return nullptr;
+        }
+        ortho_allocs_.push_back(p);
+        ortho_bytes_ += bytes;
+        return p;
+    };
+    oM_ = take((size_t)3 * W);
+    oG_ = take((size_t)W * W);
+    oT_ = take((size_t)W * W);
+    if (!ok) {
+        eig_ortho_release();
+        return SPARSH_ENODEV;
+    }
+    return SPARSH_OK;
+}
+
+// (the Gram partials are free wherever the loop orthonormalises: the launches that filled them last have been read out on the stream)
+void Engine::eig_ortho_pass(int k, double *V, double *BV, double *AV, const double *mask_in, double *mask_out)
+{
+    const int n = lev_[0].n, W = ew_;
+    GramPairs one{};
+    one.u[0] = V;
+    one.v[0] = BV ? BV : V;
+    one.dst[0] = 0;
+    launch_gram_multi(n, W, 1, one, epart_, oG_, W, st_);
+    launch_eig_chol_small(W, oG_, mask_in, oT_, mask_out, st_);
+    double *blocks[3] = {V, nullptr, nullptr};
+    int nb = 1;
+    if (BV) blocks[nb++] = BV;
+    if (AV) blocks[nb++] = AV;
+    launch_eig_transform(n, W, k, nb, blocks, oT_, st_);
 }
 
 void Engine::eig_con_forget()
@@ -46,9 +117,10 @@ void Engine::eig_con_forget()
 
 void Engine::eig_release()
 {
-    if (st_ && !(eig_allocs_.empty() && con_allocs_.empty())) (void)hipStreamSynchronize(st_);
+    if (st_ && !(eig_allocs_.empty() && con_allocs_.empty() && ortho_allocs_.empty())) (void)hipStreamSynchronize(st_);
     for (void *p : eig_allocs_) dfree(p);
     for (void *p : con_allocs_) dfree(p);
+    for (void *p : ortho_allocs_) dfree(p);
     eig_forget();
 }
 
@@ -222,7 +294,9 @@ void Engine::eig_update(bool gen, int k)
 
 // the loop of both solvers.  gen: the pencil (A, B) with B S carried beside A S; the standard solve's launches are those it always had.
 // con: the constrained entry points, which take null-space handles (the constant vector is then one more constraint); with no
-// constraint at all the launches are those of con == nullptr
+// constraint at all the launches are those of con == nullptr.  The handle's basis (set_eig_options) picks the loop body: under the
+// plain basis the launches are those the solver always had; under the ortho basis the active mask is decided on the device and W
+// and P are B-orthonormalised before the Gram launch.  `wanted` ends a solve in either once the lowest `wanted` columns are inactive.
 int Engine::eigs_run(bool gen, int nev, double *X, long ldx, double tol, int max_iters, double *lambda, double *hist, int hist_cap, int *iters,
                      int *status, double *seconds, const EigCon *con)
 {
@@ -249,12 +323,22 @@ int Engine::eigs_run(bool gen, int nev, double *X, long ldx, double tol, int max
     if (int rc = gen ? eig_reserve_gen(nev) : eig_reserve(nev); rc != SPARSH_OK) return rc;
     if (mt > 0)
         if (int rc = eig_con_reserve(mt, gen); rc != SPARSH_OK) return rc;
+    const bool ortho = eig_basis_ == SPARSH_EIG_BASIS_ORTHO;
+    if (eig_wanted_ > nev) {
+        error = "wanted exceeds nev: sparsh_set_eig_options asked for more wanted columns than this solve has";
+        return SPARSH_EINVAL;
+    }
+    if (ortho)
+        if (int rc = eig_ortho_reserve(); rc != SPARSH_OK) return rc;
+    const int need = (eig_wanted_ > 0 && eig_wanted_ < nev) ? eig_wanted_ : nev;  // the columns whose convergence ends the solve
     if (max_iters <= 0) max_iters = prm_.max_iter;
     const int W = ew_, n = lev_[0].n, k = nev, ld = 3 * W;
     const size_t len = (size_t)n * W;
     const int ndown = 2 * ld * ld + W, nup = 3 * W * W + W;
     double *down = epinned_, *up = epinned_ + kEigPinnedDown;
     eig_restarts_ = 0;
+    eig_dropped_[0] = eig_dropped_[1] = 0;
+    const double *mdown = down + ndown;  // the masks as they came down: active, W in the basis, P in the basis
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (seconds) {
         HIPCHK(hipEventCreate(&e0));
@@ -272,7 +356,8 @@ int Engine::eigs_run(bool gen, int nev, double *X, long ldx, double tol, int max
     double GA[kEigSmallMax * kEigSmallMax], GB[kEigSmallMax * kEigSmallMax], C[kEigSmallMax * kMultiMax];
     int idx[kEigSmallMax];
 
-    auto read_down = [&](int first, int count) {  // G[first, first + count) -> down[first, ...), one pinned read
+    auto read_down = [&](int first, int count) {  // G[first, first + count) -> down[first, ...), one pinned read (ortho: with the masks)
+        if (ortho) HIPCHK(hipMemcpyAsync(down + ndown, oM_, (size_t)3 * W * 8, hipMemcpyDeviceToHost, st_));
         HIPCHK(hipMemcpyAsync(down + first, eG_ + first, (size_t)count * 8, hipMemcpyDeviceToHost, st_));
         HIPCHK(hipStreamSynchronize(st_));
     };
@@ -392,7 +477,38 @@ int Engine::eigs_run(bool gen, int nev, double *X, long ldx, double tol, int max
         if (gen) launch_eig_residual_gen(n, W, eAX_, eBX_, theta_dev, eR_, epart_, norms, bnorms, st_);  // (the Gram partials are free here)
         else launch_eig_residual(n, W, eAX_, eX_, theta_dev, eR_, rpart, norms, st_);
         const bool last = it >= max_iters;
-        if (!last) {
+        if (ortho) launch_eig_active_mask(W, k, gen, tol, theta_dev, norms, gen ? bnorms : norms, oM_, st_);
+        if (!last && ortho) {
+            // P on its active columns, then 3. W = M R made B-orthogonal to X and B-orthonormalised twice (B W follows W by the same
+            // transforms), AW = A W ; 4. the Gram matrices as in the plain loop
+            if (have_p) eig_ortho_pass(k, eP_, gen ? eBP_ : nullptr, eAP_, oM_, oM_ + 2 * W);
+            vcycle_multi(eR_);
+            const double *w0 = mlev_[0].x;
+            if (mt > 0) {
+                eig_con_project(mlev_[0].x, eW_);
+                w0 = eW_;
+            }
+            GramPairs one{};
+            one.u[0] = gen ? eBX_ : eX_;
+            one.v[0] = w0;
+            one.dst[0] = 0;
+            launch_gram_multi(n, W, 1, one, epart_, oG_, W, st_);                 // C = (BX)^T W0
+            launch_eig_ortho_apply(n, W, k, eX_, oG_, oM_, w0, eW_, st_);         // stands in for the copy
+            if (have_p) {
+                // W against the orthonormalised P as well, in place: without it W and P grow parallel near convergence and the
+                // Rayleigh-Ritz pencil loses its accuracy just above the breakdown rule (P's dropped and inactive columns are zero)
+                one.u[0] = gen ? eBP_ : eP_;
+                one.v[0] = eW_;
+                launch_gram_multi(n, W, 1, one, epart_, oG_, W, st_);             // C = (BP)^T W
+                launch_eig_ortho_apply(n, W, k, eP_, oG_, oM_, eW_, eW_, st_);
+            }
+            if (gen) eig_b_spmv(eW_, eBW_);
+            eig_ortho_pass(k, eW_, gen ? eBW_ : nullptr, nullptr, oM_, oM_ + W);
+            eig_ortho_pass(k, eW_, gen ? eBW_ : nullptr, nullptr, oM_ + W, oM_ + W);
+            multi_spmv_dot(0, eW_, eAW_, mpart0_);
+            launch_gram_multi(n, W, kEigPairs, prs, epart_, eG_, ld, st_);
+            read_down(0, ndown);
+        } else if (!last) {
             // 3. W = M R, AW = A W ; 4. the Gram matrices of S = [X, W, P] and A S
             vcycle_multi(eR_);
             if (mt > 0) eig_con_project(mlev_[0].x, eW_);  // W <- Pi (M R): the projection stands in for the copy
@@ -416,12 +532,15 @@ int Engine::eigs_run(bool gen, int nev, double *X, long ldx, double tol, int max
         int nact = 0;
         for (int c = 0; c < k; ++c) {
             // re-evaluated every iteration: soft locking
-            active[c] = gen ? rn[c] > tol * std::fabs(theta[c]) * bn[c] : rn[c] > tol * std::fabs(theta[c]);
+            if (ortho) active[c] = mdown[c] != 0.0;  // decided on the device, not a second time here
+            else active[c] = gen ? rn[c] > tol * std::fabs(theta[c]) * bn[c] : rn[c] > tol * std::fabs(theta[c]);
             nact += active[c];
             if (hist && it < hist_cap) hist[(size_t)c * hist_cap + it] = rn[c];
         }
         if (prm_.print_solve) std::printf("%d\t%d of %d eigenpairs active\n", it, nact, k);
-        if (nact == 0) {
+        int nneed = 0;
+        for (int c = 0; c < need; ++c) nneed += active[c];
+        if (nneed == 0) {  // (need < k: the columns past it are guard vectors and come back as they stand)
             converged = true;
             break;
         }
@@ -430,11 +549,16 @@ int Engine::eigs_run(bool gen, int nev, double *X, long ldx, double tol, int max
         // 5. Rayleigh-Ritz on [all of X, active of W, active of P]; after a breakdown once more without P
         int m = k;
         for (int c = 0; c < k; ++c)
-            if (active[c]) idx[m++] = W + c;
+            if (ortho ? mdown[W + c] != 0.0 : active[c]) idx[m++] = W + c;
         const int m_xw = m;
         if (have_p)
             for (int c = 0; c < k; ++c)
-                if (active[c]) idx[m++] = 2 * W + c;
+                if (ortho ? mdown[2 * W + c] != 0.0 : active[c]) idx[m++] = 2 * W + c;
+        if (ortho)
+            for (int c = 0; c < k; ++c) {
+                eig_dropped_[0] += active[c] && mdown[W + c] == 0.0;
+                eig_dropped_[1] += have_p && active[c] && mdown[2 * W + c] == 0.0;
+            }
         if (rayleigh_ritz(m) != 0) {
             ++eig_restarts_;
             if (m == m_xw || rayleigh_ritz(m_xw) != 0)
@@ -451,8 +575,8 @@ int Engine::eigs_run(bool gen, int nev, double *X, long ldx, double tol, int max
     note_hip(hipGetLastError(), "kernel launch during the eigensolve");
     if (fault_ != SPARSH_OK) return fault_;
     std::copy(theta, theta + k, lambda);
+    for (int c = 0; c < k; ++c) status[c] = active[c] ? SPARSH_ENOCONV : SPARSH_OK;  // (after convergence: guard vectors still active)
     if (converged) return SPARSH_OK;
-    for (int c = 0; c < k; ++c) status[c] = active[c] ? SPARSH_ENOCONV : SPARSH_OK;
     error = gen ? "iteration cap reached before ||A x - lambda B x|| <= tol |lambda| ||B x|| for every eigenpair"
                 : "iteration cap reached before ||A x - lambda x|| <= tol |lambda| for every eigenpair";
     return SPARSH_ENOCONV;
@@ -471,6 +595,18 @@ int Engine::bench_eig_launch(int op)
         eig_b_spmv(eX_, eBX_);
     } else {
         launch_eig_update(n, ew_, ew_, eX_, eW_, eP_, eAX_, eAW_, eAP_, ecoef_, eX_, eP_, eAX_, eAP_, st_);
+    }
+    return SPARSH_OK;
+}
+
+int Engine::bench_eig_ortho_launch(int op)
+{
+    const int n = lev_[0].n;
+    if (op == 8) {
+        double *blocks[3] = {eP_, eAP_, eBP_};
+        launch_eig_transform(n, ew_, ew_, 3, blocks, oT_, st_);
+    } else {
+        launch_eig_ortho_apply(n, ew_, ew_, eX_, oG_, oM_, eW_, eW_, st_);
     }
     return SPARSH_OK;
 }

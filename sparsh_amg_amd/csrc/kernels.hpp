@@ -506,6 +506,19 @@ void launch_eig_con_project(int n, int W, int mt, const double *Y, const double 
 // column col of the interleaved block v <- value
 void launch_eig_con_fill_column(int n, int W, int col, double value, double *v, hipStream_t st);
 
+// ---- the orthonormalised basis of the LOBPCG eigensolver (eig_ortho_kernels.hip; SPARSH_EIG_BASIS_ORTHO).  Masks are W doubles in
+// device memory, 1.0 in and 0.0 out; small matrices are W x W row-major.  No launch here reduces over rows or uses atomics.
+// masks[c] = rn_c > tol |theta_c| (gen: > (tol |theta_c|) bn_c) for c < k, 0 past k; masks[W .. 3 W) (the masks of W and P) are cleared
+void launch_eig_active_mask(int W, int k, bool gen, double tol, const double *theta, const double *rn, const double *bn, double *masks,
+                            hipStream_t st);
+// eig_chol of eig_chol.hpp on one wavefront: T and mask_out from the upper triangle of G and mask_in (mask_out may be mask_in)
+void launch_eig_chol_small(int W, const double *G, const double *mask_in, double *T, double *mask_out, hipStream_t st);
+// V <- V T in place on the nb <= 3 blocks V[0 .. nb), sums over c < k ascending, columns j >= k written as zeros
+void launch_eig_transform(int n, int W, int k, int nb, double *const V[3], const double *T, hipStream_t st);
+// dst = src - X C on the columns c < k of the mask (sum over j < k ascending, one subtraction), exact zeros elsewhere; dst may be src
+void launch_eig_ortho_apply(int n, int W, int k, const double *X, const double *C, const double *mask, const double *src, double *dst,
+                            hipStream_t st);
+
 // ---- block CG on interleaved blocks (bcg_kernels.hip).  The columns of a block share one search space: the
 // scalars of block PCG become W x W matrices (row-major, device memory), solved for by bcg_small.hpp's LDL^T with dropped directions.
 constexpr int kBcgMaxGrid = 2048;  // workgroups of the two streaming kernels: one per 512 / W rows, capped at ~8 per CU

@@ -4,6 +4,7 @@ beside the block path's, and the rate of the new kernels against the copy rate D
     python tools/eig_ab.py [--out profiles/eig_lobpcg.txt] [--reps 20] [--step-seconds 420] [--max-iters 300]
     python tools/eig_ab.py --generalised [--out profiles/eig_gen_lobpcg.txt]
     python tools/eig_ab.py --constrained [--out profiles/eig_con_lobpcg.txt]
+    python tools/eig_ab.py --ortho [--guard 4] [--out profiles/eig_ortho_lobpcg.txt]
 
 Cases: poisson3d(216) with k = 4 and k = 8 under set_kernel_config(kind=0), fem_unstructured() with k = 4.  Every case runs in a
 process of its own under `timeout`; the first case that fails stops the rest.  Per case one JSON line:
@@ -30,6 +31,16 @@ null space, eigs_con_dev(8) with the implicit constant vector alone.  Per case:
   project_model_us, project_over_model           the byte model: the Gram launch reads n (mpad + W) 8 B, the apply reads the same and
                                                  writes n W 8 B, at 6.29 TB/s; gen reads Y and BY, the model counts mpad once per launch
   project_share                                  project_us over one iteration of the constrained solve
+--ortho [--guard G]: the orthonormalised basis and the guard vectors (set_eig).  Cases femgen:4, femgen:8 (the
+full-size pencil), fem:4, fem:8 (the standard problem on the same operator), femgen:4+G (k = 4 with G guard vectors, wanted = 4) and
+neu216:8 (the constrained solve on the Neumann box).  Every case solves twice on one handle, under the plain and under the ortho
+basis, and prints for each
+  rc, iterations, restarts, ms_per_iteration     one timed _dev call after a warm-up call
+  worst_rn_over_bound                            over the wanted columns, the last residual norm over tol |lambda| ||B x||
+  dropped_w, dropped_p, ortho_bytes              sparsh_eig_ortho_info after the ortho solve
+and, where a B is set, the two new launches against their byte model at 6.29 TB/s:
+  transform_us, transform_model_us               sparsh_bench_op_multi op 8: three blocks read and written in place, 6 block passes
+  ortho_apply_us, ortho_apply_model_us           op 9: X and W read, W written, 3 block passes
 """
 import argparse
 import json
@@ -46,6 +57,64 @@ COPY_BYTES_PER_S = 6.29e12  # the device-to-device copy rate DESIGN.md measures 
 CASES = ["p216:4", "p216:8", "fem:4"]
 CASES_GENERALISED = ["fem:4", "femgen:4", "fem:8", "femgen:8"]
 CASES_CONSTRAINED = ["femcon:8", "neu216:8"]
+CASES_ORTHO = ["femgen:4", "femgen:8", "fem:4", "fem:8", "femgen:4+{guard}", "neu216:8"]
+
+
+def run_case_ortho(case, reps, max_iters):
+    import scipy.sparse as sp
+
+    import sparsh_amg_amd as sa
+    from sparsh_amg_amd import problems
+
+    name, ks = case.split(":")
+    k, guard = (int(x) for x in ks.split("+")) if "+" in ks else (int(ks), 0)
+    kk = k + guard
+    gen, con = name == "femgen", name == "neu216"
+    M = None
+    if con:
+        rp, ci, v = problems.poisson3d_neumann(216)
+    else:
+        (rp, ci, v), M = problems.fem_pencil()
+    n = len(rp) - 1
+    A = sa.sp_matrix_mg(rp, ci, v)
+    if con:
+        A.set_nullspace("constant")
+    A.setup(sa.default_params(print_setup=0, print_solve=0))
+    if gen:
+        A.set_eig_b(*M)
+    W = 2 if kk <= 2 else (4 if kk <= 4 else 8)
+    X0 = np.ascontiguousarray(np.random.default_rng(0).standard_normal((n, kk)).T)
+    xd = A.dev_alloc(8 * n * kk)
+    rec = {"case": case, "rows": n, "k": k, "guard": guard, "width": W, "levels": A.nlevels}
+    Bs = sp.csr_matrix((M[2], M[1], M[0]), shape=(n, n)) if gen else None
+    for basis in ("plain", "ortho"):
+        A.set_eig(basis, wanted=k if guard else 0)
+        for _ in range(2):  # the first call reserves the blocks
+            A.h2d(xd, X0)
+            if con:
+                lam, iters, hist, status, sec, rc = A.eigs_con_dev(kk, xd, n, max_iters=max_iters, hist_cap=max_iters + 1)
+            else:
+                lam, iters, hist, status, sec, rc = (A.eigs_gen_dev if gen else A.eigs_dev)(kk, xd, n, max_iters=max_iters, hist_cap=max_iters + 1)
+        its = hist.shape[1] - 1
+        X = np.zeros((kk, n))
+        A.d2h(X, xd)
+        bn = np.linalg.norm(Bs @ X.T, axis=0) if gen else np.linalg.norm(X, axis=1)
+        over = hist[:, -1] / (1e-8 * np.abs(lam) * bn)
+        r = dict(rc=int(rc), iterations=its, restarts=A.eig_info()["restarts"], ms_per_iteration=round(sec * 1e3 / max(its, 1), 4),
+                 worst_rn_over_bound=float(np.max(over[:k])), lam=[float(x) for x in lam[:k]], active=[int(x != 0) for x in status])
+        if basis == "ortho":
+            r.update(A.eig_ortho_info())
+            r["ortho_bytes"] = r.pop("bytes")
+            if gen:
+                block = 8.0 * n * W
+                t8, t9 = (A.bench_op_multi(op, 0, nrhs=kk, reps=reps) for op in ("eig_transform", "eig_ortho_apply"))
+                r.update(transform_us=round(t8 * 1e6, 2), transform_model_us=round(6 * block / COPY_BYTES_PER_S * 1e6, 2),
+                         ortho_apply_us=round(t9 * 1e6, 2), ortho_apply_model_us=round(3 * block / COPY_BYTES_PER_S * 1e6, 2))
+        rec[basis] = r
+    A.set_eig("plain", wanted=0)
+    A.dev_free(xd)
+    A.close()
+    print(json.dumps(rec), flush=True)
 
 
 def run_case_constrained(case, reps, max_iters):
@@ -161,18 +230,22 @@ def main():
     ap.add_argument("--max-iters", type=int, default=300, help="the iteration cap of every solve")
     ap.add_argument("--generalised", action="store_true", help="the FEM pencil against its mass matrix, next to the standard solve")
     ap.add_argument("--constrained", action="store_true", help="eigs_con_dev: deflation on the FEM pencil, the singular Neumann box")
+    ap.add_argument("--ortho", action="store_true", help="plain against ortho basis (set_eig) on the FEM pencil, the standard problem and the Neumann box")
+    ap.add_argument("--guard", type=int, default=4, help="--ortho: the guard vectors of the k = 4 case with guards")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "eig_con_lobpcg.txt" if args.constrained else
-                                ("eig_gen_lobpcg.txt" if args.generalised else "eig_lobpcg.txt"))
+        args.out = os.path.join(ROOT, "profiles", "eig_ortho_lobpcg.txt" if args.ortho else ("eig_con_lobpcg.txt" if args.constrained else
+                                ("eig_gen_lobpcg.txt" if args.generalised else "eig_lobpcg.txt")))
     if args.case:
-        (run_case_constrained if args.constrained else run_case)(args.case, args.reps, args.max_iters)
+        (run_case_ortho if args.ortho else (run_case_constrained if args.constrained else run_case))(args.case, args.reps, args.max_iters)
         return 0
     lines = []
-    for case in (CASES_CONSTRAINED if args.constrained else (CASES_GENERALISED if args.generalised else CASES)):  # the driver itself never opens the GPU
+    cases = [c.format(guard=args.guard) for c in CASES_ORTHO] if args.ortho else (
+        CASES_CONSTRAINED if args.constrained else (CASES_GENERALISED if args.generalised else CASES))
+    for case in cases:  # the driver itself never opens the GPU
         cmd = ["timeout", "-k", "10", str(args.step_seconds), sys.executable, os.path.abspath(__file__), "--case", case, "--reps", str(args.reps),
-               "--max-iters", str(args.max_iters)] + (["--constrained"] if args.constrained else [])
+               "--max-iters", str(args.max_iters)] + (["--constrained"] if args.constrained else []) + (["--ortho"] if args.ortho else [])
         p = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
         sys.stdout.write(p.stdout)
         if p.returncode != 0:  # (a solve that ends at the cap is a result, SPARSH_ENOCONV in "rc", not a failure)
