@@ -466,6 +466,36 @@ int sparsh_op_gs_update(sparsh_handle h, int n, int nv, int precision, const dou
 int sparsh_op_gs_scale(sparsh_handle h, int n, int precision, const double *w, double d, double *v, double *vd, double *tail, int *ntail);
 int sparsh_op_gmres_small(sparsh_handle h, int m, int nblk, const double *hcol, const double *ccol, const double *ww_partial, double beta,
                           int k, double *hist, double *R, double *cs, double *sn, double *g, double *ny);
+/* Test hooks of the single-vector Krylov kernels (dot2, cg_update, cg_update_zero, p_update, xp_update, bicg_s, bicg_xr, bicg_p) and
+ * of finalize_kernel.  One launch through the launcher the loops use; the handle lends its stream and
+ * allocator only, n is free.  Vectors that are only read hold n doubles.  Every array a kernel writes -- updated vectors, partial
+ * sums, the history -- is padded: the host array holds SPARSH_OP_PAD doubles more than its logical length, goes to the device whole
+ * and comes back whole, so the caller sees whatever was written behind the end.  A partial-sum array has the logical length
+ * SPARSH_OP_PARTIALS (the cap of the elementwise grid); *nblk returns how many of them the launch wrote.  A host array given for two
+ * arguments is one device vector (BiCGStab's As, s, As, As); give the written arguments the padded array.  Coefficients are passed
+ * by value and put into the slots of a zeroed scalar block, alpha and nalpha each as given.
+ * sparsh_op_cg_update: zero = 0 cg_update_kernel; zero = 1 cg_update_zero_kernel<nt> with d (NULL: dconst), omega and z0.  x NULL:
+ * the deferred-x form.
+ * sparsh_op_finalize: `repeat` (1..64) back-to-back launch_finalize calls on the same arrays.  code 0..10 (the Fin codes), mode 0,
+ * 1 or 2; p0[nblk] (not read in mode 2, may be NULL there), p1[nblk1] or NULL; scal: the SPARSH_OP_SCALARS slots, in and out;
+ * hist: hist_cap (+ pad) doubles in and out, or NULL; it: the history slot, < 0: taken from the device counter, whose value goes in
+ * and comes out through *iter_ctr (>= 0).  Nothing is all-reduced between modes 1 and 2.
+ * SPARSH_EINVAL, device or not: NULL handle or required array, n <= 0, a code, mode, slot or count out of range. */
+#define SPARSH_OP_PAD 4
+#define SPARSH_OP_PARTIALS 2048
+#define SPARSH_OP_SCALARS 18
+int sparsh_op_dot2(sparsh_handle h, int n, const double *a, const double *b, const double *c, const double *d, double *p0, double *p1,
+                   int *nblk);
+int sparsh_op_cg_update(sparsh_handle h, int n, double alpha, double nalpha, const double *p, const double *Ap, double *x, double *r,
+                        double *partial, int *nblk, int zero, const double *d, double dconst, double omega, int nt, double *z0);
+int sparsh_op_p_update(sparsh_handle h, int n, double beta, const double *z, double *p);
+int sparsh_op_xp_update(sparsh_handle h, int n, double alpha, double beta, const double *z, double *p, double *x);
+int sparsh_op_bicg_s(sparsh_handle h, int n, double alpha, const double *r, const double *Ap, double *s);
+int sparsh_op_bicg_xr(sparsh_handle h, int n, double alpha, double omega1, const double *p1, const double *s1, const double *s,
+                      const double *As, const double *r0, double *x, double *r, double *q0, double *q1, int *nblk);
+int sparsh_op_bicg_p(sparsh_handle h, int n, double beta, double omega1, const double *r, const double *Ap, double *p);
+int sparsh_op_finalize(sparsh_handle h, int code, int mode, const double *p0, int nblk, const double *p1, int nblk1, double *scal,
+                       int slot_a, double *hist, int hist_cap, int it, int *iter_ctr, int repeat);
 
 /* Time `reps` back-to-back launches of one operator on resident device data with HIP events
  * on the engine's stream; returns average seconds per launch.  op: 0 spmv, 1 fused jacobi

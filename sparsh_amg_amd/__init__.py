@@ -302,6 +302,16 @@ def _load():
         "sparsh_op_gs_scale": (C.c_int, [H, C.c_int, C.c_int, c_dbl_p, C.c_double, c_dbl_p, c_dbl_p, c_dbl_p, c_int_p]),
         "sparsh_op_gmres_small": (C.c_int, [H, C.c_int, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p, C.c_double, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p,
                                             c_dbl_p, c_dbl_p, c_dbl_p]),
+        "sparsh_op_dot2": (C.c_int, [H, C.c_int] + [c_dbl_p] * 6 + [c_int_p]),
+        "sparsh_op_cg_update": (C.c_int, [H, C.c_int, C.c_double, C.c_double] + [c_dbl_p] * 5 + [c_int_p, C.c_int, c_dbl_p, C.c_double,
+                                          C.c_double, C.c_int, c_dbl_p]),
+        "sparsh_op_p_update": (C.c_int, [H, C.c_int, C.c_double, c_dbl_p, c_dbl_p]),
+        "sparsh_op_xp_update": (C.c_int, [H, C.c_int, C.c_double, C.c_double, c_dbl_p, c_dbl_p, c_dbl_p]),
+        "sparsh_op_bicg_s": (C.c_int, [H, C.c_int, C.c_double, c_dbl_p, c_dbl_p, c_dbl_p]),
+        "sparsh_op_bicg_xr": (C.c_int, [H, C.c_int, C.c_double, C.c_double] + [c_dbl_p] * 9 + [c_int_p]),
+        "sparsh_op_bicg_p": (C.c_int, [H, C.c_int, C.c_double, C.c_double, c_dbl_p, c_dbl_p, c_dbl_p]),
+        "sparsh_op_finalize": (C.c_int, [H, C.c_int, C.c_int, c_dbl_p, C.c_int, c_dbl_p, C.c_int, c_dbl_p, C.c_int, c_dbl_p, C.c_int,
+                                         C.c_int, c_int_p, C.c_int]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here = header/library mismatch: fail loudly
@@ -338,6 +348,31 @@ def _check(rc, allow=()):
     if rc != SPARSH_OK and rc not in allow:
         raise SparshError(rc, lib.sparsh_last_error().decode())
     return rc
+
+
+OP_PAD, OP_PARTIALS, OP_SCALARS = 4, 2048, 18  # SPARSH_OP_PAD, SPARSH_OP_PARTIALS, SPARSH_OP_SCALARS of sparsh_amg.h
+OP_SENTINEL = -7.25  # what the padding of a written array holds when it goes to the device
+
+
+class _OpArrays:
+    """The host arrays of one sparsh_op_* call of the Krylov kernels: written arguments become padded copies, and an object given for
+    several arguments maps to one array (so to one device vector)."""
+
+    def __init__(self):
+        self._seen = {}  # id -> (the object, kept alive; the array handed to the library)
+
+    def written(self, v):
+        a = np.concatenate([np.asarray(v, dtype=np.float64).ravel(), np.full(OP_PAD, OP_SENTINEL)])
+        self._seen[id(v)] = (v, a)
+        return a
+
+    def partials(self):
+        return self.written(np.full(OP_PARTIALS, OP_SENTINEL))
+
+    def read(self, v):
+        if id(v) not in self._seen:
+            self._seen[id(v)] = (v, np.ascontiguousarray(v, dtype=np.float64))
+        return self._seen[id(v)][1]
 
 
 def default_params(**kw) -> Params:
@@ -1747,6 +1782,110 @@ class sp_matrix_mg:
         _check(lib.sparsh_op_gmres_small(self._h, m, ww_partial.shape[1], _dp(hp), _dp(cp), _dp(ww_partial), float(beta), k, _dp(hist), _dp(R),
                                          _dp(cs), _dp(sn), _dp(g), _dp(ny)))
         return dict(hist=hist[:m], R=R[:m, :m].T.copy(), cs=cs[:m], sn=sn[:m], g=g[: m + 1], ny=ny[:k])
+
+    # ---- test hooks of the single-vector Krylov kernels and of finalize_kernel: one launch each, n comes from the arrays.  Every
+    # result is a dict; "tails" holds, per written array, what the device vector held behind its logical end (it went up filled with
+    # OP_SENTINEL).  An array object given for two arguments is one device vector.
+    def op_dot2(self, a, b, c, d):
+        """partial sums of a.b and c.d through launch_dot2: dict(p0, p1, nblk, tails)"""
+        m = _OpArrays()
+        p0, p1 = m.partials(), m.partials()
+        a, b, c, d = (m.read(v) for v in (a, b, c, d))
+        nblk = C.c_int()
+        _check(lib.sparsh_op_dot2(self._h, len(a), _dp(a), _dp(b), _dp(c), _dp(d), _dp(p0), _dp(p1), C.byref(nblk)))
+        k = nblk.value
+        return dict(p0=p0[:k].copy(), p1=p1[:k].copy(), nblk=k, tails=dict(p0=p0[k:], p1=p1[k:]))
+
+    def op_cg_update(self, alpha, p, Ap, x, r, nalpha=None, zero=False, d=None, dconst=1.0, omega=1.0, nt=False):
+        """x += alpha p (x None: deferred), r += nalpha Ap (nalpha None: -alpha), partial sums of r.r through launch_cg_update, or with
+        zero=True through launch_cg_update_zero (z0 = omega r / d, d None: dconst; nt: the nontemporal instantiation):
+        dict(x, r, z0, partial, nblk, tails)"""
+        m = _OpArrays()
+        n = len(r)
+        xo = None if x is None else m.written(x)
+        ro, part = m.written(r), m.partials()
+        z0 = m.written(np.zeros(n)) if zero else None
+        p, Ap = m.read(p), m.read(Ap)
+        d = None if d is None else m.read(d)
+        nblk = C.c_int()
+        ptr = lambda v: None if v is None else _dp(v)
+        _check(lib.sparsh_op_cg_update(self._h, n, float(alpha), float(-alpha if nalpha is None else nalpha), _dp(p), _dp(Ap), ptr(xo), _dp(ro),
+                                       _dp(part), C.byref(nblk), int(zero), ptr(d), float(dconst), float(omega), int(nt), ptr(z0)))
+        k = nblk.value
+        tails = dict(r=ro[n:], partial=part[k:])
+        if xo is not None:
+            tails["x"] = xo[n:]
+        if zero:
+            tails["z0"] = z0[n:]
+        return dict(x=None if xo is None else xo[:n].copy(), r=ro[:n].copy(), z0=z0[:n].copy() if zero else None, partial=part[:k].copy(),
+                    nblk=k, tails=tails)
+
+    def op_p_update(self, beta, z, p):
+        """p = 1.0 z + beta p through launch_p_update: dict(p, tails)"""
+        m = _OpArrays()
+        n = len(p)
+        po = m.written(p)
+        z = m.read(z)
+        _check(lib.sparsh_op_p_update(self._h, n, float(beta), _dp(z), _dp(po)))
+        return dict(p=po[:n].copy(), tails=dict(p=po[n:]))
+
+    def op_xp_update(self, alpha, beta, z, p, x):
+        """x += alpha p ; p = 1.0 z + beta p through launch_xp_update: dict(x, p, tails)"""
+        m = _OpArrays()
+        n = len(p)
+        po, xo = m.written(p), m.written(x)
+        z = m.read(z)
+        _check(lib.sparsh_op_xp_update(self._h, n, float(alpha), float(beta), _dp(z), _dp(po), _dp(xo)))
+        return dict(x=xo[:n].copy(), p=po[:n].copy(), tails=dict(x=xo[n:], p=po[n:]))
+
+    def op_bicg_s(self, alpha, r, Ap):
+        """s = r - alpha Ap through launch_bicg_s: dict(s, tails)"""
+        m = _OpArrays()
+        n = len(r)
+        s = m.written(np.zeros(n))
+        r, Ap = m.read(r), m.read(Ap)
+        _check(lib.sparsh_op_bicg_s(self._h, n, float(alpha), _dp(r), _dp(Ap), _dp(s)))
+        return dict(s=s[:n].copy(), tails=dict(s=s[n:]))
+
+    def op_bicg_xr(self, alpha, omega1, p1, s1, s, As, r0, x, r):
+        """x = x + alpha p1 + omega1 s1 ; r = s - omega1 As ; partial sums of r.r0 and r.r through launch_bicg_xr:
+        dict(x, r, q0, q1, nblk, tails)"""
+        m = _OpArrays()
+        n = len(x)
+        xo, ro, q0, q1 = m.written(x), m.written(r), m.partials(), m.partials()
+        p1, s1, s, As, r0 = (m.read(v) for v in (p1, s1, s, As, r0))
+        nblk = C.c_int()
+        _check(lib.sparsh_op_bicg_xr(self._h, n, float(alpha), float(omega1), _dp(p1), _dp(s1), _dp(s), _dp(As), _dp(r0), _dp(xo), _dp(ro),
+                                     _dp(q0), _dp(q1), C.byref(nblk)))
+        k = nblk.value
+        return dict(x=xo[:n].copy(), r=ro[:n].copy(), q0=q0[:k].copy(), q1=q1[:k].copy(), nblk=k,
+                    tails=dict(x=xo[n:], r=ro[n:], q0=q0[k:], q1=q1[k:]))
+
+    def op_bicg_p(self, beta, omega1, r, Ap, p):
+        """p = r + beta (p - omega1 Ap) through launch_bicg_p: dict(p, tails)"""
+        m = _OpArrays()
+        n = len(p)
+        po = m.written(p)
+        r, Ap = m.read(r), m.read(Ap)
+        _check(lib.sparsh_op_bicg_p(self._h, n, float(beta), float(omega1), _dp(r), _dp(Ap), _dp(po)))
+        return dict(p=po[:n].copy(), tails=dict(p=po[n:]))
+
+    def op_finalize(self, code, p0, p1=None, scal=None, slot=0, mode=0, hist=None, it=0, counter=0, repeat=1):
+        """`repeat` launch_finalize calls of one code and mode on the partial sums p0 (None in mode 2) and p1 (or None), the scalar
+        block scal (None: zeros) and the history hist (or None; its length is hist_cap); it < 0: the slot comes from the device
+        counter, which starts at `counter`.  dict(scal, hist, counter, tails)"""
+        sc = np.zeros(OP_SCALARS) if scal is None else np.array(scal, dtype=np.float64)
+        assert sc.shape == (OP_SCALARS,)
+        m = _OpArrays()
+        cap = 0 if hist is None else len(hist)
+        ho = None if hist is None else m.written(hist)
+        p0 = None if p0 is None else m.read(p0)
+        p1 = None if p1 is None else m.read(p1)
+        ctr = C.c_int(int(counter))
+        ptr = lambda v: None if v is None else _dp(v)
+        _check(lib.sparsh_op_finalize(self._h, int(code), int(mode), ptr(p0), 1 if p0 is None else len(p0), ptr(p1), 0 if p1 is None else len(p1),
+                                      _dp(sc), int(slot), ptr(ho), cap, int(it), C.byref(ctr), int(repeat)))
+        return dict(scal=sc, hist=None if ho is None else ho[:cap].copy(), counter=ctr.value, tails={} if ho is None else dict(hist=ho[cap:]))
 
 
 

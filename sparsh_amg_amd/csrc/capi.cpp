@@ -3032,3 +3032,243 @@ int sparsh_op_bcg_dir(sparsh_handle h, int n, int k, const double *Z, const doub
 }
 
 }  // extern "C"
+
+// ---- operator-level hooks of the single-vector Krylov kernels and of finalize_kernel (kernels.hip): one launch through the loops' own
+// launcher on device vectors of the call's own; the handle lends its stream and allocator
+namespace {
+
+static_assert(SPARSH_OP_SCALARS == S_COUNT, "sparsh_amg.h: SPARSH_OP_SCALARS is the number of scalar slots");
+static_assert(SPARSH_OP_PARTIALS == kEwGridMax, "sparsh_amg.h: SPARSH_OP_PARTIALS is the cap of the elementwise grid");
+
+// host arrays of one call on the device: a host array given twice is one device vector (the first registration allocates, so the
+// padded -- written -- arguments are registered first)
+struct OpVecs {
+    Engine &E;
+    struct Ent {
+        const double *host;
+        std::unique_ptr<DBuf> buf;
+    };
+    std::vector<Ent> v;
+    bool ok = true, fits = true;
+    explicit OpVecs(Engine &e) : E(e) {}
+    double *dev(const double *host, size_t count)
+    {
+        if (!host) return nullptr;
+        for (Ent &e : v)
+            if (e.host == host) {
+                if (e.buf->n < count) fits = false;
+                return e.buf->p;
+            }
+        v.push_back(Ent{host, std::make_unique<DBuf>(E, count, host)});
+        if (!v.back().buf->p) ok = false;
+        return v.back().buf->p;
+    }
+    bool get(double *host)
+    {
+        if (!host) return true;
+        for (Ent &e : v)
+            if (e.host == host) return e.buf->get(host);
+        return false;
+    }
+    int status() const
+    {
+        if (!fits) return fail(SPARSH_EINVAL, "an array given for a written and a read argument must be the padded one");
+        return ok ? SPARSH_OK : fail(SPARSH_ENODEV, "device allocation or H2D copy failed");
+    }
+};
+
+// a zeroed scalar block with the given slots set
+struct OpScal {
+    double host[S_COUNT] = {};
+    OpScal &set(int slot, double v)
+    {
+        host[slot] = v;
+        return *this;
+    }
+};
+
+constexpr size_t kOpPartials = (size_t)SPARSH_OP_PARTIALS + SPARSH_OP_PAD;
+inline size_t op_padded(int n) { return (size_t)n + SPARSH_OP_PAD; }
+
+}  // namespace
+
+#define REQUIRE_KRYLOV_OP(h, n)                                       \
+    if (!(h) || !(h)->eng) return fail(SPARSH_EINVAL, "null handle"); \
+    if ((n) <= 0) return fail(SPARSH_EINVAL, "n <= 0")
+
+extern "C" {
+
+int sparsh_op_dot2(sparsh_handle h, int n, const double *a, const double *b, const double *c, const double *d, double *p0, double *p1,
+                   int *nblk)
+{
+    REQUIRE_KRYLOV_OP(h, n);
+    if (!a || !b || !c || !d || !p0 || !p1 || !nblk || p0 == p1) return fail(SPARSH_EINVAL, "null array");
+    REQUIRE_READY(h);
+    REQUIRE_SINGLE(h);
+    Engine &E = *h->eng;
+    OpVecs V(E);
+    double *dp0 = V.dev(p0, kOpPartials), *dp1 = V.dev(p1, kOpPartials);
+    const double *da = V.dev(a, (size_t)n), *db = V.dev(b, (size_t)n), *dc = V.dev(c, (size_t)n), *dd = V.dev(d, (size_t)n);
+    if (int rc = V.status(); rc != SPARSH_OK) return rc;
+    launch_dot2(n, da, db, dc, dd, dp0, dp1, nblk, E.stream());
+    return done(E, V.get(p0) && V.get(p1));
+}
+
+int sparsh_op_cg_update(sparsh_handle h, int n, double alpha, double nalpha, const double *p, const double *Ap, double *x, double *r,
+                        double *partial, int *nblk, int zero, const double *d, double dconst, double omega, int nt, double *z0)
+{
+    REQUIRE_KRYLOV_OP(h, n);
+    if (!p || !Ap || !r || !partial || !nblk) return fail(SPARSH_EINVAL, "null array");
+    if (zero != 0 && zero != 1) return fail(SPARSH_EINVAL, "zero must be 0 or 1");
+    if (nt != 0 && nt != 1) return fail(SPARSH_EINVAL, "nt must be 0 or 1");
+    if (zero && !z0) return fail(SPARSH_EINVAL, "null array: the zero-guess form writes z0");
+    if (x == r || (zero && (z0 == r || z0 == x))) return fail(SPARSH_EINVAL, "the written vectors must be distinct arrays");
+    REQUIRE_READY(h);
+    REQUIRE_SINGLE(h);
+    Engine &E = *h->eng;
+    OpVecs V(E);
+    OpScal s;
+    s.set(S_ALPHA, alpha).set(S_NALPHA, nalpha);
+    DBuf scal(E, (size_t)S_COUNT, s.host);
+    double *dx = V.dev(x, op_padded(n)), *dr = V.dev(r, op_padded(n)), *dz0 = zero ? V.dev(z0, op_padded(n)) : nullptr;
+    double *dpart = V.dev(partial, kOpPartials);
+    const double *dp = V.dev(p, (size_t)n), *dAp = V.dev(Ap, (size_t)n), *dd = zero ? V.dev(d, (size_t)n) : nullptr;
+    if (!scal.p) return fail(SPARSH_ENODEV, "device allocation failed");
+    if (int rc = V.status(); rc != SPARSH_OK) return rc;
+    if (zero) launch_cg_update_zero(n, scal.p, dp, dAp, dx, dr, dpart, nblk, dd, dconst, omega, dz0, E.stream(), nt != 0);
+    else launch_cg_update(n, scal.p, dp, dAp, dx, dr, dpart, nblk, E.stream());
+    return done(E, V.get(x) && V.get(r) && V.get(partial) && (!zero || V.get(z0)));
+}
+
+int sparsh_op_p_update(sparsh_handle h, int n, double beta, const double *z, double *p)
+{
+    REQUIRE_KRYLOV_OP(h, n);
+    if (!z || !p) return fail(SPARSH_EINVAL, "null array");
+    REQUIRE_READY(h);
+    REQUIRE_SINGLE(h);
+    Engine &E = *h->eng;
+    OpVecs V(E);
+    OpScal s;
+    s.set(S_BETA, beta);
+    DBuf scal(E, (size_t)S_COUNT, s.host);
+    double *dp = V.dev(p, op_padded(n));
+    const double *dz = V.dev(z, (size_t)n);
+    if (!scal.p) return fail(SPARSH_ENODEV, "device allocation failed");
+    if (int rc = V.status(); rc != SPARSH_OK) return rc;
+    launch_p_update(n, scal.p, dz, dp, E.stream());
+    return done(E, V.get(p));
+}
+
+int sparsh_op_xp_update(sparsh_handle h, int n, double alpha, double beta, const double *z, double *p, double *x)
+{
+    REQUIRE_KRYLOV_OP(h, n);
+    if (!z || !p || !x || p == x) return fail(SPARSH_EINVAL, "null array");
+    REQUIRE_READY(h);
+    REQUIRE_SINGLE(h);
+    Engine &E = *h->eng;
+    OpVecs V(E);
+    OpScal s;
+    s.set(S_ALPHA, alpha).set(S_BETA, beta);
+    DBuf scal(E, (size_t)S_COUNT, s.host);
+    double *dp = V.dev(p, op_padded(n)), *dx = V.dev(x, op_padded(n));
+    const double *dz = V.dev(z, (size_t)n);
+    if (!scal.p) return fail(SPARSH_ENODEV, "device allocation failed");
+    if (int rc = V.status(); rc != SPARSH_OK) return rc;
+    launch_xp_update(n, scal.p, dz, dp, dx, E.stream());
+    return done(E, V.get(p) && V.get(x));
+}
+
+int sparsh_op_bicg_s(sparsh_handle h, int n, double alpha, const double *r, const double *Ap, double *s)
+{
+    REQUIRE_KRYLOV_OP(h, n);
+    if (!r || !Ap || !s) return fail(SPARSH_EINVAL, "null array");
+    REQUIRE_READY(h);
+    REQUIRE_SINGLE(h);
+    Engine &E = *h->eng;
+    OpVecs V(E);
+    OpScal sc;
+    sc.set(S_ALPHA, alpha);
+    DBuf scal(E, (size_t)S_COUNT, sc.host);
+    double *ds = V.dev(s, op_padded(n));
+    const double *dr = V.dev(r, (size_t)n), *dAp = V.dev(Ap, (size_t)n);
+    if (!scal.p) return fail(SPARSH_ENODEV, "device allocation failed");
+    if (int rc = V.status(); rc != SPARSH_OK) return rc;
+    launch_bicg_s(n, scal.p, dr, dAp, ds, E.stream());
+    return done(E, V.get(s));
+}
+
+int sparsh_op_bicg_xr(sparsh_handle h, int n, double alpha, double omega1, const double *p1, const double *s1, const double *s,
+                      const double *As, const double *r0, double *x, double *r, double *q0, double *q1, int *nblk)
+{
+    REQUIRE_KRYLOV_OP(h, n);
+    if (!p1 || !s1 || !s || !As || !r0 || !x || !r || !q0 || !q1 || !nblk) return fail(SPARSH_EINVAL, "null array");
+    if (x == r || q0 == q1) return fail(SPARSH_EINVAL, "the written vectors must be distinct arrays");
+    REQUIRE_READY(h);
+    REQUIRE_SINGLE(h);
+    Engine &E = *h->eng;
+    OpVecs V(E);
+    OpScal sc;
+    sc.set(S_ALPHA, alpha).set(S_OMEGA1, omega1);
+    DBuf scal(E, (size_t)S_COUNT, sc.host);
+    double *dx = V.dev(x, op_padded(n)), *dr = V.dev(r, op_padded(n)), *dq0 = V.dev(q0, kOpPartials), *dq1 = V.dev(q1, kOpPartials);
+    const double *dp1 = V.dev(p1, (size_t)n), *ds1 = V.dev(s1, (size_t)n), *ds = V.dev(s, (size_t)n), *dAs = V.dev(As, (size_t)n),
+                 *dr0 = V.dev(r0, (size_t)n);
+    if (!scal.p) return fail(SPARSH_ENODEV, "device allocation failed");
+    if (int rc = V.status(); rc != SPARSH_OK) return rc;
+    launch_bicg_xr(n, scal.p, dp1, ds1, ds, dAs, dr0, dx, dr, dq0, dq1, nblk, E.stream());
+    return done(E, V.get(x) && V.get(r) && V.get(q0) && V.get(q1));
+}
+
+int sparsh_op_bicg_p(sparsh_handle h, int n, double beta, double omega1, const double *r, const double *Ap, double *p)
+{
+    REQUIRE_KRYLOV_OP(h, n);
+    if (!r || !Ap || !p) return fail(SPARSH_EINVAL, "null array");
+    REQUIRE_READY(h);
+    REQUIRE_SINGLE(h);
+    Engine &E = *h->eng;
+    OpVecs V(E);
+    OpScal sc;
+    sc.set(S_BETA, beta).set(S_OMEGA1, omega1);
+    DBuf scal(E, (size_t)S_COUNT, sc.host);
+    double *dp = V.dev(p, op_padded(n));
+    const double *dr = V.dev(r, (size_t)n), *dAp = V.dev(Ap, (size_t)n);
+    if (!scal.p) return fail(SPARSH_ENODEV, "device allocation failed");
+    if (int rc = V.status(); rc != SPARSH_OK) return rc;
+    launch_bicg_p(n, scal.p, dr, dAp, dp, E.stream());
+    return done(E, V.get(p));
+}
+
+int sparsh_op_finalize(sparsh_handle h, int code, int mode, const double *p0, int nblk, const double *p1, int nblk1, double *scal,
+                       int slot_a, double *hist, int hist_cap, int it, int *iter_ctr, int repeat)
+{
+    if (!h || !h->eng) return fail(SPARSH_EINVAL, "null handle");
+    if (code < FIN_STORE || code > FIN_FCG_BETA) return fail(SPARSH_EINVAL, "code must be one of the Fin codes 0..10");
+    if (mode < 0 || mode > 2) return fail(SPARSH_EINVAL, "mode must be 0, 1 or 2");
+    if (!scal || !iter_ctr || (mode != 2 && !p0)) return fail(SPARSH_EINVAL, "null array");
+    if (nblk < 1 || (p1 && nblk1 < 1)) return fail(SPARSH_EINVAL, "nblk < 1");
+    if (slot_a < 0 || slot_a >= S_COUNT) return fail(SPARSH_EINVAL, "slot out of range");
+    if (hist && hist_cap < 1) return fail(SPARSH_EINVAL, "hist_cap < 1");
+    if (*iter_ctr < 0) return fail(SPARSH_EINVAL, "the iteration counter must be >= 0");
+    if (repeat < 1 || repeat > 64) return fail(SPARSH_EINVAL, "repeat must be in 1..64");
+    REQUIRE_READY(h);
+    REQUIRE_SINGLE(h);
+    Engine &E = *h->eng;
+    OpVecs V(E);
+    double *dscal = V.dev(scal, (size_t)S_COUNT), *dhist = hist ? V.dev(hist, op_padded(hist_cap)) : nullptr;
+    const double *d0 = mode != 2 ? V.dev(p0, (size_t)nblk) : nullptr, *d1 = (mode != 2 && p1) ? V.dev(p1, (size_t)nblk1) : nullptr;
+    int *dctr = static_cast<int *>(E.dalloc(2 * sizeof(int)));
+    if (int rc = V.status(); rc != SPARSH_OK || !dctr) {
+        E.dfree(dctr);
+        return rc != SPARSH_OK ? rc : fail(SPARSH_ENODEV, "device allocation failed");
+    }
+    bool ok = hipMemcpy(dctr, iter_ctr, sizeof(int), hipMemcpyHostToDevice) == hipSuccess;
+    // (mode 2 reads no partials: its sums are what S_SUM0 / S_SUM1 of the block hold, as after the all-reduce)
+    for (int k = 0; ok && k < repeat; ++k)
+        launch_finalize((Fin)code, d0, d1, nblk, dscal, slot_a, dhist, it, E.stream(), mode, dctr, hist ? hist_cap : 1, p1 ? nblk1 : -1);
+    ok = ok && V.get(scal) && V.get(hist);
+    ok = ok && hipMemcpy(iter_ctr, dctr, sizeof(int), hipMemcpyDeviceToHost) == hipSuccess;
+    E.dfree(dctr);
+    return done(E, ok);
+}
+
+}  // extern "C"

@@ -2213,8 +2213,6 @@ int launch_csr_op(const DevCsr &A, const CsrArgs &a, bool finest, hipStream_t st
 
 // ------------------------------------------------------------------ elementwise
 
-constexpr int kEwGridMax = 2048;  // grid-stride: ~8 workgroups per CU
-
 inline int ew_grid(int n)
 {
     int g = (n + kBlock * 2 - 1) / (kBlock * 2);
@@ -2529,8 +2527,10 @@ __global__ __launch_bounds__(kFinBlock) void finalize_kernel(int code, int mode,
     }
     // residual-history slot: explicit (eager launches) or a device-side counter (graph replays,
     // where kernel arguments are frozen)
+    // (only a code that stores a residual takes a slot: the others leave the counter alone even when they are handed a history)
+    const bool stores = code == FIN_SQRT || code == FIN_CG_BETA || code == FIN_BICG_BETA || code == FIN_PCG_BETA_RES;
     int hslot = it;
-    if (hist && it < 0) hslot = (*iter_ctr)++;
+    if (hist && stores && it < 0) hslot = (*iter_ctr)++;
     if (hslot >= hist_cap) hslot = hist_cap - 1;
     switch (code) {
     case FIN_STORE: scal[slot_a] = s0; break;

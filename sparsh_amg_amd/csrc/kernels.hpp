@@ -136,6 +136,7 @@ struct KernelConfig {
 enum CsrFamily : int { FAM_CSR_BLOCK = 0, FAM_CSR_WAVE = 1, FAM_SELL = 2, FAM_SDIA = 3, FAM_SDIA_TAB = 4, FAM_CSR_ROWLANE = 5, FAM_CSR_ROWLANE16 = 6 };
 
 constexpr int kBlock = 256;       // threads per workgroup (4 waves)
+constexpr int kEwGridMax = 2048;  // workgroups of an elementwise launch (grid-stride: ~8 per CU) = the most partial sums it writes
 constexpr int kStreamNnz = 2048;  // products staged in LDS per workgroup (16 KiB)
 constexpr int kWaveNnz = 512;     // products staged in LDS per wave (4 KiB) in the wave-granular kernel
 constexpr int kSdRecInts = 48;        // 192 B per slice record
@@ -324,7 +325,8 @@ enum Fin : int {
     FIN_PCG_BETA_RES = 9, // FIN_PCG_BETA on sum0 (z.r) and res = sqrt(sum1) (r.r) ; hist
     FIN_FCG_BETA = 10     // flexible CG: rz = sum0 (z.r) ; beta = -sum1 (z.Ap) / pAp
 };
-// it >= 0: residual-history slot; it < 0: take the slot from the device counter *iter_ctr (graph replays).
+// it >= 0: residual-history slot; it < 0: take the slot from the device counter *iter_ctr (graph replays), which only the codes
+// that store a residual advance.  The slot is clamped to hist_cap - 1.
 // mode 0: reduce the partials and apply `code` (single GPU); mode 1: reduce only, local sums to
 // scal[S_SUM0], scal[S_SUM1] (then all-reduced across ranks); mode 2: apply `code` to those sums
 void launch_finalize(Fin code, const double *partial0, const double *partial1, int nblk, double *scal, int slot_a,
