@@ -84,9 +84,9 @@ struct DBuf {
     if ((h)->eng->distributed()) return fail(SPARSH_ESTATE, "operator-level entry points are single-GPU test hooks (host vectors carry no halo)")
 
 // checked before REQUIRE_READY: a combination that no setup can make valid is a bad argument, with or without a device
-#define REQUIRE_SMOOTHER_FITS(h, method)                                                                                        \
-    if ((h) && (h)->eng && (method) == SPARSH_PCG && (h)->eng->sor_on() && (h)->eng->sor_order() != SPARSH_SOR_SYMMETRIC) \
-    return fail(SPARSH_EINVAL, "SPARSH_PCG needs a symmetric preconditioner: the SOR smoother must use SPARSH_SOR_SYMMETRIC")
+// (SPARSH_PCG alone: SPARSH_FCG is refused by the solve itself, with its other refusals)
+#define REQUIRE_SMOOTHER_FITS(h, method) \
+    if (const char *why_ = (h) && (h)->eng && (method) == SPARSH_PCG ? (h)->eng->sor_refusal(method) : nullptr) return fail(SPARSH_EINVAL, why_)
 
 // likewise: GMRES on a handle that a multi-GPU transport has been installed on
 #define REQUIRE_GMRES_FITS(h, method)                                                                                              \

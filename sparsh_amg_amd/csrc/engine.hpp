@@ -312,11 +312,13 @@ public:
                   double *seconds);
     int amg_solve_dev(const double *b_dev, double *x_dev, int iterations, double *hist, int hist_cap, int *ncycles);
 
-    // stepwise CG / AMG-PCG (bench: time exactly k iterations)
+    // stepwise CG / AMG-PCG (bench: time exactly k iterations; engine_krylov.cpp, as everything of the single-vector Krylov methods)
     int pcg_init(const double *b_dev, double *x_dev, bool precond);
     int pcg_steps(int nsteps, int *done);
     int krylov_hist(double *hist, int hist_cap);  // copies the residual history, returns iterations so far
     double krylov_residual() const { return ks_.r1; }
+    // why `method` cannot run under the SOR order selected now (nullptr: it can); needs no device
+    const char *sor_refusal(int method) const;
 
     // operator-level (device pointers)
     void op_spmv(int l, const double *x, double *y);
@@ -535,7 +537,6 @@ private:
     long level_visits_for(int l, int stride) const;
     long cycle_visits_for(int stride) const;
     bool kc_scratch();  // partial sums and scalar blocks of the K step (no-op once held)
-    int fcg(const double *b, double *x, int max_iters, double *hist, int hist_cap, int *iters);
     // refusals of a setup under SPARSH_NULLSPACE_CONSTANT and the two defects of level 0: SPARSH_OK or SPARSH_EINVAL with the reason
     int nullspace_check(const sparsh_params &p, bool with_defects);
     // the operator the coarsest-level solver factors: A_L, or A_L with the pinned row and column under a constant null space
@@ -557,8 +558,7 @@ private:
     double cheby_ratio_ = kChebyDefaultRatio;
     int cheby_steps_ = kChebyDefaultSteps;
     int cheby_flip_ = 0;  // cheby_bench_step
-    void adopt_sweeps();
-    int pcg_smoother_check();  // SPARSH_PCG under the current smoother: symmetric SOR order, layouts built  // prm_.sweeps = the Jacobi sweep count this handle's smoother selection asks for
+    void adopt_sweeps();  // prm_.sweeps = the Jacobi sweep count this handle's smoother selection asks for
     int smoother_ = SPARSH_SMOOTH_JACOBI;
     int sm_sweeps_ = 0;       // sweeps of sparsh_set_smoother (0: the default)
     int sor_order_ = SPARSH_SOR_FORWARD;
@@ -570,11 +570,26 @@ private:
     // V(nu,nu) cycle on the float hierarchy from a zero guess: z64 = V32(r64), partial sums of z.r
     void vcycle_f32(const double *r64, double *z64, double *partial, int *nblk);
     void f32_apply(int l, CsrOp op, const float *b, const float *x, float *y);  // the level's sweep / residual launch (sdia or CSR mirror)
+    // ---- the single-vector Krylov methods (engine_krylov.cpp), solve_dev's cases.  What they share:
+    int krylov_prepare(int method);  // the method's refusals, then smoother_prepare and cycle_prepare when it applies M; SPARSH_* code
+    // b and x under a constant null space (b then points at the projected copy), x staged in `stage` on a partitioned handle
+    // (nullptr: a method that does not run there); returns the x to take the first residual from
+    const double *krylov_start(const double *&b, double *x, double *stage);
+    double residual_norm(const double *r, int rr_slot = -1);  // ||r|| read back (S_RES); r.r also stored in rr_slot when >= 0
+    bool read_due(int count, bool last) const;                // the host reads the residual after iteration `count`
+    bool read_residual(int slot, int shown, double &res);     // res = hist_dev_[slot], the print_solve line; false: NaN
+    void copy_hist(int count, double *hist, int hist_cap);    // the first min(count, hist_cap) residuals to the host (stream idle)
+    // projection under a null space, synchronise, history and *iters out; returns the fault if there is one, else rc
+    int krylov_finish(double *x, int count, int rc, double *hist, int hist_cap, int *iters);
+    // while (res > tol): iteration cap, fault, body(slot) = the launches of one iteration, which leave its residual norm in
+    // hist_dev_[slot], the read schedule; `shown`: what print_solve calls the first iteration.  SPARSH_OK / ENOCONV / ENUMERIC
+    template <class Body> int krylov_loop(double res, int max_iters, int shown, int &count, Body body);
     void pcg_body(bool precond, int slot);
     bool capture_graph(bool precond);
     void drop_graph();
     int pcg(const double *b, double *x, int max_iters, double *hist, int hist_cap, int *iters, bool precond);
     int bicg(const double *b, double *x, int max_iters, double *hist, int hist_cap, int *iters, bool precond);
+    int fcg(const double *b, double *x, int max_iters, double *hist, int hist_cap, int *iters);
     int gmres(const double *b, double *x, int max_iters, double *hist, int hist_cap, int *iters, bool precond);
     int gmres_reserve();   // basis, partial sums and device state of the current restart length (no-op once held)
     void gmres_release();
