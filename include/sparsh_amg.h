@@ -40,6 +40,8 @@ extern "C" {
 #define SPARSH_PGMRES 6 /* restarted GMRES, right-preconditioned with one V-cycle from a zero guess: the z = M v of SPARSH_PBICG */
 #define SPARSH_FCG 7    /* flexible preconditioned CG (Notay's FCG(1)): the Krylov method that takes the K-cycle; see "W- and K-cycles" below */
 #define SPARSH_BCG 8    /* block conjugate gradients: sparsh_solve_multi / sparsh_solve_multi_dev only; see "block CG" below */
+#define SPARSH_MBICG 10 /* block BiCGStab (unsymmetric systems): sparsh_solve_multi / sparsh_solve_multi_dev only; see "block BiCGStab" below.
+                         * 9 is no method and stays SPARSH_EINVAL everywhere */
 
 /* Smoother of the V-cycle (sparsh_set_smoother). */
 #define SPARSH_SMOOTH_JACOBI 0  /* weighted Jacobi, parallel::jacobi_smoother (default) */
@@ -705,7 +707,7 @@ int sparsh_op_project_dev(sparsh_handle h, int n, double *x_dev, const double *r
  * (row sums in stored order, the epilogues of the Jacobi cycle, the recurrences of SPARSH_PCG); the cycle is the plain Jacobi
  * V(nu,nu) cycle from a zero guess with nothing fused, so column c follows sparsh_solve(SPARSH_PCG) of the same right-hand side up to
  * the last bits of the reductions and of the box-grid kernels' fused launches.
- * method: SPARSH_PCG here (SPARSH_BCG: the coupled loop described further below).  X: initial guesses in, solutions out.  hist[c * hist_cap + k] = column c's residual after iteration
+ * method: SPARSH_PCG here (SPARSH_BCG: the coupled loop described further below; SPARSH_MBICG: block BiCGStab, further below).  X: initial guesses in, solutions out.  hist[c * hist_cap + k] = column c's residual after iteration
  * k + 1; entries from iters[c] on are left untouched.  iters / status: nrhs ints each.  All scalars stay on the device, one set per
  * column; a column whose residual is <= tol (at the start or after an iteration) is frozen there and then: its x and r are never
  * written again (predicated writes) and its iteration count stands, so it ends with the iterate a single solve with check_every = 1
@@ -787,6 +789,52 @@ int sparsh_op_bcg_small(sparsh_handle h, int W, int k, const double *G, const do
 int sparsh_op_bcg_update(sparsh_handle h, int n, int k, const double *X, const double *R, const double *P, const double *Q,
                          const double *alpha, double *Xo, double *Ro, double *norms);
 int sparsh_op_bcg_dir(sparsh_handle h, int n, int k, const double *Z, const double *P, const double *beta, double *Po);
+
+/* ---- block BiCGStab: up to SPARSH_MAX_RHS right-hand sides of an unsymmetric system ----
+ * sparsh_solve_multi / sparsh_solve_multi_dev with method SPARSH_MBICG.  Block PCG, block CG and the eigensolvers need a symmetric
+ * operator; this is the block method for a general one.  Arguments, the column-major layout, the hist / iters / status conventions,
+ * the return codes, the refusals and the memory rules are those of SPARSH_PCG through those calls; SPARSH_PCG and SPARSH_BCG keep
+ * their bits, launches and bytes.  sparsh_solve, sparsh_solve_dev and sparsh_krylov_init_dev refuse the method (SPARSH_EINVAL, with
+ * or without a device), and SPARSH_PBICG stays refused by the block calls.
+ * Per column the arithmetic is that of sparsh_solve(SPARSH_PBICG), parentheses included; all columns go through two block V-cycles
+ * and two block SpMVs per iteration, so the hierarchy is read twice per iteration whatever nrhs:
+ *   R0 = B - A X ; R = R0 ; P = R0 ; res_c = ||R0_c|| ; then per iteration
+ *   P1 = M P ; AP = A P1 ; alpha1_c = (R.R0)_c, alpha_c = alpha1_c / (AP.R0)_c ; S = R - alpha_c AP ; S1 = M S ; AS = A S1 ;
+ *   omega_c = (AS.S)_c / (AS.AS)_c (0 if (AS.AS)_c = 0) ; X = (X + alpha_c P1) + omega_c S1 ; R = S - omega_c AS ;
+ *   beta_c = (R.R0)_c / alpha1_c * (alpha_c / omega_c) ; res_c = ||R_c|| ; P = R + beta_c (P - omega_c AP).
+ * Every scalar stays on the device, one set per column.  A column whose residual is <= tol (at the start or after an iteration), and
+ * a column with a NaN residual (status SPARSH_ENUMERIC), is frozen there and then, as in block PCG: its X, R, P, S and scalars are
+ * never written again (predicated stores), it keeps the x it had bit for bit, and it rides through the cycles and SpMVs of the
+ * others.  Columns never interact.  A zero denominator is not trapped: the NaN or inf it gives turns the next residual into
+ * SPARSH_ENUMERIC, as in the single loop.  Reductions: one partial sum per column and workgroup, added in a fixed order; no atomics.
+ * Memory: X, R, P, AP are the block PCG's; R0, S, AS, P1 (n * width doubles each) and the per-column state are the solver's own,
+ * reserved at the first SPARSH_MBICG call for a width and released with the block vectors.  sparsh_mbicg_info: the iterations of the
+ * last such solve (the largest count of a column) and those bytes, never counted by sparsh_multi_info; zeros before the first.  Any
+ * pointer may be NULL. */
+int sparsh_mbicg_info(sparsh_handle h, int *iterations, long *bytes);
+/* Operator-level hooks of block BiCGStab's kernels: one launch each through the loop's own launcher, on host blocks that are
+ * column-major n x nrhs (ld = n) with any n > 0; a ready handle lends its stream only.  The device runs them at the width
+ * W = nrhs rounded up to 2, 4 or 8.  frozen: nrhs ints, nonzero = the column must come back untouched; alpha, omega, beta: nrhs
+ * coefficients.  Written blocks (S; X and R; P) are in/out: a frozen column keeps its input.  The padding columns of a written block
+ * hold a sentinel before the launch and SPARSH_ENUMERIC is returned unless they still do after it.
+ * dot2: part0[c * g + w] / part1[c * g + w] = workgroup w's share of a_c . b_c / c_c . d_c, c < W, *nblk = g (the blocks may be one
+ * another); the part arrays hold SPARSH_MAX_RHS * SPARSH_MBICG_PARTIALS doubles.  bicg_xr likewise: shares of R_c . R0_c and R_c . R_c.
+ * mbicg_finalize: code 0 INIT, 1 ALPHA, 2 OMEGA, 3 BETA_RES on part0 (W * n0 doubles, column c's n0 partials at c * n0) and part1 (may
+ * be NULL); scal: SPARSH_MBICG_SCALARS x SPARSH_MAX_RHS, slot-major, in/out, slots in the order alpha1, apr0, alpha, ass, asas, omega1,
+ * beta, rr0, res; frozen / iters / status: nrhs ints each, in/out (status 1: frozen on a NaN); hist: nrhs x hist_cap, in/out. */
+#define SPARSH_MBICG_SCALARS 9
+#define SPARSH_MBICG_PARTIALS 2048
+int sparsh_op_dot2_multi(sparsh_handle h, int n, int nrhs, const double *a, const double *b, const double *c, const double *d, double *part0,
+                         double *part1, int *nblk);
+int sparsh_op_bicg_s_multi(sparsh_handle h, int n, int nrhs, const int *frozen, const double *alpha, const double *R, const double *AP,
+                           double *S);
+int sparsh_op_bicg_xr_multi(sparsh_handle h, int n, int nrhs, const int *frozen, const double *alpha, const double *omega, const double *P1,
+                            const double *S1, const double *S, const double *AS, const double *R0, double *X, double *R, double *part0,
+                            double *part1, int *nblk);
+int sparsh_op_bicg_p_multi(sparsh_handle h, int n, int nrhs, const int *frozen, const double *beta, const double *omega, const double *R,
+                           const double *AP, double *P);
+int sparsh_op_mbicg_finalize(sparsh_handle h, int code, int nrhs, const double *part0, int n0, const double *part1, int n1, double *scal,
+                             int *frozen, int *iters, int *status, double tol, double *hist, int hist_cap, int it);
 
 /* ---- the lowest eigenpairs of the SPD level-0 operator by LOBPCG on the block path ----
  * nev <= SPARSH_MAX_RHS eigenpairs A x = lambda x with the smallest lambda, the block V-cycle as preconditioner.  The standard

@@ -29,6 +29,13 @@ METHODS = {"amg": SPARSH_AMG, "cg": SPARSH_CG, "pcg": SPARSH_PCG, "bicg": SPARSH
            "gmres": SPARSH_GMRES, "pgmres": SPARSH_PGMRES}
 SPARSH_BCG = 8
 BLOCK_METHODS = {"bcg": SPARSH_BCG}  # methods of solve_multi only: the columns of a block share one search space
+SPARSH_MBICG = 10
+# block BiCGStab, a method of solve_multi only as well; the columns are frozen one by one as in "pcg" (BLOCK_METHODS holds the
+# coupled methods, whose columns share one search space)
+UNSYMMETRIC_BLOCK_METHODS = {"mbicg": SPARSH_MBICG}
+SPARSH_MBICG_SCALARS, SPARSH_MBICG_PARTIALS = 9, 2048
+MBICG_SLOTS = ("ALPHA1", "APR0", "ALPHA", "ASS", "ASAS", "OMEGA1", "BETA", "RR0", "RES")
+MBICG_FIN = {"init": 0, "alpha": 1, "omega": 2, "beta_res": 3}
 FLEXIBLE_METHODS = {"fcg": SPARSH_FCG}  # methods whose preconditioner may change between applications (the K-cycle)
 SPARSH_CYCLE_V, SPARSH_CYCLE_W, SPARSH_CYCLE_K = 0, 1, 2
 CYCLES = {"v": SPARSH_CYCLE_V, "w": SPARSH_CYCLE_W, "k": SPARSH_CYCLE_K}
@@ -46,13 +53,18 @@ SPARSH_MAX_RHS = 8
 
 
 
+# every method name: the single-vector methods, the flexible one, and the two kinds of solve_multi only
+_METHOD_CODES = {**METHODS, **FLEXIBLE_METHODS, **BLOCK_METHODS, **UNSYMMETRIC_BLOCK_METHODS}
+
+
 def _method(method):
-    """method code of a name ("pcg", "fcg", ...) or the code itself"""
-    if isinstance(method, str):
-        if method in BLOCK_METHODS:
-            return BLOCK_METHODS[method]
-        return METHODS[method] if method in METHODS else FLEXIBLE_METHODS[method]
-    return method
+    """method code of a name ("pcg", "fcg", "mbicg", ...) or the code itself"""
+    return _METHOD_CODES[method] if isinstance(method, str) else method
+
+
+def multi_width(nrhs):
+    """width of the interleaved device block behind nrhs columns: 2, 4 or 8"""
+    return 2 if nrhs <= 2 else (4 if nrhs <= 4 else 8)
 
 
 c_int_p = C.POINTER(C.c_int)
@@ -257,6 +269,13 @@ def _load():
         "sparsh_op_bcg_small": (C.c_int, [H, C.c_int, C.c_int, c_dbl_p, c_dbl_p, C.c_double, c_dbl_p, c_int_p]),
         "sparsh_op_bcg_update": (C.c_int, [H, C.c_int, C.c_int] + [c_dbl_p] * 8),
         "sparsh_op_bcg_dir": (C.c_int, [H, C.c_int, C.c_int] + [c_dbl_p] * 4),
+        "sparsh_mbicg_info": (C.c_int, [H, c_int_p, C.POINTER(C.c_long)]),
+        "sparsh_op_dot2_multi": (C.c_int, [H, C.c_int, C.c_int] + [c_dbl_p] * 6 + [c_int_p]),
+        "sparsh_op_bicg_s_multi": (C.c_int, [H, C.c_int, C.c_int, c_int_p] + [c_dbl_p] * 4),
+        "sparsh_op_bicg_xr_multi": (C.c_int, [H, C.c_int, C.c_int, c_int_p] + [c_dbl_p] * 11 + [c_int_p]),
+        "sparsh_op_bicg_p_multi": (C.c_int, [H, C.c_int, C.c_int, c_int_p] + [c_dbl_p] * 5),
+        "sparsh_op_mbicg_finalize": (C.c_int, [H, C.c_int, C.c_int, c_dbl_p, C.c_int, c_dbl_p, C.c_int, c_dbl_p, c_int_p, c_int_p, c_int_p,
+                                               C.c_double, c_dbl_p, C.c_int, C.c_int]),
         "sparsh_op_spmv_dot_multi": (C.c_int, [H, C.c_int, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p]),
         "sparsh_op_residual_multi": (C.c_int, [H, C.c_int, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p]),
         "sparsh_op_jacobi_multi": (C.c_int, [H, C.c_int, C.c_int, c_dbl_p, c_dbl_p, C.c_int, C.c_int]),
@@ -1335,7 +1354,7 @@ class sp_matrix_mg:
 
     def solve_multi(self, method, B, X, hist_cap=8192, allow=()):
         """Block AMG-PCG ("pcg") or block CG ("bcg": the columns share one search space, one iteration count for all; bcg_info()
-        has the ranks): X (n, nrhs) holds the initial guesses on entry and the solutions on return.  Returns (histories, iters,
+        has the ranks) or block BiCGStab ("mbicg": unsymmetric systems, per column the arithmetic of "pbicg"): X (n, nrhs) holds the initial guesses on entry and the solutions on return.  Returns (histories, iters,
         status, rc): histories[c] = column c's residual after every iteration it ran; SPARSH_ENOCONV / SPARSH_ENUMERIC are handed
         back in rc and per column in status, other codes raise."""
         Bf, Xf = self._block(B), self._block(X)
@@ -1399,6 +1418,87 @@ class sp_matrix_mg:
         Po = Pf if in_place else np.zeros_like(Pf, order="F")
         _check(lib.sparsh_op_bcg_dir(self._h, n, k, _dp(Zf), _dp(Pf), _dp(be), _dp(Po)))
         return Po
+
+    def mbicg_info(self):
+        """The last solve_multi("mbicg", ...): its iterations (the largest count of a column) and the device bytes of the solver's
+        own blocks (zeros before the first such solve)."""
+        it, b = C.c_int(), C.c_long()
+        _check(lib.sparsh_mbicg_info(self._h, C.byref(it), C.byref(b)))
+        return dict(iterations=it.value, bytes=b.value)
+
+    # the hooks of block BiCGStab's kernels: blocks of shape (n, nrhs), n free of the handle's matrix; `frozen` marks the columns a
+    # launch must leave alone and the coefficients are one per column
+    @staticmethod
+    def _mb_cols(nrhs, frozen, *coefs):
+        fr = np.zeros(nrhs, dtype=np.int32) if frozen is None else np.ascontiguousarray(frozen, dtype=np.int32)
+        cs = [np.ascontiguousarray(np.broadcast_to(np.asarray(c, dtype=np.float64), (nrhs,))) for c in coefs]
+        if len(fr) != nrhs:
+            raise ValueError("one frozen flag per column")
+        return (fr, *cs)
+
+    def op_dot2_multi(self, a, b, c, d):
+        """(part0, part1), each of shape (W, nblk): every workgroup's shares of a_c . b_c and c_c . d_c, W = nrhs rounded up to 2, 4
+        or 8 (the padding columns' shares are zeros).  Arrays that are the same object are one device block."""
+        blocks = {}
+        fa, fb, fc, fd = (blocks.setdefault(id(v), self._block(v)) for v in (a, b, c, d))
+        n, k = fa.shape
+        p0, p1 = np.zeros(SPARSH_MAX_RHS * SPARSH_MBICG_PARTIALS), np.zeros(SPARSH_MAX_RHS * SPARSH_MBICG_PARTIALS)
+        nblk = C.c_int()
+        _check(lib.sparsh_op_dot2_multi(self._h, n, k, _dp(fa), _dp(fb), _dp(fc), _dp(fd), _dp(p0), _dp(p1), C.byref(nblk)))
+        W, g = multi_width(k), nblk.value
+        return p0[: W * g].reshape(W, g).copy(), p1[: W * g].reshape(W, g).copy()
+
+    def op_bicg_s_multi(self, alpha, R, AP, S, frozen=None):
+        """S = R - alpha_c AP on the columns that are not frozen; the others keep the S given."""
+        Rf, Af, Sf = self._block(R), self._block(AP), self._block(S)
+        n, k = Sf.shape
+        fr, al = self._mb_cols(k, frozen, alpha)
+        _check(lib.sparsh_op_bicg_s_multi(self._h, n, k, _ip(fr), _dp(al), _dp(Rf), _dp(Af), _dp(Sf)))
+        return Sf
+
+    def op_bicg_xr_multi(self, alpha, omega, P1, S1, S, AS, R0, X, R, frozen=None):
+        """(X, R, part0, part1): X = (X + alpha_c P1) + omega_c S1 and R = S - omega_c AS on the columns that are not frozen, and every
+        workgroup's shares of R_c . R0_c and R_c . R_c, of shape (W, nblk)."""
+        P1f, S1f, Sf, ASf, R0f, Xf, Rf = (self._block(v) for v in (P1, S1, S, AS, R0, X, R))
+        n, k = Xf.shape
+        fr, al, om = self._mb_cols(k, frozen, alpha, omega)
+        p0, p1 = np.zeros(SPARSH_MAX_RHS * SPARSH_MBICG_PARTIALS), np.zeros(SPARSH_MAX_RHS * SPARSH_MBICG_PARTIALS)
+        nblk = C.c_int()
+        _check(lib.sparsh_op_bicg_xr_multi(self._h, n, k, _ip(fr), _dp(al), _dp(om), _dp(P1f), _dp(S1f), _dp(Sf), _dp(ASf), _dp(R0f), _dp(Xf),
+                                           _dp(Rf), _dp(p0), _dp(p1), C.byref(nblk)))
+        W, g = multi_width(k), nblk.value
+        return Xf, Rf, p0[: W * g].reshape(W, g).copy(), p1[: W * g].reshape(W, g).copy()
+
+    def op_bicg_p_multi(self, beta, omega, R, AP, P, frozen=None):
+        """P = R + beta_c (P - omega_c AP) on the columns that are not frozen."""
+        Rf, Af, Pf = self._block(R), self._block(AP), self._block(P)
+        n, k = Pf.shape
+        fr, be, om = self._mb_cols(k, frozen, beta, omega)
+        _check(lib.sparsh_op_bicg_p_multi(self._h, n, k, _ip(fr), _dp(be), _dp(om), _dp(Rf), _dp(Af), _dp(Pf)))
+        return Pf
+
+    def op_mbicg_finalize(self, code, nrhs, part0, part1, state, tol, hist=None, it=0):
+        """One finalise launch of block BiCGStab.  code: "init", "alpha", "omega" or "beta_res"; part0 / part1 (None: absent): arrays
+        of shape (nrhs, n0) / (nrhs, n1), the partial sums of every column; state: dict(scal (SPARSH_MBICG_SCALARS, nrhs), frozen,
+        iters, status (nrhs,)); hist: (nrhs, hist_cap) or None.  Returns (state, hist), both new."""
+        W = multi_width(nrhs)
+
+        def padded(p):
+            p = np.asarray(p, dtype=np.float64)
+            out = np.zeros((W, p.shape[1]))
+            out[:nrhs] = p
+            return out
+
+        q0 = padded(part0)
+        q1 = None if part1 is None else padded(part1)
+        scal = np.zeros((SPARSH_MBICG_SCALARS, SPARSH_MAX_RHS))
+        scal[:, :nrhs] = state["scal"]
+        fr, its, st = (np.array(state[k], dtype=np.int32) for k in ("frozen", "iters", "status"))
+        h = None if hist is None else np.array(hist, dtype=np.float64, order="C")
+        _check(lib.sparsh_op_mbicg_finalize(self._h, MBICG_FIN[code] if isinstance(code, str) else int(code), nrhs, _dp(q0), q0.shape[1],
+                                            None if q1 is None else _dp(q1), 0 if q1 is None else q1.shape[1], _dp(scal), _ip(fr), _ip(its),
+                                            _ip(st), float(tol), None if h is None else _dp(h), 0 if h is None else h.shape[1], int(it)))
+        return dict(scal=scal[:, :nrhs].copy(), frozen=fr, iters=its, status=st), h
 
     def op_spmv_dot_multi(self, level, X):
         """(A_l X, [x_c . (A_l x_c)]) through the block launch PCG uses for A p and p.Ap."""

@@ -99,6 +99,10 @@ struct DBuf {
 #define REQUIRE_CYCLE_FITS(h, method) \
     if ((h) && (h)->eng && (h)->eng->cycle_check(method) != SPARSH_OK) return fail(SPARSH_EINVAL, (h)->eng->error)
 
+// SPARSH_MBICG is a method of the block entry points alone: a bad argument with or without a device
+#define REQUIRE_NOT_BLOCK_ONLY(method) \
+    if ((method) == SPARSH_MBICG) return fail(SPARSH_EINVAL, "SPARSH_MBICG is a method of sparsh_solve_multi / sparsh_solve_multi_dev only")
+
 #define REQUIRE_HOST(h)                                               \
     if (!(h) || !(h)->eng) return fail(SPARSH_EINVAL, "null handle"); \
     if (!(h)->eng->host_ready()) return fail(SPARSH_ESTATE, "sparsh_setup / sparsh_setup_host has not been called (or failed)")
@@ -861,6 +865,7 @@ int sparsh_vcycle_dev(sparsh_handle h, const double *b_dev, double *x_dev, int i
 
 int sparsh_solve(sparsh_handle h, int method, const double *b, double *x, double *hist, int hist_cap, int *iters)
 {
+    REQUIRE_NOT_BLOCK_ONLY(method);
     REQUIRE_SMOOTHER_FITS(h, method);
     REQUIRE_CYCLE_FITS(h, method);
     REQUIRE_GMRES_FITS(h, method);
@@ -878,6 +883,7 @@ int sparsh_solve(sparsh_handle h, int method, const double *b, double *x, double
 int sparsh_solve_dev(sparsh_handle h, int method, const double *b_dev, double *x_dev, int max_iters, double *hist, int hist_cap,
                      int *iters, double *seconds)
 {
+    REQUIRE_NOT_BLOCK_ONLY(method);
     REQUIRE_SMOOTHER_FITS(h, method);
     REQUIRE_CYCLE_FITS(h, method);
     REQUIRE_GMRES_FITS(h, method);
@@ -1179,6 +1185,7 @@ int sparsh_dist_deep_op_get(sparsh_handle h, int *rowptr, int *col, double *val,
 
 int sparsh_krylov_init_dev(sparsh_handle h, int method, const double *b_dev, double *x_dev)
 {
+    REQUIRE_NOT_BLOCK_ONLY(method);
     REQUIRE_SMOOTHER_FITS(h, method);
     REQUIRE_CYCLE_FITS(h, method);
     REQUIRE_READY(h);
@@ -2076,18 +2083,34 @@ int sparsh_profile_read(sparsh_handle h, double *out4)
 #define REQUIRE_MULTI_FITS(h) \
     if (const char *why_ = (h)->eng->multi_refusal()) return fail(SPARSH_EINVAL, why_)
 
+}  // extern "C"
+
+namespace {
+
+int block_solve(Engine &E, int method, int nrhs, const double *B, long ldb, double *X, long ldx, int max_iters, double *hist, int hist_cap,
+                int *iters, int *status, double *seconds)
+{
+    if (method == SPARSH_BCG) return E.solve_bcg_dev(nrhs, B, ldb, X, ldx, max_iters, hist, hist_cap, iters, status, seconds);
+    if (method == SPARSH_MBICG) return E.solve_mbicg_dev(nrhs, B, ldb, X, ldx, max_iters, hist, hist_cap, iters, status, seconds);
+    return E.solve_multi_dev(nrhs, B, ldb, X, ldx, max_iters, hist, hist_cap, iters, status, seconds);
+}
+
+}  // namespace
+
+extern "C" {
+
 int sparsh_solve_multi_dev(sparsh_handle h, int method, int nrhs, const double *B_dev, long ldb, double *X_dev, long ldx, int max_iters,
                            double *hist, int hist_cap, int *iters, int *status, double *seconds)
 {
     REQUIRE_MULTI_ARGS(h, nrhs);
-    if (method != SPARSH_PCG && method != SPARSH_BCG) return fail(SPARSH_EINVAL, "block solves take SPARSH_PCG or SPARSH_BCG only");
+    if (method != SPARSH_PCG && method != SPARSH_BCG && method != SPARSH_MBICG)
+        return fail(SPARSH_EINVAL, "block solves take SPARSH_PCG, SPARSH_BCG or SPARSH_MBICG only");
     if (!B_dev || !X_dev || !iters || !status || (hist_cap > 0 && !hist)) return fail(SPARSH_EINVAL, "NULL array");
     if (hist_cap < 0) return fail(SPARSH_EINVAL, "hist_cap < 0");
     if (ldb < h->eng->n0() || ldx < h->eng->n0()) return fail(SPARSH_EINVAL, "ldb and ldx must be at least the number of rows");
     REQUIRE_MULTI_FITS(h);
     REQUIRE_READY(h);
-    int rc = method == SPARSH_BCG ? h->eng->solve_bcg_dev(nrhs, B_dev, ldb, X_dev, ldx, max_iters, hist, hist_cap, iters, status, seconds)
-                                  : h->eng->solve_multi_dev(nrhs, B_dev, ldb, X_dev, ldx, max_iters, hist, hist_cap, iters, status, seconds);
+    int rc = block_solve(*h->eng, method, nrhs, B_dev, ldb, X_dev, ldx, max_iters, hist, hist_cap, iters, status, seconds);
     if (rc != SPARSH_OK) return fail(rc, h->eng->error);
     return rc;
 }
@@ -2096,7 +2119,8 @@ int sparsh_solve_multi(sparsh_handle h, int method, int nrhs, const double *B, l
                        int *iters, int *status)
 {
     REQUIRE_MULTI_ARGS(h, nrhs);
-    if (method != SPARSH_PCG && method != SPARSH_BCG) return fail(SPARSH_EINVAL, "block solves take SPARSH_PCG or SPARSH_BCG only");
+    if (method != SPARSH_PCG && method != SPARSH_BCG && method != SPARSH_MBICG)
+        return fail(SPARSH_EINVAL, "block solves take SPARSH_PCG, SPARSH_BCG or SPARSH_MBICG only");
     if (!B || !X || !iters || !status || (hist_cap > 0 && !hist)) return fail(SPARSH_EINVAL, "NULL array");
     if (hist_cap < 0) return fail(SPARSH_EINVAL, "hist_cap < 0");
     if (ldb < h->eng->n0() || ldx < h->eng->n0()) return fail(SPARSH_EINVAL, "ldb and ldx must be at least the number of rows");
@@ -2111,8 +2135,7 @@ int sparsh_solve_multi(sparsh_handle h, int method, int nrhs, const double *B, l
         (void)hipMemcpy(db.p + (size_t)c * n, B + (size_t)c * ldb, n * 8, hipMemcpyHostToDevice);
         (void)hipMemcpy(dx.p + (size_t)c * n, X + (size_t)c * ldx, n * 8, hipMemcpyHostToDevice);
     }
-    int rc = method == SPARSH_BCG ? E.solve_bcg_dev(nrhs, db.p, (long)n, dx.p, (long)n, 0, hist, hist_cap, iters, status, nullptr)
-                                  : E.solve_multi_dev(nrhs, db.p, (long)n, dx.p, (long)n, 0, hist, hist_cap, iters, status, nullptr);
+    int rc = block_solve(E, method, nrhs, db.p, (long)n, dx.p, (long)n, 0, hist, hist_cap, iters, status, nullptr);
     (void)hipStreamSynchronize(E.stream());
     for (int c = 0; c < nrhs; ++c) (void)hipMemcpy(X + (size_t)c * ldx, dx.p + (size_t)c * n, n * 8, hipMemcpyDeviceToHost);
     if (rc != SPARSH_OK) return fail(rc, E.error);
@@ -3269,6 +3292,233 @@ int sparsh_op_finalize(sparsh_handle h, int code, int mode, const double *p0, in
     ok = ok && hipMemcpy(iter_ctr, dctr, sizeof(int), hipMemcpyDeviceToHost) == hipSuccess;
     E.dfree(dctr);
     return done(E, ok);
+}
+
+}  // extern "C"
+
+// ---- block BiCGStab (engine_mbicg.cpp, mbicg_kernels.hip): its info call and the operator-level hooks of its kernels.  A hook is one
+// launch through the launcher the loop uses, on device blocks of the call's own; the handle lends its stream and allocator.
+namespace {
+
+static_assert(SPARSH_MBICG_SCALARS == MB_COUNT, "sparsh_amg.h: SPARSH_MBICG_SCALARS is the number of per-column scalar slots");
+static_assert(SPARSH_MBICG_PARTIALS == kMultiGridMax, "sparsh_amg.h: SPARSH_MBICG_PARTIALS is the cap of the block kernels' grid");
+
+// what the padding columns of a block a hook's launch may write hold before the launch: they must come back with these bits
+constexpr double kMbicgPadding = -7.25e300;
+
+// host blocks (column-major, n x nrhs) as interleaved device blocks of width W.  A host array given twice is one device block; the
+// written arguments are registered first, with the sentinel in their padding columns (read-only blocks are padded with zeros).
+struct MbBlocks {
+    Engine &E;
+    int n, nrhs, W;
+    struct Ent {
+        const double *host;
+        std::unique_ptr<DBuf> buf;
+    };
+    std::vector<Ent> v;
+    std::vector<double> stage;
+    bool ok = true;
+    MbBlocks(Engine &e, int n_, int nrhs_) : E(e), n(n_), nrhs(nrhs_), W(multi_width(nrhs_)), stage((size_t)n_ * multi_width(nrhs_)) {}
+    double *dev(const double *host, bool written)
+    {
+        for (Ent &e : v)
+            if (e.host == host) return e.buf->p;
+        for (size_t i = 0; i < (size_t)n; ++i)
+            for (int c = 0; c < W; ++c) stage[i * W + c] = c < nrhs ? host[(size_t)c * n + i] : (written ? kMbicgPadding : 0.0);
+        v.push_back(Ent{host, std::make_unique<DBuf>(E, stage.size(), stage.data())});
+        if (!v.back().buf->p) ok = false;
+        return v.back().buf->p;
+    }
+    // the block back into its host array; *clean goes false if a padding column no longer holds the sentinel
+    bool get(double *host, bool *clean)
+    {
+        for (Ent &e : v)
+            if (e.host == host) {
+                if (!e.buf->get(stage.data())) return false;
+                for (size_t i = 0; i < (size_t)n; ++i) {
+                    for (int c = 0; c < nrhs; ++c) host[(size_t)c * n + i] = stage[i * W + c];
+                    for (int c = nrhs; c < W; ++c)
+                        if (std::memcmp(&stage[i * W + c], &kMbicgPadding, 8) != 0) *clean = false;
+                }
+                return true;
+            }
+        return false;
+    }
+};
+
+// the per-column state of a hook on the device: scal (MB_COUNT x 8, slot-major) and frozen / iters / status (8 ints each); the
+// padding columns are frozen
+struct MbState {
+    DBuf scal, flags;
+    MbicgState s;
+    MbState(Engine &E, int nrhs, const double *scal_host, const int *frozen, const int *iters, const int *status)
+        : scal(E, (size_t)MB_COUNT * kMultiMax), flags(E, (3 * kMultiMax + 1) / 2)
+    {
+        int f[3 * kMultiMax] = {};
+        for (int c = 0; c < kMultiMax; ++c) {
+            f[c] = c < nrhs ? (frozen && frozen[c] != 0) : 1;
+            f[kMultiMax + c] = (c < nrhs && iters) ? iters[c] : 0;
+            f[2 * kMultiMax + c] = (c < nrhs && status) ? status[c] : 0;
+        }
+        if (scal.p) (void)hipMemcpy(scal.p, scal_host, (size_t)MB_COUNT * kMultiMax * 8, hipMemcpyHostToDevice);
+        if (flags.p) (void)hipMemcpy(flags.p, f, sizeof(f), hipMemcpyHostToDevice);
+        s.scal = scal.p;
+        s.frozen = reinterpret_cast<int *>(flags.p);
+        s.iters = s.frozen + kMultiMax;
+        s.status = s.frozen + 2 * kMultiMax;
+    }
+    bool ok() const { return scal.p && flags.p; }
+};
+
+// a zeroed scalar block with one or two slots set per column
+struct MbScal {
+    double host[MB_COUNT * kMultiMax] = {};
+    MbScal &set(int slot, int nrhs, const double *v)
+    {
+        for (int c = 0; c < nrhs; ++c) host[slot * kMultiMax + c] = v[c];
+        return *this;
+    }
+};
+
+}  // namespace
+
+#define REQUIRE_MBICG_OP(h, n, nrhs)                                                                                  \
+    if (!(h) || !(h)->eng) return fail(SPARSH_EINVAL, "null handle");                                                 \
+    if ((n) <= 0) return fail(SPARSH_EINVAL, "n <= 0");                                                               \
+    if ((nrhs) < 1 || (nrhs) > SPARSH_MAX_RHS) return fail(SPARSH_EINVAL, "nrhs must be 1 .. SPARSH_MAX_RHS (8)")
+
+extern "C" {
+
+int sparsh_mbicg_info(sparsh_handle h, int *iterations, long *bytes)
+{
+    if (!h || !h->eng) return fail(SPARSH_EINVAL, "null handle");
+    if (iterations) *iterations = h->eng->mbicg_iterations();
+    if (bytes) *bytes = (long)h->eng->mbicg_bytes();
+    return SPARSH_OK;
+}
+
+int sparsh_op_dot2_multi(sparsh_handle h, int n, int nrhs, const double *a, const double *b, const double *c, const double *d, double *part0,
+                         double *part1, int *nblk)
+{
+    REQUIRE_MBICG_OP(h, n, nrhs);
+    if (!a || !b || !c || !d || !part0 || !part1 || !nblk || part0 == part1) return fail(SPARSH_EINVAL, "NULL array");
+    REQUIRE_READY(h);
+    REQUIRE_SINGLE(h);
+    Engine &E = *h->eng;
+    MbBlocks V(E, n, nrhs);
+    const int W = V.W, g = mbicg_reduce_grid(n);
+    const double *da = V.dev(a, false), *db = V.dev(b, false), *dc = V.dev(c, false), *dd = V.dev(d, false);
+    DBuf p0(E, (size_t)W * g), p1(E, (size_t)W * g);
+    if (!V.ok || !p0.p || !p1.p) return fail(SPARSH_ENODEV, "device allocation or H2D copy failed");
+    *nblk = launch_dot2_multi(n, W, da, db, dc, dd, p0.p, p1.p, E.stream());
+    return done(E, p0.get(part0) && p1.get(part1));
+}
+
+int sparsh_op_bicg_s_multi(sparsh_handle h, int n, int nrhs, const int *frozen, const double *alpha, const double *R, const double *AP,
+                           double *S)
+{
+    REQUIRE_MBICG_OP(h, n, nrhs);
+    if (!frozen || !alpha || !R || !AP || !S || S == R || S == AP) return fail(SPARSH_EINVAL, "NULL array");
+    REQUIRE_READY(h);
+    REQUIRE_SINGLE(h);
+    Engine &E = *h->eng;
+    MbBlocks V(E, n, nrhs);
+    MbScal sc;
+    MbState st(E, nrhs, sc.set(MB_ALPHA, nrhs, alpha).host, frozen, nullptr, nullptr);
+    double *ds = V.dev(S, true);
+    const double *dr = V.dev(R, false), *dap = V.dev(AP, false);
+    if (!V.ok || !st.ok()) return fail(SPARSH_ENODEV, "device allocation or H2D copy failed");
+    launch_bicg_s_multi(n, V.W, st.s, dr, dap, ds, E.stream());
+    bool clean = true;
+    if (!V.get(S, &clean)) return done(E, false);
+    if (!clean) return fail(SPARSH_ENUMERIC, "a padding column of the block was written");
+    return done(E, true);
+}
+
+int sparsh_op_bicg_xr_multi(sparsh_handle h, int n, int nrhs, const int *frozen, const double *alpha, const double *omega, const double *P1,
+                            const double *S1, const double *S, const double *AS, const double *R0, double *X, double *R, double *part0,
+                            double *part1, int *nblk)
+{
+    REQUIRE_MBICG_OP(h, n, nrhs);
+    if (!frozen || !alpha || !omega || !P1 || !S1 || !S || !AS || !R0 || !X || !R || !part0 || !part1 || !nblk) return fail(SPARSH_EINVAL, "NULL array");
+    if (X == R || part0 == part1) return fail(SPARSH_EINVAL, "the written arrays must be distinct");
+    for (const double *in : {P1, S1, S, AS, R0})
+        if (in == X || in == R) return fail(SPARSH_EINVAL, "a written block may not be a read block");
+    REQUIRE_READY(h);
+    REQUIRE_SINGLE(h);
+    Engine &E = *h->eng;
+    MbBlocks V(E, n, nrhs);
+    MbScal sc;
+    sc.set(MB_ALPHA, nrhs, alpha).set(MB_OMEGA1, nrhs, omega);
+    MbState st(E, nrhs, sc.host, frozen, nullptr, nullptr);
+    const int W = V.W, g = mbicg_reduce_grid(n);
+    double *dx = V.dev(X, true), *dr = V.dev(R, true);
+    const double *dp1 = V.dev(P1, false), *ds1 = V.dev(S1, false), *ds = V.dev(S, false), *das = V.dev(AS, false), *dr0 = V.dev(R0, false);
+    DBuf p0(E, (size_t)W * g), p1(E, (size_t)W * g);
+    if (!V.ok || !st.ok() || !p0.p || !p1.p) return fail(SPARSH_ENODEV, "device allocation or H2D copy failed");
+    *nblk = launch_bicg_xr_multi(n, W, st.s, dp1, ds1, ds, das, dr0, dx, dr, p0.p, p1.p, E.stream());
+    bool clean = true;
+    if (!(V.get(X, &clean) && V.get(R, &clean) && p0.get(part0) && p1.get(part1))) return done(E, false);
+    if (!clean) return fail(SPARSH_ENUMERIC, "a padding column of a block was written");
+    return done(E, true);
+}
+
+int sparsh_op_bicg_p_multi(sparsh_handle h, int n, int nrhs, const int *frozen, const double *beta, const double *omega, const double *R,
+                           const double *AP, double *P)
+{
+    REQUIRE_MBICG_OP(h, n, nrhs);
+    if (!frozen || !beta || !omega || !R || !AP || !P || P == R || P == AP) return fail(SPARSH_EINVAL, "NULL array");
+    REQUIRE_READY(h);
+    REQUIRE_SINGLE(h);
+    Engine &E = *h->eng;
+    MbBlocks V(E, n, nrhs);
+    MbScal sc;
+    sc.set(MB_BETA, nrhs, beta).set(MB_OMEGA1, nrhs, omega);
+    MbState st(E, nrhs, sc.host, frozen, nullptr, nullptr);
+    double *dp = V.dev(P, true);
+    const double *dr = V.dev(R, false), *dap = V.dev(AP, false);
+    if (!V.ok || !st.ok()) return fail(SPARSH_ENODEV, "device allocation or H2D copy failed");
+    launch_bicg_p_multi(n, V.W, st.s, dr, dap, dp, E.stream());
+    bool clean = true;
+    if (!V.get(P, &clean)) return done(E, false);
+    if (!clean) return fail(SPARSH_ENUMERIC, "a padding column of the block was written");
+    return done(E, true);
+}
+
+int sparsh_op_mbicg_finalize(sparsh_handle h, int code, int nrhs, const double *part0, int n0, const double *part1, int n1, double *scal,
+                             int *frozen, int *iters, int *status, double tol, double *hist, int hist_cap, int it)
+{
+    if (!h || !h->eng) return fail(SPARSH_EINVAL, "null handle");
+    if (nrhs < 1 || nrhs > SPARSH_MAX_RHS) return fail(SPARSH_EINVAL, "nrhs must be 1 .. SPARSH_MAX_RHS (8)");
+    if (code < MBFIN_INIT || code > MBFIN_BETA_RES) return fail(SPARSH_EINVAL, "code must be one of the finalise codes 0..3");
+    if (!part0 || !scal || !frozen || !iters || !status) return fail(SPARSH_EINVAL, "NULL array");
+    if (n0 < 1 || n0 > kMultiGridMax || (part1 && (n1 < 1 || n1 > kMultiGridMax))) return fail(SPARSH_EINVAL, "the partial counts must be 1 .. SPARSH_MBICG_PARTIALS");
+    if (hist_cap < 0 || (hist_cap > 0 && !hist) || it < 0) return fail(SPARSH_EINVAL, "hist_cap < 0, it < 0 or no history array");
+    REQUIRE_READY(h);
+    REQUIRE_SINGLE(h);
+    Engine &E = *h->eng;
+    const int W = multi_width(nrhs);
+    MbState st(E, nrhs, scal, frozen, iters, status);
+    DBuf p0(E, (size_t)W * n0, part0), p1(E, (size_t)W * (part1 ? n1 : 1), part1);
+    // the histories of all 8 columns at the stride hist_cap, as the loop keeps them (one entry more: never an empty allocation)
+    std::vector<double> hh((size_t)kMultiMax * hist_cap + 1, 0.0);
+    for (int c = 0; c < nrhs && hist_cap > 0; ++c) std::copy(hist + (size_t)c * hist_cap, hist + (size_t)(c + 1) * hist_cap, hh.begin() + (size_t)c * hist_cap);
+    DBuf dh(E, hh.size(), hh.data());
+    if (!st.ok() || !p0.p || !p1.p || !dh.p) return fail(SPARSH_ENODEV, "device allocation or H2D copy failed");
+    launch_finalize_mbicg((MbicgFin)code, W, nrhs, p0.p, n0, part1 ? p1.p : nullptr, part1 ? n1 : 0, st.s, tol, hist_cap > 0 ? dh.p : nullptr,
+                          hist_cap, it, E.stream());
+    int f[3 * kMultiMax];
+    bool ok = st.scal.get(scal) && dh.get(hh.data()) && hipMemcpy(f, st.flags.p, sizeof(f), hipMemcpyDeviceToHost) == hipSuccess;
+    if (!ok) return done(E, false);
+    for (int c = 0; c < nrhs; ++c) {
+        frozen[c] = f[c];
+        iters[c] = f[kMultiMax + c];
+        status[c] = f[2 * kMultiMax + c];
+        if (hist_cap > 0) std::copy(hh.begin() + (size_t)c * hist_cap, hh.begin() + (size_t)(c + 1) * hist_cap, hist + (size_t)c * hist_cap);
+    }
+    for (int c = nrhs; c < W; ++c)
+        if (!f[c]) return fail(SPARSH_ENUMERIC, "a padding column came back running");
+    return done(E, true);
 }
 
 }  // extern "C"

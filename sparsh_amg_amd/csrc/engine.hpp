@@ -401,6 +401,14 @@ public:
     int bcg_iterations() const { return bcg_last_[0]; }
     int bcg_min_rank() const { return bcg_last_[1]; }
     int bcg_dropped() const { return bcg_last_[2]; }
+    // block BiCGStab (engine_mbicg.cpp) with the arguments, conventions and return codes of solve_multi_dev:
+    // per column the arithmetic of bicg(precond = true), the columns frozen one by one on the device.  X, R, P and AP are the block
+    // PCG's x, r, p and Ap; R0, S, AS, P1 and the per-column state are the solver's own, reserved at the first such call for a
+    // width and counted in mbicg_bytes(), never in multi_bytes().
+    int solve_mbicg_dev(int nrhs, const double *B, long ldb, double *X, long ldx, int max_iters, double *hist, int hist_cap, int *iters,
+                        int *status, double *seconds);
+    size_t mbicg_bytes() const { return mbicg_bytes_; }
+    int mbicg_iterations() const { return mbicg_last_; }
     // operator-level hooks on column-major device arrays (ld = rows of the level): each interleaves, runs the block launch and
     // de-interleaves.  which: 0 Y = A X with dots, 1 residual, 2 Jacobi leg (sweeps, x_is_zero), 3 restriction, 4 prolongation
     // (X = coarse block, Y = fine block in/out), 5 coarse solve, 6 one vcycle_multi from a zero guess (level 0)
@@ -641,6 +649,12 @@ private:
     double *bcg_gm_ = nullptr, *bcg_coef_ = nullptr, *bcg_part_ = nullptr;
     size_t bcg_bytes_ = 0;
     int bcg_last_[3] = {0, 0, 0};  // iterations, minimum rank and dropped directions of the last solve
+    // block BiCGStab: four blocks of n * width doubles and the per-column state; in multi_allocs_ too, counted on their own
+    int mbicg_reserve();
+    MbicgState mb_;
+    double *mb_r0_ = nullptr, *mb_s_ = nullptr, *mb_as_ = nullptr, *mb_p1_ = nullptr;
+    size_t mbicg_bytes_ = 0;
+    int mbicg_last_ = 0;  // iterations of the last solve (the largest count of a column)
 
     // LOBPCG (engine_eig.cpp): seven interleaved blocks of n * width doubles, the partial sums of the Gram and residual launches,
     // G = [S^T S, S^T A S, residual norms] and coef = [Cx, Cw, Cp, theta]

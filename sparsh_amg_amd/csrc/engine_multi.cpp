@@ -44,6 +44,9 @@ void Engine::multi_forget()
     bcg_ = BcgState();  // block CG's small arrays are in multi_allocs_ too (engine_bcg.cpp)
     bcg_gm_ = bcg_coef_ = bcg_part_ = nullptr;
     bcg_bytes_ = 0;
+    mb_ = MbicgState();  // ... and block BiCGStab's blocks (engine_mbicg.cpp)
+    mb_r0_ = mb_s_ = mb_as_ = mb_p1_ = nullptr;
+    mbicg_bytes_ = 0;
 }
 
 void Engine::multi_release()

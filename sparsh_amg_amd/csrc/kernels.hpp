@@ -555,4 +555,39 @@ void launch_bcg_dir(int n, int W, int k, const int *done, const double *Z, const
 void launch_bcg_finalize(int W, int nrhs, const double *partial, int nblk, const BcgState &s, double tol, double *hist, int hist_cap, int it,
                          hipStream_t st);
 
+// ---- block BiCGStab on interleaved blocks (mbicg_kernels.hip).  Per column the arithmetic of the single
+// BiCGStab kernels; the columns are frozen one by one as in block PCG.  scal[slot * kMultiMax + c]; frozen / iters / status as in
+// MultiState (status kMultiStatusNumeric for a column frozen on a NaN residual).
+enum MbicgSlot : int { MB_ALPHA1 = 0, MB_APR0, MB_ALPHA, MB_ASS, MB_ASAS, MB_OMEGA1, MB_BETA, MB_RR0, MB_RES, MB_COUNT };
+struct MbicgState {
+    double *scal = nullptr;  // MB_COUNT * kMultiMax
+    int *frozen = nullptr, *iters = nullptr, *status = nullptr;  // kMultiMax each
+};
+enum MbicgFin : int {
+    MBFIN_INIT = 0,     // res = sqrt(sum0); scalars zeroed; freezes the padding columns and the columns with res <= tol (iters 0) or a NaN
+    MBFIN_ALPHA = 1,    // FIN_BICG_ALPHA per column that is not frozen: alpha1 = sum0 ; apr0 = sum1 ; alpha = alpha1 / apr0
+    MBFIN_OMEGA = 2,    // FIN_BICG_OMEGA: ass = sum0 ; asas = sum1 ; omega1 = asas == 0 ? 0 : ass / asas
+    MBFIN_BETA_RES = 3  // FIN_BICG_BETA: beta = sum0 / alpha1 * (alpha / omega1) ; rr0 = sum0 ; res = sqrt(sum1) ; hist[c * hist_cap + it]
+                        // (it < hist_cap), iters = it + 1, and the freeze
+};
+// workgroups of the S and P launches: one per 512 / W rows, at most kMultiGridMax (grid-stride beyond)
+int mbicg_grid(int n, int W);
+// workgroups of the two reducing launches, where a lane owns a row: the grid of the single-vector elementwise kernels, one per 512
+// rows, at most kMultiGridMax
+int mbicg_reduce_grid(int n);
+// part0[c * g + w] / part1[c * g + w]: workgroup w's shares of a_c . b_c / c_c . d_c (W * g doubles each; the blocks may be one
+// another).  Returns g = mbicg_reduce_grid(n), as launch_bicg_xr_multi does.
+int launch_dot2_multi(int n, int W, const double *a, const double *b, const double *c, const double *d, double *part0, double *part1,
+                      hipStream_t st);
+// S = R - alpha_c AP
+void launch_bicg_s_multi(int n, int W, const MbicgState &s, const double *R, const double *AP, double *S, hipStream_t st);
+// X = (X + alpha_c P1) + omega_c S1 ; R = S - omega_c AS ; part0: shares of R_c . R0_c ; part1: shares of R_c . R_c
+int launch_bicg_xr_multi(int n, int W, const MbicgState &s, const double *P1, const double *S1, const double *S, const double *AS,
+                         const double *R0, double *X, double *R, double *part0, double *part1, hipStream_t st);
+// P = R + beta_c (P - omega_c AP)
+void launch_bicg_p_multi(int n, int W, const MbicgState &s, const double *R, const double *AP, double *P, hipStream_t st);
+// one workgroup: column c's partials of p0 (n0 of them) and p1 (n1; p1 may be nullptr: sum1 = 0) added in a fixed order, then `code`
+void launch_finalize_mbicg(MbicgFin code, int W, int nrhs, const double *p0, int n0, const double *p1, int n1, const MbicgState &s, double tol,
+                           double *hist, int hist_cap, int it, hipStream_t st);
+
 }  // namespace sparsh

@@ -61,6 +61,24 @@ def poisson3d_neumann(nx: int, ny: int | None = None, nz: int | None = None):
     return rp, ci, v
 
 
+def convection_diffusion(nx: int, ny: int, nz: int | None = None, cx: float = 0.8, cy: float = 0.3, cz: float = 0.0):
+    """Upwind convection-diffusion on an nx x ny (x nz) grid, x fastest: the Laplacian stencil (2 per dimension, -1) plus c_k times the
+    first-order upwind difference (1 on the diagonal, -1 on the lower neighbour) in every dimension.  Unsymmetric for c != 0; with
+    nx = ny it is kron(I, T) + kron(T, I) + cx kron(I, C) + cy kron(C, I) of T = tridiag(-1, 2, -1), C = bidiag(-1, 1)."""
+    dims = (nx, ny) if nz is None else (nx, ny, nz)
+    cs = (cx, cy) if nz is None else (cx, cy, cz)
+    nd = len(dims)
+    rp, ci, v = _stencil_csr(dims, 2.0 * nd)
+    rows = np.repeat(np.arange(len(rp) - 1, dtype=np.int64), np.diff(rp))
+    stride, diag = 1, 2.0 * nd
+    for d, c in zip(dims, cs):
+        v[ci == rows - stride] = -1.0 + c * -1.0
+        diag = diag + c * 1.0
+        stride *= d
+    v[ci == rows] = diag
+    return rp, ci, v
+
+
 def dumbbell_laplacian(a: int, bridge: int):
     """Graph Laplacian (off-diagonal entries -1, the diagonal the degree) of two a x a x a grid cubes joined by a corridor of
     ``bridge`` points, one point wide, which runs from the last point of cube 1 to the first point of cube 2.  Order: cube 1
