@@ -642,6 +642,44 @@ private:
     MultiState ms_;
     int mflip_ = 0;  // bench_multi_launch
     std::vector<void *> multi_allocs_;
+    size_t mlen0_ = 0;  // doubles of mlev_[0].x as multi_reserve allocated it (block BiCGStab swaps a block of its own with it)
+    // ---- what the block solvers share (engine_multi.cpp): block PCG, block CG and block BiCGStab all of it, LOBPCG the allocator and
+    // the clock.
+    // `doubles` doubles zeroed on the stream, registered in `owner` and counted in `bytes`.  ok false on entry: nothing happens; on any
+    // failure what was allocated is freed, ok becomes false and nullptr comes back
+    double *take_zeroed(std::vector<void *> &owner, size_t &bytes, bool &ok, size_t doubles);
+    // the entry of a block solve: ready, no fault, multi_refusal(), multi_reserve(nrhs), then max_iters <= 0 -> params.max_iter and
+    // the clamp to the rows of level 0 (the single loop stops at n iterations too); SPARSH_* code, the reason in error
+    int block_begin(int nrhs, int &max_iters);
+    // HIP-event time of the stream work from its construction to stop(), which synchronises and writes *seconds; seconds == nullptr:
+    // no event is made and stop() does nothing.  The destructor drops events that no stop() took care of
+    struct StreamClock {
+        StreamClock(Engine &e, double *seconds);
+        ~StreamClock();
+        StreamClock(const StreamClock &) = delete;
+        StreamClock &operator=(const StreamClock &) = delete;
+        void stop();
+
+    private:
+        Engine &eng_;
+        double *seconds_;
+        hipEvent_t e0_ = nullptr, e1_ = nullptr;
+    };
+    // host[0, count) = dev[0, count) through pinned_, stream synchronised
+    void read_block_flags(const int *dev, int *host, int count);
+    // the loop of the three block solvers on `count` device flags and their host copy: a first read, then while running() (evaluated
+    // on the host copy), below the cap and without fault: body(it) = the launches of iteration it, and after the iterations read_due
+    // names another read and, under print_solve, shown(it) = the solver's own line
+    template <class Running, class Body, class Shown>
+    void block_loop(const int *dev, int *host, int count, int max_iters, Running running, Body body, Shown shown);
+    // after the loop: the block x back into the caller's X, the last flag read, the clock stopped, launch errors noted under `what`;
+    // returns the fault (SPARSH_OK: none)
+    int block_finish(int nrhs, const double *x, double *X, long ldx, const int *dev, int *host, int count, StreamClock &clock, const char *what);
+    // the first min(count, hist_cap) residuals of column c to hist[c * hist_cap ...] (stream idle)
+    void copy_hist_multi(int c, int count, double *hist, int hist_cap);
+    // block PCG's and block BiCGStab's end, from flags = [frozen, iters, status] (kMultiMax each): status[c], iters[c] and the history
+    // per column, the text in error; returns the fault or SPARSH_OK / ENOCONV / ENUMERIC, and through *most the largest count
+    int block_verdict(int nrhs, const int *flags, double *hist, int hist_cap, int *iters, int *status, int *most = nullptr);
     // block CG: gm = [G, C1, C2] and coef = [alpha, beta] (W x W each), the factor and flags, the Gram launch's partial sums; in
     // multi_allocs_ (they go with the block vectors) but counted on their own
     int bcg_reserve();
@@ -760,5 +798,20 @@ private:
     void tune_box_kernels();
     void tune_placement();
 };
+
+// (here because three files instantiate it: engine_multi.cpp, engine_bcg.cpp, engine_mbicg.cpp)
+template <class Running, class Body, class Shown>
+void Engine::block_loop(const int *dev, int *host, int count, int max_iters, Running running, Body body, Shown shown)
+{
+    read_block_flags(dev, host, count);
+    for (int it = 0; running() && it < max_iters && fault_ == SPARSH_OK;) {
+        body(it);
+        ++it;
+        if (read_due(it, it >= max_iters)) {
+            read_block_flags(dev, host, count);
+            if (prm_.print_solve) shown(it);
+        }
+    }
+}
 
 }  // namespace sparsh

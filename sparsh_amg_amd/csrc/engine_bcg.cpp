@@ -3,12 +3,12 @@
 //
 // The loop runs on the block vectors of engine_multi.cpp (x, r, p, Ap and the cycle's level blocks) with the block V-cycle, the block
 // SpMV and the eigensolver's Gram launch; its own kernels are in bcg_kernels.hip.  All coefficients stay on the device; the host reads
-// 16 flags every params.check_every iterations.
+// 16 flags every params.check_every iterations.  The gate, the clock, the loop and the finish are the block solvers' shared ones
+// (engine_multi.cpp); the verdict is its own: one status for all columns.
 #include "engine.hpp"
 
 #include <algorithm>
 #include <cstdio>
-#include <cstring>
 
 namespace sparsh {
 
@@ -20,18 +20,7 @@ int Engine::bcg_reserve()
     const int W = mw_;
     bool ok = true;
     size_t bytes = 0;
-    auto take = [&](size_t doubles) -> double * {
-        if (!ok) return nullptr;
-        double *p = static_cast<double *>(dalloc(doubles * 8));
-        if (!p || !check(hipMemsetAsync(p, 0, doubles * 8, st_), "hipMemsetAsync")) {
-            ok = false;
-            if (p) dfree(p);
-            return nullptr;
-        }
-        multi_allocs_.push_back(p);
-        bytes += doubles * 8;
-        return p;
-    };
+    auto take = [&](size_t doubles) { return take_zeroed(multi_allocs_, bytes, ok, doubles); };
     double *gm = take(3 * (size_t)W * W);
     double *coef = take(2 * (size_t)W * W);
     double *part = take(2 * (size_t)W * W * kEigMaxGrid);
@@ -57,30 +46,13 @@ int Engine::bcg_reserve()
 int Engine::solve_bcg_dev(int nrhs, const double *B, long ldb, double *X, long ldx, int max_iters, double *hist, int hist_cap, int *iters,
                           int *status, double *seconds)
 {
-    if (!ready_) {
-        error = "sparsh_setup has not been called";
-        return SPARSH_ESTATE;
-    }
-    if (fault_ != SPARSH_OK) return fault_;
-    if (const char *why = multi_refusal()) {
-        error = why;
-        return SPARSH_EINVAL;
-    }
-    if (int rc = multi_reserve(nrhs); rc != SPARSH_OK) return rc;
+    if (int rc = block_begin(nrhs, max_iters); rc != SPARSH_OK) return rc;
     if (int rc = bcg_reserve(); rc != SPARSH_OK) return rc;
-    if (max_iters <= 0) max_iters = prm_.max_iter;
-    max_iters = std::min(max_iters, lev_[0].nglob);
     const int W = mw_, n = lev_[0].n, k = nrhs;
-    const int check_every = std::max(1, prm_.check_every);
     const int *done = bcg_.flags + BF_DONE;
     double *G = bcg_gm_, *C1 = bcg_gm_ + W * W, *C2 = bcg_gm_ + 2 * W * W;
     double *alpha = bcg_coef_, *beta = bcg_coef_ + W * W;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (seconds) {
-        HIPCHK(hipEventCreate(&e0));
-        HIPCHK(hipEventCreate(&e1));
-        HIPCHK(hipEventRecord(e0, st_));
-    }
+    StreamClock clock(*this, seconds);
     // init: R = B - A X, ||R_c||, Z = M R, P = Z
     launch_interleave(n, nrhs, W, X, ldx, mx_, st_);
     launch_interleave(n, nrhs, W, B, ldb, mr_, st_);
@@ -91,50 +63,30 @@ int Engine::solve_bcg_dev(int nrhs, const double *B, long ldb, double *X, long l
     HIPCHK(hipMemcpyAsync(mp_, mlev_[0].x, (size_t)n * W * 8, hipMemcpyDeviceToDevice, st_));
 
     int flags[BF_COUNT];
-    auto read_flags = [&]() {
-        HIPCHK(hipMemcpyAsync(pinned_, bcg_.flags, sizeof(flags), hipMemcpyDeviceToHost, st_));
-        HIPCHK(hipStreamSynchronize(st_));
-        std::memcpy(flags, pinned_, sizeof(flags));
-    };
     GramPairs two{}, one{};
     two.u[0] = mp_, two.v[0] = mAp_, two.dst[0] = 0;      // G  = P^T Q
     two.u[1] = mp_, two.v[1] = mr_, two.dst[1] = W * W;   // C1 = P^T R
     one.u[0] = mAp_, one.dst[0] = 2 * W * W;              // C2 = Q^T Z (Z is wherever the cycle's ping-pong left it)
-    read_flags();
-    int it = 0;
-    while (!flags[BF_DONE] && it < max_iters && fault_ == SPARSH_OK) {
-        MultiArgs a;
-        a.x = mp_;
-        a.y = mAp_;
-        launch_csr_multi(lev_[0].A, W, OP_SPMV, a, st_, cfg_);  // Q = A P
-        launch_gram_multi(n, W, 2, two, bcg_part_, bcg_gm_, W, st_);
-        launch_bcg_small(W, k, true, G, C1, 1.0, bcg_, alpha, it, st_);  // alpha = pinv(G) C1
-        const int nrr = launch_bcg_update(n, W, k, done, mx_, mr_, mp_, mAp_, alpha, mx_, mr_, mpart1_, st_);
-        launch_bcg_finalize(W, nrhs, mpart1_, nrr, bcg_, prm_.tol, mhist_, hist_cap_dev_, it, st_);
-        vcycle_multi(mr_);  // Z = M R
-        one.v[0] = mlev_[0].x;
-        launch_gram_multi(n, W, 1, one, bcg_part_, bcg_gm_, W, st_);
-        launch_bcg_small(W, k, false, G, C2, -1.0, bcg_, beta, it, st_);  // beta = -pinv(G) C2, the factor kept
-        launch_bcg_dir(n, W, k, done, mlev_[0].x, mp_, beta, mp_, st_);   // P = Z + P beta
-        ++it;
-        if (it % check_every == 0 || it >= max_iters) {
-            read_flags();
-            if (prm_.print_solve) std::printf("%d\trank %d of %d\n", it, flags[BF_RANK], nrhs);
-        }
-    }
-    launch_deinterleave(n, nrhs, W, mx_, X, ldx, st_);
-    read_flags();
-    if (seconds) {
-        HIPCHK(hipEventRecord(e1, st_));
-        HIPCHK(hipEventSynchronize(e1));
-        float ms = 0.f;
-        HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-        *seconds = ms * 1e-3;
-        HIPCHK(hipEventDestroy(e0));
-        HIPCHK(hipEventDestroy(e1));
-    }
-    note_hip(hipGetLastError(), "kernel launch during the block CG solve");
-    if (fault_ != SPARSH_OK) return fault_;
+    block_loop(
+        bcg_.flags, flags, BF_COUNT, max_iters, [&] { return !flags[BF_DONE]; },
+        [&](int it) {
+            MultiArgs a;
+            a.x = mp_;
+            a.y = mAp_;
+            launch_csr_multi(lev_[0].A, W, OP_SPMV, a, st_, cfg_);  // Q = A P
+            launch_gram_multi(n, W, 2, two, bcg_part_, bcg_gm_, W, st_);
+            launch_bcg_small(W, k, true, G, C1, 1.0, bcg_, alpha, it, st_);  // alpha = pinv(G) C1
+            const int nrr = launch_bcg_update(n, W, k, done, mx_, mr_, mp_, mAp_, alpha, mx_, mr_, mpart1_, st_);
+            launch_bcg_finalize(W, nrhs, mpart1_, nrr, bcg_, prm_.tol, mhist_, hist_cap_dev_, it, st_);
+            vcycle_multi(mr_);  // Z = M R
+            one.v[0] = mlev_[0].x;
+            launch_gram_multi(n, W, 1, one, bcg_part_, bcg_gm_, W, st_);
+            launch_bcg_small(W, k, false, G, C2, -1.0, bcg_, beta, it, st_);  // beta = -pinv(G) C2, the factor kept
+            launch_bcg_dir(n, W, k, done, mlev_[0].x, mp_, beta, mp_, st_);   // P = Z + P beta
+        },
+        [&](int it) { std::printf("%d\trank %d of %d\n", it, flags[BF_RANK], nrhs); });
+    if (int rc = block_finish(nrhs, mx_, X, ldx, bcg_.flags, flags, BF_COUNT, clock, "kernel launch during the block CG solve"); rc != SPARSH_OK)
+        return rc;
     const int ran = flags[BF_ITERS];
     bcg_last_[0] = ran;
     bcg_last_[1] = flags[BF_MIN_RANK];
@@ -147,12 +99,10 @@ int Engine::solve_bcg_dev(int nrhs, const double *B, long ldb, double *X, long l
         rc = SPARSH_ENOCONV;  // the cap came first: X holds the iterate reached
         error = "iteration cap reached before ||r|| <= tol in every column of the block";
     }
-    const int m = std::min(std::min(ran, hist_cap), hist_cap_dev_);
     for (int c = 0; c < nrhs; ++c) {
         if (status) status[c] = rc;
         if (iters) iters[c] = ran;
-        if (hist && m > 0)
-            HIPCHK(hipMemcpy(hist + (size_t)c * hist_cap, mhist_ + (size_t)c * hist_cap_dev_, (size_t)m * 8, hipMemcpyDeviceToHost));
+        copy_hist_multi(c, ran, hist, hist_cap);
     }
     return fault_ != SPARSH_OK ? fault_ : rc;
 }

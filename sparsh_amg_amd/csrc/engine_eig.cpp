@@ -66,19 +66,7 @@ int Engine::eig_ortho_reserve()
     if (oM_) return SPARSH_OK;
     const int W = ew_;
     bool ok = true;
-    auto take = [&](size_t doubles) -> double * {
-        if (!ok) return nullptr;
-        const size_t bytes = doubles * 8;
-        double *p = static_cast<double *>(dalloc(bytes));
-        if (!p || !check(hipMemsetAsync(p, 0, bytes, st_), "hipMemsetAsync")) {
-            if (p) dfree(p);
-            ok = false;
-            return nullptr;
-        }
-        ortho_allocs_.push_back(p);
-        ortho_bytes_ += bytes;
-        return p;
-    };
+    auto take = [&](size_t doubles) { return take_zeroed(ortho_allocs_, ortho_bytes_, ok, doubles); };
     oM_ = take((size_t)3 * W);
     oG_ = take((size_t)W * W);
     oT_ = take((size_t)W * W);
@@ -138,19 +126,7 @@ int Engine::eig_con_reserve(int mt, bool gen)
     eig_con_release();
     const int W = ew_, nblk = (mt + W - 1) / W, mpad = nblk * W;
     bool ok = true;
-    auto take = [&](size_t doubles) -> double * {
-        if (!ok) return nullptr;
-        const size_t bytes = doubles * 8;
-        double *p = static_cast<double *>(dalloc(bytes));
-        if (!p || !check(hipMemsetAsync(p, 0, bytes, st_), "hipMemsetAsync")) {
-            if (p) dfree(p);
-            ok = false;
-            return nullptr;
-        }
-        con_allocs_.push_back(p);
-        con_bytes_ += bytes;
-        return p;
-    };
+    auto take = [&](size_t doubles) { return take_zeroed(con_allocs_, con_bytes_, ok, doubles); };
     const size_t len = (size_t)lev_[0].n * W;
     cY_ = take(len * nblk);
     cBY_ = gen ? take(len * nblk) : cY_;
@@ -178,18 +154,7 @@ int Engine::eig_reserve(int nev)
     if (W == ew_) return SPARSH_OK;
     eig_release();
     bool ok = true;
-    auto take = [&](size_t doubles) -> double * {
-        if (!ok) return nullptr;
-        const size_t bytes = doubles * 8;
-        double *p = static_cast<double *>(dalloc(bytes));
-        if (!p || !check(hipMemsetAsync(p, 0, bytes, st_), "hipMemsetAsync")) {
-            ok = false;
-            return p;
-        }
-        eig_allocs_.push_back(p);
-        eig_bytes_ += bytes;
-        return p;
-    };
+    auto take = [&](size_t doubles) { return take_zeroed(eig_allocs_, eig_bytes_, ok, doubles); };
     const size_t len = (size_t)lev_[0].n * W;
     double **blocks[7] = {&eX_, &eAX_, &eW_, &eAW_, &eP_, &eAP_, &eR_};
     for (double **b : blocks) *b = take(len);
@@ -212,18 +177,12 @@ int Engine::eig_reserve_gen(int nev)
 {
     if (int rc = eig_reserve(nev); rc != SPARSH_OK) return rc;
     if (eBX_) return SPARSH_OK;
-    const size_t bytes = (size_t)lev_[0].n * ew_ * 8;
+    bool ok = true;
     double **blocks[3] = {&eBX_, &eBW_, &eBP_};
-    for (double **b : blocks) {
-        double *p = static_cast<double *>(dalloc(bytes));
-        if (!p || !check(hipMemsetAsync(p, 0, bytes, st_), "hipMemsetAsync")) {
-            if (p) dfree(p);
-            eig_release();
-            return SPARSH_ENODEV;
-        }
-        eig_allocs_.push_back(p);
-        eig_bytes_ += bytes;
-        *b = p;
+    for (double **b : blocks) *b = take_zeroed(eig_allocs_, eig_bytes_, ok, (size_t)lev_[0].n * ew_);
+    if (!ok) {
+        eig_release();
+        return SPARSH_ENODEV;
     }
     return SPARSH_OK;
 }
@@ -339,12 +298,7 @@ int Engine::eigs_run(bool gen, int nev, double *X, long ldx, double tol, int max
     eig_restarts_ = 0;
     eig_dropped_[0] = eig_dropped_[1] = 0;
     const double *mdown = down + ndown;  // the masks as they came down: active, W in the basis, P in the basis
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (seconds) {
-        HIPCHK(hipEventCreate(&e0));
-        HIPCHK(hipEventCreate(&e1));
-        HIPCHK(hipEventRecord(e0, st_));
-    }
+    StreamClock clock(*this, seconds);
     GramPairs prs;
     eig_gram_pairs(prs, gen);
     double *norms = eG_ + 2 * ld * ld, *theta_dev = ecoef_ + 3 * W * W, *rpart = epart_ + (size_t)kEigPairs * W * W * kEigMaxGrid;
@@ -382,18 +336,8 @@ int Engine::eigs_run(bool gen, int nev, double *X, long ldx, double tol, int max
             if (!std::isfinite(p[i])) return false;
         return true;
     };
-    auto stop_clock = [&]() {
-        if (!seconds) return;
-        HIPCHK(hipEventRecord(e1, st_));
-        HIPCHK(hipEventSynchronize(e1));
-        float ms = 0.f;
-        HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-        *seconds = ms * 1e-3;
-        HIPCHK(hipEventDestroy(e0));
-        HIPCHK(hipEventDestroy(e1));
-    };
     auto numeric = [&](const char *what) {
-        stop_clock();
+        clock.stop();
         for (int c = 0; c < k; ++c) status[c] = SPARSH_ENUMERIC;
         if (fault_ != SPARSH_OK) return fault_;  // (a NaN that a failed launch left behind: the fault's own message stands)
         error = what;
@@ -431,7 +375,7 @@ int Engine::eigs_run(bool gen, int nev, double *X, long ldx, double tol, int max
         HIPCHK(hipMemcpyAsync(down, cG_, (size_t)mpad * mpad * 8, hipMemcpyDeviceToHost, st_));
         HIPCHK(hipStreamSynchronize(st_));
         if (fault_ != SPARSH_OK) {
-            stop_clock();
+            clock.stop();
             return fault_;
         }
         double Gc[kEigConMax * kEigConMax], Gi[kEigConMax * kEigConMax];
@@ -461,7 +405,7 @@ int Engine::eigs_run(bool gen, int nev, double *X, long ldx, double tol, int max
     read_down(0, 2 * ld * ld);
     for (int c = 0; c < k; ++c) idx[c] = c;
     if (fault_ != SPARSH_OK) {  // (the fault's own message stands)
-        stop_clock();
+        clock.stop();
         return fault_;
     }
     if (!finite(down, 2 * ld * ld))
@@ -571,7 +515,7 @@ int Engine::eigs_run(bool gen, int nev, double *X, long ldx, double tol, int max
     }
     launch_deinterleave(n, k, W, eX_, X, ldx, st_);
     HIPCHK(hipStreamSynchronize(st_));
-    stop_clock();
+    clock.stop();
     note_hip(hipGetLastError(), "kernel launch during the eigensolve");
     if (fault_ != SPARSH_OK) return fault_;
     std::copy(theta, theta + k, lambda);

@@ -36,6 +36,7 @@ void Engine::multi_forget()
 {
     mw_ = 0;
     multi_bytes_ = 0;
+    mlen0_ = 0;
     mlev_.clear();
     multi_allocs_.clear();
     mx_ = mr_ = mp_ = mAp_ = mpart0_ = mpart1_ = mcs_in_ = mcs_out_ = mhist_ = nullptr;
@@ -62,24 +63,14 @@ int Engine::multi_reserve(int nrhs)
     if (W == mw_) return SPARSH_OK;
     multi_release();
     bool ok = true;
-    auto take = [&](size_t doubles) -> double * {
-        if (!ok) return nullptr;
-        const size_t bytes = std::max<size_t>(doubles, 1) * 8;
-        double *p = static_cast<double *>(dalloc(bytes));
-        if (!p || !check(hipMemsetAsync(p, 0, bytes, st_), "hipMemsetAsync")) {
-            ok = false;
-            return p;
-        }
-        multi_allocs_.push_back(p);
-        multi_bytes_ += bytes;
-        return p;
-    };
+    auto take = [&](size_t doubles) { return take_zeroed(multi_allocs_, multi_bytes_, ok, std::max<size_t>(doubles, 1)); };
     const int nl = (int)lev_.size();
     mlev_.assign((size_t)nl, MultiLevel());
     int cap = kMultiMax;
     for (int l = 0; l < nl; ++l) {
         const DevLevel &L = lev_[l];
         const size_t len = (size_t)L.n * W;
+        if (l == 0) mlen0_ = std::max<size_t>(len, 1);
         mlev_[l].x = take(len);
         mlev_[l].x2 = take(len);
         mlev_[l].r = take(len);
@@ -217,10 +208,23 @@ void Engine::vcycle_multi(const double *b0)
     }
 }
 
-// ---------------------------------------------------------------------------- block PCG
+// ---------------------------------------------------------------------------- what the block solvers share
 
-int Engine::solve_multi_dev(int nrhs, const double *B, long ldb, double *X, long ldx, int max_iters, double *hist, int hist_cap, int *iters,
-                            int *status, double *seconds)
+double *Engine::take_zeroed(std::vector<void *> &owner, size_t &bytes, bool &ok, size_t doubles)
+{
+    if (!ok) return nullptr;
+    double *p = static_cast<double *>(dalloc(doubles * 8));
+    if (!p || !check(hipMemsetAsync(p, 0, doubles * 8, st_), "hipMemsetAsync")) {
+        ok = false;
+        dfree(p);
+        return nullptr;
+    }
+    owner.push_back(p);
+    bytes += doubles * 8;
+    return p;
+}
+
+int Engine::block_begin(int nrhs, int &max_iters)
 {
     if (!ready_) {
         error = "sparsh_setup has not been called";
@@ -233,15 +237,97 @@ int Engine::solve_multi_dev(int nrhs, const double *B, long ldb, double *X, long
     }
     if (int rc = multi_reserve(nrhs); rc != SPARSH_OK) return rc;
     if (max_iters <= 0) max_iters = prm_.max_iter;
-    max_iters = std::min(max_iters, lev_[0].nglob);  // (the single loop stops at n iterations too)
-    const int W = mw_, n = lev_[0].n;
-    const int check_every = std::max(1, prm_.check_every);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (seconds) {
-        HIPCHK(hipEventCreate(&e0));
-        HIPCHK(hipEventCreate(&e1));
-        HIPCHK(hipEventRecord(e0, st_));
+    max_iters = std::min(max_iters, lev_[0].nglob);
+    return SPARSH_OK;
+}
+
+Engine::StreamClock::StreamClock(Engine &e, double *seconds) : eng_(e), seconds_(seconds)
+{
+    if (!seconds_) return;
+    eng_.note_hip(hipEventCreate(&e0_), "hipEventCreate");
+    eng_.note_hip(hipEventCreate(&e1_), "hipEventCreate");
+    eng_.note_hip(hipEventRecord(e0_, eng_.st_), "hipEventRecord");
+}
+
+void Engine::StreamClock::stop()
+{
+    if (!seconds_) return;
+    eng_.note_hip(hipEventRecord(e1_, eng_.st_), "hipEventRecord");
+    eng_.note_hip(hipEventSynchronize(e1_), "hipEventSynchronize");
+    float ms = 0.f;
+    eng_.note_hip(hipEventElapsedTime(&ms, e0_, e1_), "hipEventElapsedTime");
+    *seconds_ = ms * 1e-3;
+    eng_.note_hip(hipEventDestroy(e0_), "hipEventDestroy");
+    eng_.note_hip(hipEventDestroy(e1_), "hipEventDestroy");
+    e0_ = e1_ = nullptr;
+    seconds_ = nullptr;  // stopped
+}
+
+Engine::StreamClock::~StreamClock()
+{
+    if (e0_) (void)hipEventDestroy(e0_);
+    if (e1_) (void)hipEventDestroy(e1_);
+}
+
+void Engine::read_block_flags(const int *dev, int *host, int count)
+{
+    HIPCHK(hipMemcpyAsync(pinned_, dev, (size_t)count * sizeof(int), hipMemcpyDeviceToHost, st_));
+    HIPCHK(hipStreamSynchronize(st_));
+    std::memcpy(host, pinned_, (size_t)count * sizeof(int));
+}
+
+int Engine::block_finish(int nrhs, const double *x, double *X, long ldx, const int *dev, int *host, int count, StreamClock &clock,
+                         const char *what)
+{
+    launch_deinterleave(lev_[0].n, nrhs, mw_, x, X, ldx, st_);
+    read_block_flags(dev, host, count);
+    clock.stop();
+    note_hip(hipGetLastError(), what);
+    return fault_;
+}
+
+void Engine::copy_hist_multi(int c, int count, double *hist, int hist_cap)
+{
+    const int m = std::min(std::min(count, hist_cap), hist_cap_dev_);
+    if (hist && m > 0)
+        HIPCHK(hipMemcpy(hist + (size_t)c * hist_cap, mhist_ + (size_t)c * hist_cap_dev_, (size_t)m * 8, hipMemcpyDeviceToHost));
+}
+
+int Engine::block_verdict(int nrhs, const int *flags, double *hist, int hist_cap, int *iters, int *status, int *most)
+{
+    int rc = SPARSH_OK, largest = 0;
+    bool numeric = false, noconv = false;
+    for (int c = 0; c < nrhs; ++c) {
+        int st = SPARSH_OK;
+        if (!flags[c]) st = SPARSH_ENOCONV;  // the cap came first: x holds the iterate reached
+        else if (flags[2 * kMultiMax + c] == kMultiStatusNumeric) st = SPARSH_ENUMERIC;
+        numeric = numeric || st == SPARSH_ENUMERIC;
+        noconv = noconv || st == SPARSH_ENOCONV;
+        const int k = flags[kMultiMax + c];
+        largest = std::max(largest, k);
+        if (status) status[c] = st;
+        if (iters) iters[c] = k;
+        copy_hist_multi(c, k, hist, hist_cap);
     }
+    if (most) *most = largest;
+    if (numeric) {
+        rc = SPARSH_ENUMERIC;
+        error = "NaN residual in a column of the block";
+    } else if (noconv) {
+        rc = SPARSH_ENOCONV;
+        error = "iteration cap reached before ||r|| <= tol in a column of the block";
+    }
+    return fault_ != SPARSH_OK ? fault_ : rc;
+}
+
+// ---------------------------------------------------------------------------- block PCG
+
+int Engine::solve_multi_dev(int nrhs, const double *B, long ldb, double *X, long ldx, int max_iters, double *hist, int hist_cap, int *iters,
+                            int *status, double *seconds)
+{
+    if (int rc = block_begin(nrhs, max_iters); rc != SPARSH_OK) return rc;
+    const int W = mw_, n = lev_[0].n;
+    StreamClock clock(*this, seconds);
     // init: r = b - A x, ||r||, z = M r, rz = z.r, p = z
     launch_interleave(n, nrhs, W, X, ldx, mx_, st_);
     launch_interleave(n, nrhs, W, B, ldb, mr_, st_);
@@ -254,68 +340,22 @@ int Engine::solve_multi_dev(int nrhs, const double *B, long ldb, double *X, long
     HIPCHK(hipMemcpyAsync(mp_, mlev_[0].x, (size_t)n * W * 8, hipMemcpyDeviceToDevice, st_));
 
     int flags[3 * kMultiMax];
-    auto read_flags = [&]() {
-        HIPCHK(hipMemcpyAsync(pinned_, mflags_, sizeof(flags), hipMemcpyDeviceToHost, st_));
-        HIPCHK(hipStreamSynchronize(st_));
-        std::memcpy(flags, pinned_, sizeof(flags));
-    };
-    auto all_frozen = [&]() {
-        for (int c = 0; c < nrhs; ++c)
-            if (!flags[c]) return false;
-        return true;
-    };
-    read_flags();
-    int it = 0;
-    while (!all_frozen() && it < max_iters && fault_ == SPARSH_OK) {
-        const int np = multi_spmv_dot(0, mp_, mAp_, mpart0_);  // Ap = A p ; p.Ap
-        launch_finalize_multi(MFIN_ALPHA, W, nrhs, mpart0_, np, nullptr, 0, ms_, 0, prm_.tol, nullptr, 0, 0, st_);
-        const int nrr = launch_cg_update_multi(n, W, ms_, mp_, mAp_, mx_, mr_, mpart1_, st_);  // x += alpha p ; r -= alpha Ap ; r.r
-        vcycle_multi(mr_);                                                                 // z = M r
-        const int nzr = launch_dot_multi(n, W, mlev_[0].x, mr_, mpart0_, st_);               // z.r
-        launch_finalize_multi(MFIN_BETA_RES, W, nrhs, mpart0_, nzr, mpart1_, nrr, ms_, 0, prm_.tol, mhist_, hist_cap_dev_, std::min(it, hist_cap_dev_ - 1), st_);
-        launch_p_update_multi(n, W, ms_, mlev_[0].x, mp_, st_);  // p = z + beta p
-        ++it;
-        if (it % check_every == 0 || it >= max_iters) {
-            read_flags();
-            if (prm_.print_solve) std::printf("%d\t%d of %d columns running\n", it, (int)std::count(flags, flags + nrhs, 0), nrhs);
-        }
-    }
-    launch_deinterleave(n, nrhs, W, mx_, X, ldx, st_);
-    read_flags();
-    if (seconds) {
-        HIPCHK(hipEventRecord(e1, st_));
-        HIPCHK(hipEventSynchronize(e1));
-        float ms = 0.f;
-        HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-        *seconds = ms * 1e-3;
-        HIPCHK(hipEventDestroy(e0));
-        HIPCHK(hipEventDestroy(e1));
-    }
-    note_hip(hipGetLastError(), "kernel launch during the block solve");
-    if (fault_ != SPARSH_OK) return fault_;
-    int rc = SPARSH_OK;
-    bool numeric = false, noconv = false;
-    for (int c = 0; c < nrhs; ++c) {
-        int st = SPARSH_OK;
-        if (!flags[c]) st = SPARSH_ENOCONV;  // the cap came first: x holds the iterate reached
-        else if (flags[2 * kMultiMax + c] == kMultiStatusNumeric) st = SPARSH_ENUMERIC;
-        numeric = numeric || st == SPARSH_ENUMERIC;
-        noconv = noconv || st == SPARSH_ENOCONV;
-        const int k = flags[kMultiMax + c];
-        if (status) status[c] = st;
-        if (iters) iters[c] = k;
-        const int m = std::min(std::min(k, hist_cap), hist_cap_dev_);
-        if (hist && m > 0)
-            HIPCHK(hipMemcpy(hist + (size_t)c * hist_cap, mhist_ + (size_t)c * hist_cap_dev_, (size_t)m * 8, hipMemcpyDeviceToHost));
-    }
-    if (numeric) {
-        rc = SPARSH_ENUMERIC;
-        error = "NaN residual in a column of the block";
-    } else if (noconv) {
-        rc = SPARSH_ENOCONV;
-        error = "iteration cap reached before ||r|| <= tol in a column of the block";
-    }
-    return fault_ != SPARSH_OK ? fault_ : rc;
+    block_loop(
+        mflags_, flags, 3 * kMultiMax, max_iters, [&] { return std::count(flags, flags + nrhs, 0) > 0; },
+        [&](int it) {
+            const int np = multi_spmv_dot(0, mp_, mAp_, mpart0_);  // Ap = A p ; p.Ap
+            launch_finalize_multi(MFIN_ALPHA, W, nrhs, mpart0_, np, nullptr, 0, ms_, 0, prm_.tol, nullptr, 0, 0, st_);
+            const int nrr = launch_cg_update_multi(n, W, ms_, mp_, mAp_, mx_, mr_, mpart1_, st_);  // x += alpha p ; r -= alpha Ap ; r.r
+            vcycle_multi(mr_);                                                                 // z = M r
+            const int nzr = launch_dot_multi(n, W, mlev_[0].x, mr_, mpart0_, st_);               // z.r
+            launch_finalize_multi(MFIN_BETA_RES, W, nrhs, mpart0_, nzr, mpart1_, nrr, ms_, 0, prm_.tol, mhist_, hist_cap_dev_,
+                                  std::min(it, hist_cap_dev_ - 1), st_);
+            launch_p_update_multi(n, W, ms_, mlev_[0].x, mp_, st_);  // p = z + beta p
+        },
+        [&](int it) { std::printf("%d\t%d of %d columns running\n", it, (int)std::count(flags, flags + nrhs, 0), nrhs); });
+    if (int rc = block_finish(nrhs, mx_, X, ldx, mflags_, flags, 3 * kMultiMax, clock, "kernel launch during the block solve"); rc != SPARSH_OK)
+        return rc;
+    return block_verdict(nrhs, flags, hist, hist_cap, iters, status);
 }
 
 // ---------------------------------------------------------------------------- hooks
