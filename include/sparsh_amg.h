@@ -253,6 +253,18 @@ int sparsh_level_box_threads(sparsh_handle h, int level, int *double_threads, in
  * each, the planner's first; part_cap > 0 bounds the marching kernel's workgroups.  Writes at most cap plans, returns their number
  * (-1: bad kernel). */
 int sparsh_debug_box_plan_candidates(int kernel, int nx, int ny, int nz, int part_cap, int cap, int *plans);
+/* Box-grid levels whose six off-diagonal stencil constants are each 0 or +-2^k, k >= 0 (every level of a constant-coefficient
+ * Laplacian on a uniform grid under pairwise aggregation: -1, -2, -4, ...): the box kernels (double sweep and plane-marching kernel)
+ * evaluate the off-diagonal terms of their stencil sums as one FMA each.  c x is exact for such c unless it overflows, so the FMA
+ * rounds what sum + c x rounds: the same bits wherever the unfused result is finite, six fp64 instructions fewer per point and stage.
+ * The rule is decided once at setup from the coefficients alone.  mode: 1 (default) where the rule holds / 0 never (A/B); may be
+ * called before or after setup, drops a captured graph. */
+int sparsh_set_box_exact_fma(sparsh_handle h, int mode);
+/* on: the level is a box grid and its box kernels run the FMA instances under the current mode; rule: its constants satisfy the rule. */
+int sparsh_level_box_exact_fma(sparsh_handle h, int level, int *on, int *rule);
+/* Debug entry (no handle, no device): the rule on seven stencil constants (-plane, -line, -1, diagonal, +1, +line, +plane; the
+ * diagonal is not looked at).  1 / 0. */
+int sparsh_debug_box_exact_offdiag(const double *c);
 int sparsh_level_double_sweep(sparsh_handle h, int level, int *on, int *dims, int *plan, double *single_us, double *double_us);
 int sparsh_level_constant_diagonal(sparsh_handle h, int level, int *is_const, double *value);
 int sparsh_level_prolong_fused(sparsh_handle h, int level, int *fused);

@@ -149,6 +149,9 @@ def _load():
         "sparsh_set_box_plan": (C.c_int, [H, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
         "sparsh_set_box_plan_ex": (C.c_int, [H, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
         "sparsh_level_box_threads": (C.c_int, [H, C.c_int, c_int_p, c_int_p]),
+        "sparsh_set_box_exact_fma": (C.c_int, [H, C.c_int]),
+        "sparsh_level_box_exact_fma": (C.c_int, [H, C.c_int, c_int_p, c_int_p]),
+        "sparsh_debug_box_exact_offdiag": (C.c_int, [c_dbl_p]),
         "sparsh_debug_box_plan_candidates": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_int_p]),
         "sparsh_op_spmv_dot": (C.c_int, [H, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p]),
         "sparsh_op_jacobi_dot": (C.c_int, [H, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p]),
@@ -457,6 +460,15 @@ def box_plan_candidates(kernel, nx, ny, nz, part_cap=0):
     return [tuple(buf[4 * i:4 * i + 4]) for i in range(min(n, cap))]
 
 
+def box_exact_offdiag(c):
+    """Debug hook (host only): whether the six off-diagonal constants of the 7-point stencil c = (-plane, -line, -1, diagonal, +1, +line,
+    +plane) are each 0 or +-2^k, k >= 0 -- the rule under which the box kernels fuse their off-diagonal terms (set_box_exact_fma)."""
+    c = np.ascontiguousarray(c, dtype=np.float64)
+    if c.shape != (7,):
+        raise ValueError("seven stencil constants")
+    return bool(lib.sparsh_debug_box_exact_offdiag(_dp(c)))
+
+
 def eig_small(GA, GB, k):
     """Debug hook (host only): the Rayleigh-Ritz step of the eigensolver on the pencil (GA, GB) of order m <= 24.  Returns
     (breakdown, theta[k], C (m, k))."""
@@ -642,6 +654,18 @@ class sp_matrix_mg:
         a, b = C.c_int(0), C.c_int(0)
         _check(lib.sparsh_level_box_threads(self._h, int(level), C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    def set_box_exact_fma(self, mode=1):
+        """Box-grid levels whose off-diagonal stencil constants are all 0 or +-2^k, k >= 0: the box kernels' off-diagonal terms as one
+        FMA each (same bits): 0 never, 1 where the rule holds (default).  Before or after setup."""
+        _check(lib.sparsh_set_box_exact_fma(self._h, int(mode)))
+        return self
+
+    def level_box_exact_fma(self, level):
+        """Whether `level`'s box kernels run the FMA instances under the current mode."""
+        on, rule = C.c_int(0), C.c_int(0)
+        _check(lib.sparsh_level_box_exact_fma(self._h, int(level), C.byref(on), C.byref(rule)))
+        return bool(on.value)
 
     def set_constant_diagonal(self, enable=True):
         """Levels with one constant diagonal: the zero-guess sweeps take it as an argument instead of streaming diag[]."""

@@ -1,6 +1,8 @@
 #include "box_plan.hpp"
 
 #include <algorithm>
+#include <cstdint>
+#include <cstring>
 
 namespace sparsh {
 
@@ -128,6 +130,20 @@ std::vector<BoxPlan> box_plan_candidates(int kernel, int nx, int ny, int nz, int
         out.swap(kept);
     }
     return out;
+}
+
+bool box_exact_offdiag(const double *c)
+{
+    for (int u = 0; u < 7; ++u) {
+        if (u == 3) continue;
+        std::uint64_t bits;
+        std::memcpy(&bits, &c[u], sizeof bits);
+        const std::uint64_t mag = bits & 0x7fffffffffffffffull;
+        if (mag == 0) continue;  // +-0.0
+        const unsigned exponent = (unsigned)(mag >> 52);
+        if ((mag & 0x000fffffffffffffull) != 0 || exponent < 1023 || exponent == 2047) return false;
+    }
+    return true;
 }
 
 }  // namespace sparsh

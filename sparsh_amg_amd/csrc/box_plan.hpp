@@ -46,4 +46,11 @@ BoxPlan box_planner(int kernel, int nx, int ny, int nz, bool shared_cu = false);
 // launches more than part_cap workgroups (part_cap <= 0: no bound).
 std::vector<BoxPlan> box_plan_candidates(int kernel, int nx, int ny, int nz, int part_cap);
 
+// Whether the six off-diagonal constants c[0..2], c[4..6] of a box-grid stencil (BoxArgs::c; the diagonal c[3] is not looked at) let the
+// kernels fuse sum + c x into one FMA without changing a bit: each is 0.0 or finite with |c| = 2^k, k >= 0 (mantissa field zero, biased
+// exponent from 1023 up).  Then c x is exact unless it overflows -- scaling by a power of two >= 1 rounds nothing, denormals included --
+// and fma(c, x, sum) rounds the same exact value once that sum + c x does.  Magnitudes below 1 do not qualify: c x can then underflow
+// inexactly.  A property of the operator alone.
+bool box_exact_offdiag(const double *c);
+
 }  // namespace sparsh

@@ -528,6 +528,29 @@ int sparsh_level_box_threads(sparsh_handle h, int level, int *double_threads, in
     return SPARSH_OK;
 }
 
+int sparsh_set_box_exact_fma(sparsh_handle h, int mode)
+{
+    if (!h || !h->eng) return fail(SPARSH_EINVAL, "null handle");
+    if (mode < 0 || mode > 1) return fail(SPARSH_EINVAL, "mode must be 0 (never) or 1 (where every off-diagonal constant of the level is 0 or +-2^k, k >= 0)");
+    h->eng->set_box_exact_fma(mode);
+    return SPARSH_OK;
+}
+
+int sparsh_level_box_exact_fma(sparsh_handle h, int level, int *on, int *rule)
+{
+    REQUIRE_READY(h);
+    REQUIRE_LEVEL(h, level);
+    const DevLevel &L = h->eng->level(level);
+    if (on) *on = L.A.box_nx > 0 && L.A.box_fma ? 1 : 0;
+    if (rule) *rule = L.A.box_nx > 0 && L.A.box_exact ? 1 : 0;
+    return SPARSH_OK;
+}
+
+int sparsh_debug_box_exact_offdiag(const double *c)
+{
+    return c && box_exact_offdiag(c) ? 1 : 0;
+}
+
 int sparsh_debug_box_plan_candidates(int kernel, int nx, int ny, int nz, int part_cap, int cap, int *plans)
 {
     if (kernel != 1 && kernel != 2) return -1;

@@ -386,6 +386,8 @@ bool upload_sdia(Engine &E, const HostCsr &A, DevCsr &D)
                     D.box_nz = nz;
                     D.box2 = box_planner(2, nx, ny, nz);
                     D.box1 = box_planner(1, nx, ny, nz);
+                    D.box_exact = box_exact_offdiag(tab.cval);
+                    D.box_fma = D.box_exact && E.kernel_cfg().box_exact_fma != 0;
                 }
             }
         }
@@ -1955,6 +1957,13 @@ int Engine::set_box_plan(int l, int kernel, int threads, int q, int ty, int cz)
     }
     config_changed();
     return SPARSH_OK;
+}
+
+void Engine::set_box_exact_fma(int mode)
+{
+    cfg_.box_exact_fma = mode;
+    for (DevLevel &L : lev_) L.A.box_fma = L.A.box_exact && mode != 0;
+    config_changed();
 }
 
 double Engine::op_resnorm(int l, const double *b, const double *x)

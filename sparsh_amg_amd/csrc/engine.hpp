@@ -332,6 +332,8 @@ public:
     // kernel (1); q = ty = cz = 0: the planner's plan on 1024 threads, kernel 3 = the marching kernel's shared-CU plan.  Refuses (SPARSH_EINVAL, reason in error) what the kernel cannot run or
     // what writes more partials than part0_ / part1_ hold; does not switch the kernel on
     int set_box_plan(int l, int kernel, int threads, int q, int ty, int cz);
+    // KernelConfig::box_exact_fma = mode (0 never, 1 where DevCsr::box_exact holds), applied to every level that exists; before or after setup
+    void set_box_exact_fma(int mode);
     // fuse_zero: also write the coarse level's zero-guess sweep (aggregation P, no gather step); returns whether it did
     bool op_restrict(int l, const double *r, double *bc, bool fuse_zero = false);
     // level_paired(l) levels: b_{l+1} = R (b - A x) and x_{l+1} = omega b_{l+1} / d_{l+1} in one launch

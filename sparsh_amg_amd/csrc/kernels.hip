@@ -1352,9 +1352,16 @@ struct BoxArgs {
     double omega;
 };
 
+// One off-diagonal term of a stencil sum.  XF (the level's DevCsr::box_fma: every off-diagonal constant is 0 or +-2^k, k >= 0,
+// box_exact_offdiag): c x is then exact unless it overflows, so the one rounding of fma(c, x, sum) is the one of sum + c x -- the same bits
+// wherever the unfused sum is finite, zero signs included (a product of -0.0 leaves sum alone either way, and +0.0 + -0.0 = +0.0 in both).
+// The fusion is written out; the file is still compiled with -ffp-contract=off.  (A macro on the kernels' XF and sum, not a function: the
+// condition is a constant, so the XF = false instances are the statement `sum + c * x` as it stood, the same code instruction for instruction.)
+#define BOX_TERM(c, x) (XF ? __builtin_fma((c), (x), sum) : sum + (c) * (x))
+
 // ZERO: the leg starts from a zero guess -- x0 is not read: the first (matrix-free) sweep x1 = omega b / d is evaluated where x0 would be
 // loaded, from the right-hand side the stages need anyway, so the launch performs the first THREE sweeps of the leg (y = J(J(omega b / d)))
-template <int BS, int Q, int TAG, bool ZERO>
+template <int BS, int Q, int TAG, bool ZERO, bool XF>
 __global__ __launch_bounds__(BS) void sdia_box2_kernel(BoxArgs g, const double *__restrict__ x, const double *__restrict__ b,
                                                         double *__restrict__ y)
 {
@@ -1450,13 +1457,13 @@ __global__ __launch_bounds__(BS) void sdia_box2_kernel(BoxArgs g, const double *
             if (plane && v1[q]) {
                 const int s = sidx[q];
                 double sum = 0.0;
-                sum = sum + c0 * xm[q];
-                sum = sum + c1 * X0[s - pitch];
-                sum = sum + c2 * X0[s - 1];
+                sum = BOX_TERM(c0, xm[q]);
+                sum = BOX_TERM(c1, X0[s - pitch]);
+                sum = BOX_TERM(c2, X0[s - 1]);
                 sum = sum + c3 * xc[q];
-                sum = sum + c4 * X0[s + 1];
-                sum = sum + c5 * X0[s + pitch];
-                sum = sum + c6 * xp[q];
+                sum = BOX_TERM(c4, X0[s + 1]);
+                sum = BOX_TERM(c5, X0[s + pitch]);
+                sum = BOX_TERM(c6, xp[q]);
                 const double h = 1.0 * bk[q] + (-1.0) * sum;
                 x1k[q] = xc[q] + div_const(om * h, dc);
             }
@@ -1469,13 +1476,13 @@ __global__ __launch_bounds__(BS) void sdia_box2_kernel(BoxArgs g, const double *
                 if (v2[q]) {
                     const int s = sidx[q];
                     double sum = 0.0;
-                    sum = sum + c0 * x1m[q];
-                    sum = sum + c1 * X1[s - pitch];
-                    sum = sum + c2 * X1[s - 1];
+                    sum = BOX_TERM(c0, x1m[q]);
+                    sum = BOX_TERM(c1, X1[s - pitch]);
+                    sum = BOX_TERM(c2, X1[s - 1]);
                     sum = sum + c3 * x1c[q];
-                    sum = sum + c4 * X1[s + 1];
-                    sum = sum + c5 * X1[s + pitch];
-                    sum = sum + c6 * x1k[q];
+                    sum = BOX_TERM(c4, X1[s + 1]);
+                    sum = BOX_TERM(c5, X1[s + pitch]);
+                    sum = BOX_TERM(c6, x1k[q]);
                     const double h = 1.0 * bp[q] + (-1.0) * sum;
                     y[(long)k2 * P + base + p] = x1c[q] + div_const(om * h, dc);
                 }
@@ -1523,7 +1530,7 @@ struct Box1Args {
     double *partial;         // one per workgroup (the reducing epilogues)
 };
 
-template <int BS, int Q, int EPI, int TAG>
+template <int BS, int Q, int EPI, int TAG, bool XF>
 __global__ __launch_bounds__(BS) void sdia_box1_kernel(BoxArgs g, Box1Args a)
 {
     extern __shared__ double box_lds[];
@@ -1598,13 +1605,13 @@ __global__ __launch_bounds__(BS) void sdia_box1_kernel(BoxArgs g, Box1Args a)
             const long row = (long)k * P + base + p;
             double sum = 0.0;
             if (v1[q]) {
-                sum = sum + c0 * xm[q];
-                sum = sum + c1 * X0[s - pitch];
-                sum = sum + c2 * X0[s - 1];
+                sum = BOX_TERM(c0, xm[q]);
+                sum = BOX_TERM(c1, X0[s - pitch]);
+                sum = BOX_TERM(c2, X0[s - 1]);
                 sum = sum + c3 * xc[q];
-                sum = sum + c4 * X0[s + 1];
-                sum = sum + c5 * X0[s + pitch];
-                sum = sum + c6 * xp[q];
+                sum = BOX_TERM(c4, X0[s + 1]);
+                sum = BOX_TERM(c5, X0[s + pitch]);
+                sum = BOX_TERM(c6, xp[q]);
             }
             if constexpr (EPI == BOX_SPMV_DOT) {
                 if (v1[q]) {
@@ -1673,6 +1680,8 @@ __global__ __launch_bounds__(BS) void sdia_box1_kernel(BoxArgs g, Box1Args a)
         }
     }
 }
+
+#undef BOX_TERM
 
 // Residual + restriction (+ the coarse level's zero-guess sweep) on a box-grid level whose aggregates pair a grid point with its
 // neighbour one line (AXIS 1) or one plane (AXIS 2) up, coarse points numbered lexicographically: one thread per aggregate computes
@@ -1988,14 +1997,19 @@ BoxArgs box_args(const DevCsr &A, double omega, const BoxPlan &p = {})
     return g;
 }
 
-// f(BS, Q) with the plan's threads (256, 512, else 1024) and points per thread (4, 3, else 2) as compile-time constants
+// f(BS, Q, XF) with the plan's threads (256, 512, else 1024), points per thread (4, 3, else 2) and the level's exact-FMA flag
+// (DevCsr::box_fma) as compile-time constants
 template <class F>
-void box_dispatch(const BoxPlan &p, F &&f)
+void box_dispatch(const BoxPlan &p, bool fma, F &&f)
 {
     auto with_q = [&](auto bs) {
-        if (p.q == 4) f(bs, std::integral_constant<int, 4>{});
-        else if (p.q == 3) f(bs, std::integral_constant<int, 3>{});
-        else f(bs, std::integral_constant<int, 2>{});
+        auto with_xf = [&](auto q) {
+            if (fma) f(bs, q, std::true_type{});
+            else f(bs, q, std::false_type{});
+        };
+        if (p.q == 4) with_xf(std::integral_constant<int, 4>{});
+        else if (p.q == 3) with_xf(std::integral_constant<int, 3>{});
+        else with_xf(std::integral_constant<int, 2>{});
     };
     if (p.threads == 256) with_q(std::integral_constant<int, 256>{});
     else if (p.threads == 512) with_q(std::integral_constant<int, 512>{});
@@ -2026,10 +2040,11 @@ int launch_box1(const DevCsr &A, int epi, const CsrArgs &a, bool finest, hipStre
     const dim3 grid(nwg), block(A.box1.threads);
     const size_t lds = box_lds_bytes(1, g.nx, g.TY);
     auto launch = [&](auto e) {
-        box_dispatch(A.box1, [&](auto bs, auto q) {
+        box_dispatch(A.box1, A.box_fma, [&](auto bs, auto q, auto xf) {
             constexpr int BS = decltype(bs)::value, Q = decltype(q)::value, E = decltype(e)::value;
-            if (finest) hipLaunchKernelGGL((sdia_box1_kernel<BS, Q, E, 1>), grid, block, lds, st, g, b);
-            else hipLaunchKernelGGL((sdia_box1_kernel<BS, Q, E, 0>), grid, block, lds, st, g, b);
+            constexpr bool XF = decltype(xf)::value;
+            if (finest) hipLaunchKernelGGL((sdia_box1_kernel<BS, Q, E, 1, XF>), grid, block, lds, st, g, b);
+            else hipLaunchKernelGGL((sdia_box1_kernel<BS, Q, E, 0, XF>), grid, block, lds, st, g, b);
         });
     };
     switch (epi) {
@@ -2052,14 +2067,15 @@ void launch_box2(const DevCsr &A, const double *x, const double *b, double *y, d
     const BoxArgs g = box_args(A, omega, A.box2);
     const dim3 grid(A.box2.workgroups(g.ny, g.nz)), block(A.box2.threads);
     const size_t lds = box_lds_bytes(2, g.nx, g.TY);
-    box_dispatch(A.box2, [&](auto bs, auto q) {
+    box_dispatch(A.box2, A.box_fma, [&](auto bs, auto q, auto xf) {
         constexpr int BS = decltype(bs)::value, Q = decltype(q)::value;
+        constexpr bool XF = decltype(xf)::value;
         if (from_zero) {
-            if (finest) hipLaunchKernelGGL((sdia_box2_kernel<BS, Q, 1, true>), grid, block, lds, st, g, x, b, y);
-            else hipLaunchKernelGGL((sdia_box2_kernel<BS, Q, 0, true>), grid, block, lds, st, g, x, b, y);
+            if (finest) hipLaunchKernelGGL((sdia_box2_kernel<BS, Q, 1, true, XF>), grid, block, lds, st, g, x, b, y);
+            else hipLaunchKernelGGL((sdia_box2_kernel<BS, Q, 0, true, XF>), grid, block, lds, st, g, x, b, y);
         } else {
-            if (finest) hipLaunchKernelGGL((sdia_box2_kernel<BS, Q, 1, false>), grid, block, lds, st, g, x, b, y);
-            else hipLaunchKernelGGL((sdia_box2_kernel<BS, Q, 0, false>), grid, block, lds, st, g, x, b, y);
+            if (finest) hipLaunchKernelGGL((sdia_box2_kernel<BS, Q, 1, false, XF>), grid, block, lds, st, g, x, b, y);
+            else hipLaunchKernelGGL((sdia_box2_kernel<BS, Q, 0, false, XF>), grid, block, lds, st, g, x, b, y);
         }
     });
 }

@@ -85,6 +85,10 @@ struct DevCsr {
     // the same for the single-stage kernel of the launches that carry an epilogue (sdia_box1_kernel): plan and the setup's verdict
     BoxPlan box1;
     bool box1_on = false;
+    // box_exact = the stencil's off-diagonal constants are all 0 or +-2^k, k >= 0 (box_exact_offdiag: decided at setup from sd_tab.cval,
+    // the operator alone); box_fma = box_exact under KernelConfig::box_exact_fma: both box kernels then take the instances whose
+    // off-diagonal terms are one FMA each -- the same bits, six fp64 instructions fewer per point and stage
+    bool box_exact = false, box_fma = false;
     // rank-local blocks: slices whose rows touch no halo column (interior) / some (boundary)
     int *int_list = nullptr, *bnd_list = nullptr;
     int nint = 0, nbnd = 0;
@@ -121,6 +125,8 @@ struct KernelConfig {
                                // measured it faster than the table kernel (levels of >= 400 000 rows), 2 wherever a plan exists
     int box2 = 1;              // box-grid levels (DevCsr::box_nx): two Jacobi sweeps per launch (sdia_box2_kernel): 0 never, 1 where the
                                // setup measured it faster than two single sweeps (levels of >= 400 000 rows), 2 wherever a plan exists
+    int box_exact_fma = 1;     // box-grid levels: the off-diagonal terms of the box kernels' stencil sums as one FMA each (DevCsr::box_fma):
+                               // 0 never, 1 where the level's constants make that exact (DevCsr::box_exact)
     bool const_diag = true;    // levels whose diagonal is one constant: the vector kernels that divide by it (zero-guess sweeps fused
                                // into cg_update / the restriction) take it as an argument instead of streaming diag[]
     bool fuse_prolong = true;  // V-cycle: the last post-sweep of a level adds its result to the finer level's iterate itself

@@ -6,7 +6,8 @@
   hipcc --offload-arch=gfx950 -std=c++17 -O3 -fPIC -fopenmp -ffp-contract=off --cuda-device-only -S kernels.hip -o kernels.s
   python tools/box_step_valu_count.py [tag=]kernels.s [[tag=]other.s ...]
 
-For the instances <512, 3, 0, false> and <1024, 4, 1, false> (or those named with --instance BS,Q,TAG,ZERO): the plane loop is the
+For the instances <512, 3, 0, false> and <1024, 4, 1, false> (or those named with --instance BS,Q,TAG,ZERO[,XF]; XF, the exact-FMA
+parameter, defaults to 1 and is ignored for an assembly file from before the kernels had it): the plane loop is the
 loop of the function with the most basic blocks (the compiler marks them "in Loop: Header=..."); its blocks that hold a v_rcp_f64
 are the plain-division fallback of div_const and are counted apart.  Counted: all instructions, those whose mnemonic starts with v_
 (VALU), and of those the ones on fp64 operands (mnemonic contains f64).  Static counts of the loop's code, not executed instructions.
@@ -41,15 +42,21 @@ def plane_loop(blocks):
 
 
 def report(tag, path, inst):
-    bs, q, t, zero = inst
-    symbol = f"_ZN6sparsh12_GLOBAL__N_116sdia_box2_kernelILi{bs}ELi{q}ELi{t}ELb{zero}EEEvNS0_7BoxArgsEPKdS4_Pd"
-    loop = plane_loop(basic_blocks(function_lines(path, symbol)))
+    bs, q, t, zero, xf = inst
+    symbol = f"_ZN6sparsh12_GLOBAL__N_116sdia_box2_kernelILi{bs}ELi{q}ELi{t}ELb{zero}ELb{xf}EEEvNS0_7BoxArgsEPKdS4_Pd"
+    name = f"<{bs}, {q}, {t}, {'true' if zero else 'false'}, {'true' if xf else 'false'}>"
+    try:
+        lines = function_lines(path, symbol)
+    except StopIteration:  # an assembly file from before the exact-FMA parameter
+        lines = function_lines(path, symbol.replace(f"ELb{zero}ELb{xf}EEEv", f"ELb{zero}EEEv"))
+        name = f"<{bs}, {q}, {t}, {'true' if zero else 'false'}>"
+    loop = plane_loop(basic_blocks(lines))
     fallback = [b for b in loop if "v_rcp_f64_e32" in b["ins"]]
     ins = [x for b in loop if b not in fallback for x in b["ins"]]
     valu = [x for x in ins if x.startswith("v_")]
     f64 = collections.Counter(x for x in valu if "f64" in x)
     fb_valu = sum(x.startswith("v_") for b in fallback for x in b["ins"])
-    print(f"{tag:8s} <{bs}, {q}, {t}, {'true' if zero else 'false'}>: plane step without the plain-division fallback: {len(ins)} instructions, "
+    print(f"{tag:8s} {name}: plane step without the plain-division fallback: {len(ins)} instructions, "
           f"{len(valu)} VALU, {sum(f64.values())} of them fp64-class; fallback: {len(fallback)} blocks, {fb_valu} VALU")
     print(f"{'':8s} fp64-class by opcode: " + ", ".join(f"{k} {f64[k]}" for k in sorted(f64)))
 
@@ -57,9 +64,9 @@ def report(tag, path, inst):
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("asm", nargs="+", help="[tag=]path of a device assembly file of kernels.hip")
-    ap.add_argument("--instance", action="append", help="BS,Q,TAG,ZERO (ZERO 0 or 1); default 512,3,0,0 and 1024,4,1,0")
+    ap.add_argument("--instance", action="append", help="BS,Q,TAG,ZERO[,XF] (ZERO, XF 0 or 1; XF defaults to 1); default 512,3,0,0 and 1024,4,1,0")
     args = ap.parse_args()
-    insts = [tuple(int(v) for v in s.split(",")) for s in (args.instance or ["512,3,0,0", "1024,4,1,0"])]
+    insts = [(tuple(int(v) for v in s.split(",")) + (1,))[:5] for s in (args.instance or ["512,3,0,0", "1024,4,1,0"])]
     for inst in insts:
         for a in args.asm:
             tag, _, path = a.rpartition("=")
